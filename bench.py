@@ -18,16 +18,26 @@ fewer GPUs than ranks several ranks share one GPU, and config.ranks_per_gpu
 says so (such a line rehearses the split; it is not a scaling point).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload lineitem_full]
-                    [--scale 100] [--cpu-seconds 10] [--e2e-scale 10]
+                    [--scale 100] [--dump-outputs DIR]
+                    [--full [--cpu-seconds 10] [--e2e-scale 10] [--no-verify] [--no-traffic]]
 
 --gpus N without a torch.distributed launcher starts N ranks itself (one
 process per GPU, before this process touches a GPU); under torchrun the
-launcher's RANK / LOCAL_RANK / WORLD_SIZE are used.  Every rank checks every
-decoded value of its shard on its GPU against the seeded generator
-(libflscheck.so) after the timed region.  Rank 0 of a 1-GPU run also times
-the CPU baseline (a FastLanes-shaped CPU decoder, oracle/flsfast.cpp, on the
-host's cores) and the end-to-end rates into pinned host memory / DuckDB
-DataChunks, which are never `value`.
+launcher's RANK / LOCAL_RANK / WORLD_SIZE are used.
+
+A plain run does what `value` needs and no more: encode, upload, warm up,
+time the steps, print the line.  --dump-outputs DIR then also writes a fixed,
+seeded sample of the decoded columns as they stand after the last timed step
+(dump_outputs below), so two builds can be compared output for output.
+
+--full adds everything else, none of which is ever `value`: every rank checks
+every decoded value of its shard on its GPU against the seeded generator
+(libflscheck.so) after the timed region, and rank 0 of a 1-GPU run measures
+the HBM traffic per launch (rocprofv3 --pmc child passes), times the CPU
+baseline (a FastLanes-shaped CPU decoder, oracle/flsfast.cpp, on the host's
+cores) and the end-to-end rates into pinned host memory / DuckDB DataChunks.
+Its upload also runs the library's placement search, which a plain run
+switches off (PLAIN_PLACEMENT below).
 """
 from __future__ import annotations
 
@@ -46,11 +56,19 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
+T_START = time.perf_counter()
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s)
 HBM_ACHIEVABLE_GBS = 6290.0  # measured achievable per GPU (MI355X_MICROARCH.md; SURVEY.md 8(d) "also vs 6.29")
 PCIE_GBS = 63.0         # PCIe Gen5 x16 per GPU, spec (MI355X_MICROARCH.md)
 WORKLOADS = ["lineitem_full", "lineitem", "lineitem_dbl", "c1", "c3", "c4"]
+# A plain run's upload keeps the resident buffers where the first allocation put
+# them, unless the environment says otherwise.  The library's default search
+#  allocates the whole decoded table again for every
+# further placement it rates: 3-6 s each at SF100, 15-22 s for the default six,
+# for a step 1.4 % faster (20.98 against 21.27 ms, three interleaved runs each
+# on one box).  --full leaves the default in place.
+PLAIN_PLACEMENT = {"FLS_PLACEMENT_DECODE": "0", "FLS_PLACEMENT_TRIES": "1"}
 
 
 def parse(argv=None):
@@ -61,20 +79,28 @@ def parse(argv=None):
     p.add_argument("--workload", default="lineitem_full", choices=WORKLOADS)
     p.add_argument("--scale", type=float, default=100.0, help="lineitem scale factor")
     p.add_argument("--rows", type=int, default=0, help="row override (c1/c3/c4; 0 = config default)")
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (0 = skip)")
+    p.add_argument("--full", action="store_true",
+                   help="also verify every decoded value and measure the PMC traffic, the CPU baseline and the "
+                        "end-to-end rates (the options below trim these)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write a seeded sample of the decoded columns after the last timed step as DIR/<name>.npy")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline budget (0 = skip)")
     p.add_argument("--e2e-scale", type=float, default=10.0,
-                   help="scale of the end-to-end (pinned host / DataChunk) measurement (0 = skip)")
+                   help="--full: scale of the end-to-end (pinned host / DataChunk) measurement (0 = skip)")
     p.add_argument("--threads", type=int, default=0, help="host threads for encode / CPU baseline (0 = host cores)")
-    p.add_argument("--no-verify", action="store_true", help="skip the full-shard GPU check")
+    p.add_argument("--no-verify", action="store_true", help="--full: skip the full-shard GPU check")
     p.add_argument("--no-traffic", action="store_true",
-                   help="skip the rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child passes")
+                   help="--full: skip the rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child passes")
     p.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--e2e-child", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--dry-run", action="store_true",
                    help="launcher rehearsal on CPU: ranks, shards and the cross-rank reduction over gloo; "
                         "no GPU, no decode (tests/test_bench_launcher.py)")
     p.add_argument("--dry-run-node-gpus", type=int, default=0, help=argparse.SUPPRESS)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def log(*a):
@@ -372,6 +398,113 @@ def verify_full(fl, t, args) -> tuple[int, int]:
     return int(sum(mism)), int(t.device_rows) * t.ncols
 
 
+# ---- --dump-outputs -----------------------------------------------------------
+DUMP_SEED = 20240607
+DUMP_BLOCKS = 32      # sampled row blocks, the shard's first and last rows among them
+DUMP_BLOCK_ROWS = 4096
+
+
+def dump_blocks(nrows: int) -> list[tuple[int, int]]:
+    """The sampled row ranges [(first row, rows)] of a shard of nrows rows: a
+    function of nrows alone, so two runs with the same arguments sample the
+    same rows.  A shard no larger than the sample is taken whole."""
+    if nrows <= DUMP_BLOCKS * DUMP_BLOCK_ROWS:
+        return [(0, nrows)] if nrows else []
+    rng = np.random.default_rng(DUMP_SEED)
+    starts = {0, nrows - DUMP_BLOCK_ROWS}
+    while len(starts) < DUMP_BLOCKS:
+        starts.add(int(rng.integers(0, nrows - DUMP_BLOCK_ROWS)))
+    return [(s, DUMP_BLOCK_ROWS) for s in sorted(starts)]
+
+
+def dump_outputs(fl, t, dev: int, outdir: Path, rank: int, world: int) -> dict:
+    """Write a sample of what the last timed step left in HBM, the resident
+    decoded columns a caller reads through fls_device_column / fls_device_heap,
+    as outdir/<column>.npy (float64: every lineitem integer is exact in it).
+    A string column goes out as <column>.len.npy (float64 lengths) and
+    <column>.bytes.npy (float32, the sampled strings' bytes back to back),
+    never as its string_t records, whose pointers differ from run to run.
+    The sample is dump_blocks(): 32 blocks of 4,096 rows, about 30 MB for the
+    16-column lineitem.  Ranks of a multi-rank run prefix their files r<rank>_."""
+    import ctypes as C
+
+    def d2h(dst: np.ndarray, src: int):
+        if dst.nbytes:
+            fl._check(fl.lib.fls_device_memcpy(dev, dst.ctypes.data, src, dst.nbytes, 1))
+
+    blocks = dump_blocks(int(t.device_rows))
+    outdir.mkdir(parents=True, exist_ok=True)
+    prefix = f"r{rank}_" if world > 1 else ""
+    files, total = [], 0
+
+    def save(name: str, a: np.ndarray):
+        nonlocal total
+        np.save(outdir / f"{prefix}{name}.npy", a)
+        files.append(f"{prefix}{name}.npy")
+        total += a.nbytes
+
+    for c in range(t.ncols):
+        ci = t.column(c)
+        name, ob = ci.name.decode(), ci.out_bytes
+        base, _ = t.device_column(c)
+        raw = [np.empty(n * ob, dtype=np.uint8) for _, n in blocks]
+        for (row, _), buf in zip(blocks, raw):
+            d2h(buf, base + row * ob)
+        if ci.type not in fl.STRING_TYPES:
+            dt = np.dtype(fl.NP_DTYPE[ci.type])
+            if dt.itemsize != ob:
+                dt = np.dtype({1: np.int8, 2: np.int16, 4: np.int32, 8: np.int64}[ob])
+            save(name, np.concatenate(raw).view(dt).astype(np.float64))
+            continue
+        # string_t: u32 length, then 12 inline bytes, or a 4-byte prefix and a
+        # host pointer: into the host mirror of the column's FSST heap (the
+        # bytes are read from the HBM heap at the same offset) or into the
+        # host image's dictionary
+        dp, hp, hn = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        has_heap = fl._check(fl.lib.fls_device_heap(t.h, c, C.byref(dp), C.byref(hp), C.byref(hn))) == 1
+        d_heap, h_heap, heap_n = dp.value or 0, hp.value or 0, hn.value
+        lens_all, bytes_all = [], []
+        for buf in raw:
+            rec = buf.reshape(-1, 16)
+            lens = rec[:, :4].copy().view(np.uint32).ravel().astype(np.int64)
+            ptrs = rec[:, 8:16].copy().view(np.uint64).ravel()
+            long_ = lens > 12
+            chars = np.zeros(int(lens.sum()), dtype=np.uint8)
+            at = np.concatenate(([0], np.cumsum(lens)))[:-1]
+            # inline strings
+            idx = np.flatnonzero(~long_ & (lens > 0))
+            if len(idx):
+                k = np.arange(12)
+                m = k[None, :] < lens[idx, None]
+                chars[(at[idx, None] + k[None, :])[m]] = rec[idx, 4:16][m]
+            idx = np.flatnonzero(long_)
+            in_heap = (ptrs[idx] >= np.uint64(h_heap)) & (ptrs[idx] < np.uint64(h_heap + heap_n)) \
+                if has_heap else np.zeros(len(idx), dtype=bool)
+            host, idx = idx[~in_heap], idx[in_heap]
+            if len(idx):
+                off = (ptrs[idx] - np.uint64(h_heap)).astype(np.int64)
+                lo, hi = int(off.min()), int((off + lens[idx]).max())
+                assert hi <= heap_n and hi - lo <= (1 << 28), "string heap span of a sampled block out of range"
+                span = np.empty(hi - lo, dtype=np.uint8)
+                d2h(span, d_heap + lo)
+                rep = np.repeat(np.arange(len(idx)), lens[idx])
+                within = np.arange(len(rep)) - np.repeat(np.cumsum(lens[idx]) - lens[idx], lens[idx])
+                chars[at[idx][rep] + within] = span[(off - lo)[rep] + within]
+            for p in np.unique(ptrs[host]):   # dictionary strings: a handful of distinct host strings
+                rows = host[ptrs[host] == p]
+                n = int(lens[rows[0]])
+                assert (lens[rows] == n).all()
+                chars[at[rows, None] + np.arange(n)[None, :]] = np.frombuffer(C.string_at(int(p), n), np.uint8)
+            lens_all.append(lens)
+            bytes_all.append(chars)
+        save(name + ".len", np.concatenate(lens_all).astype(np.float64))
+        save(name + ".bytes", np.concatenate(bytes_all).astype(np.float32))
+    return {"dir": str(outdir), "files": files, "bytes": total, "seed": DUMP_SEED,
+            "rows": int(sum(n for _, n in blocks)), "blocks": len(blocks),
+            "sample": "the shard's first and last rows and seeded blocks between them, in row order; "
+                      "every row when the shard is smaller than the sample"}
+
+
 # ---- cross-rank reduction -----------------------------------------------------
 # per-rank record: [seconds, values, achieved GB/s, kernel ms, algorithmic
 # bytes per launch, mismatching values, values checked, row groups]
@@ -479,7 +612,9 @@ def main(argv=None):
     under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith("ROCPROF") for k in os.environ)
     if under_profiler:
         traffic_note = "not measured (already running under rocprofv3)"
-    if world == 1 and not args.no_traffic and not args.pmc_child and not under_profiler:
+    if not args.full:
+        traffic_note = "not measured (plain run; --full measures it)"
+    if args.full and world == 1 and not args.no_traffic and not args.pmc_child and not under_profiler:
         traffic, traffic_note = measure_traffic(args)
         log(f"[traffic] {traffic_note}")
     if args.e2e_child:
@@ -491,11 +626,13 @@ def main(argv=None):
     # would, not among the HBM the metric's upload allocated and rated
     # 
     e2e = None
-    if rank == 0 and world == 1 and args.e2e_scale > 0 and not args.pmc_child:
+    if args.full and rank == 0 and world == 1 and args.e2e_scale > 0 and not args.pmc_child:
         e2e = e2e_child(args)
 
+    t_imp = time.perf_counter()
     import torch  # torch first: its HIP runtime is the one the engine binds to
     import torch.distributed as dist
+    log(f"[rank {rank}] imported torch in {time.perf_counter() - t_imp:.1f} s")
 
     dist_on = world > 1
     if dist_on:
@@ -511,6 +648,9 @@ def main(argv=None):
         log(f"[launcher] {world} ranks on {len(set(gpu_ids))} GPU(s): {rpg} ranks share a GPU "
             f"(a rehearsal of the {world}-way split, not a scaling point)")
 
+    if not args.full:
+        for k, v in PLAIN_PLACEMENT.items():
+            os.environ.setdefault(k, v)
     import pkgload
     fl = pkgload.load()
     cores = host_cores()
@@ -555,8 +695,16 @@ def main(argv=None):
     algo = st.algo_bytes
     achieved = algo / (avg_ms * 1e-3) / 1e9
 
+    dumped = None
+    if args.dump_outputs:
+        t_dump = time.perf_counter()
+        dumped = dump_outputs(fl, t, dev, Path(args.dump_outputs), rank, world)
+        log(f"[rank {rank}] wrote {len(dumped['files'])} arrays ({dumped['bytes'] / 1e6:.1f} MB) to "
+            f"{args.dump_outputs} in {time.perf_counter() - t_dump:.1f} s")
+
+    verify = args.full and not args.no_verify
     bad, checked = 0, 0
-    if not args.no_verify:
+    if verify:
         bad, checked = verify_full(fl, t, args)
         if bad:
             log(f"[rank {rank}] VERIFY FAILED: {bad} of {checked} values differ from the generator")
@@ -570,7 +718,7 @@ def main(argv=None):
 
     ncols_main = t.ncols
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(fl, args, nthreads, nrows, cores)
 
     if rank == 0:
@@ -581,10 +729,12 @@ def main(argv=None):
                "ranks_per_gpu": rpg, "physical_gpus": len(set(gpu_ids)),
                "step": "one decode launch over all resident vectors of the shard (HBM -> HBM)",
                "compressed_bytes_rank0": img.len, "decoded_bytes_rank0": int(st.out_bytes),
+               "placement_search": {k: fl.config()[k][1] for k in PLAIN_PLACEMENT},
                "verified_values_bit_exact": checked_total if (bad_total == 0 and checked_total > 0) else 0,
                "verified_mismatches": bad_total,
                "verification": "every decoded value of every rank's shard vs the seeded generator, on the GPU "
-                               "(libflscheck.so)" if not args.no_verify else "skipped (--no-verify)"}
+                               "(libflscheck.so)" if verify else
+                               "skipped (--no-verify)" if args.full else "skipped (plain run; --full verifies)"}
         line = {
             "metric": f"decoded values/sec ({args.workload}" + (f" SF{args.scale:g} full scan)" if big else ")"),
             "value": total_vals / dt,
@@ -622,8 +772,12 @@ def main(argv=None):
                          for i, r in enumerate(per_rank)] if world > 1 else None,
             "e2e": e2e,
             "cpu_baseline": cpu,
+            "full": args.full,
+            "dump": dumped,
         }
         print(json.dumps(line), flush=True)
+        log(f"[rank 0] result line {time.perf_counter() - T_START:.1f} s after start, "
+            f"{(args.steps + args.warmup) * dt / args.steps:.1f} s of them in warm-up and steps")
     if dist_on:
         dist.destroy_process_group()
     if bad_total:

@@ -53,7 +53,7 @@ for mode in "$@"; do
     k=${mode#pytest:}
     step 600 $O/pytest_${k//[^A-Za-z0-9_]/_}_$TAG.log $PYT -k "$k" || exit $? ;;
   bench)
-    timeout -k 10 500 python bench.py > $O/bench_$TAG.json 2> $O/bench_$TAG.log
+    timeout -k 10 500 python bench.py --full > $O/bench_$TAG.json 2> $O/bench_$TAG.log
     rc=$?; echo "[$TAG] bench rc=$rc"; cat $O/bench_$TAG.json; [ $rc -eq 0 ] || exit $rc
     step 400 $O/prof_$TAG.log rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -o kt --output-format csv -- \
         python3 bench.py --steps 20 --cpu-seconds 0 --e2e-scale 0 --no-verify --no-traffic || exit $?
@@ -65,7 +65,7 @@ for mode in "$@"; do
     python3 scripts/trace_span.py "$kt" --algo-bytes "$ab" > $O/step_spans_$TAG.txt && tail -2 $O/step_spans_$TAG.txt ;;
   shares)
     for sf in 25 12.5; do
-      timeout -k 10 400 python bench.py --scale $sf --steps 20 --cpu-seconds 0 --e2e-scale 0 --no-traffic \
+      timeout -k 10 400 python bench.py --full --scale $sf --steps 20 --cpu-seconds 0 --e2e-scale 0 --no-traffic \
           > $O/bench_sf${sf}_$TAG.json 2> $O/bench_sf${sf}_$TAG.log
       rc=$?; python3 -c "import json;d=json.load(open('$O/bench_sf${sf}_$TAG.json'));print('sf$sf', d['ms_per_step'], d['roofline']['frac'])"
       [ $rc -eq 0 ] || exit $rc
@@ -78,7 +78,7 @@ for mode in "$@"; do
     python3 scripts/trace_span.py "$kt" --algo-bytes "$ab" > $O/step_spans_sf12_$TAG.txt && tail -2 $O/step_spans_sf12_$TAG.txt ;;
   configs)
     for wl in c3 c4 lineitem lineitem_dbl; do
-      timeout -k 10 500 python bench.py --workload $wl --steps 10 --cpu-seconds 5 > $O/bench_${wl}_$TAG.json 2> $O/bench_${wl}_$TAG.log
+      timeout -k 10 500 python bench.py --full --workload $wl --steps 10 --cpu-seconds 5 > $O/bench_${wl}_$TAG.json 2> $O/bench_${wl}_$TAG.log
       rc=$?; echo "[$TAG] bench $wl rc=$rc"; [ $rc -eq 0 ] || exit $rc
       python3 -c "import json;d=json.load(open('$O/bench_${wl}_$TAG.json'));print(d['value'],d['roofline']['achieved'],d['roofline']['frac'],d['roofline']['traffic'])"
     done ;;
@@ -129,7 +129,7 @@ for mode in "$@"; do
         --workload "$wl" --scale "$sc" --cols "$cols" --env "$env" --out $O/wave_trace_${TAG}.npz || exit $?
     head -20 $O/wave_trace_${TAG}_${wl}_${sc}.txt ;;
   launcher2)
-    timeout -k 10 600 python bench.py --gpus 2 --scale 1 --steps 5 --cpu-seconds 0 --e2e-scale 0 --no-traffic \
+    timeout -k 10 600 python bench.py --full --gpus 2 --scale 1 --steps 5 --cpu-seconds 0 --e2e-scale 0 --no-traffic \
         > $O/bench_gpus2_$TAG.json 2> $O/bench_gpus2_$TAG.log
     rc=$?; echo "[$TAG] launcher2 rc=$rc"; cat $O/bench_gpus2_$TAG.json; [ $rc -eq 0 ] || exit $rc ;;
   *)

@@ -109,7 +109,7 @@ def test_bench_two_ranks_one_gpu(_built):
     lease): each rank decodes and verifies its contiguous shard; the line
     carries both ranks' records and every value of the table is verified."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
-    r = subprocess.run([sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", "2", "--scale", "1",
+    r = subprocess.run([sys.executable, "-u", str(ROOT / "bench.py"), "--full", "--gpus", "2", "--scale", "1",
                         "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--e2e-scale", "0", "--no-traffic"],
                        capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -126,6 +126,60 @@ def test_bench_two_ranks_one_gpu(_built):
     assert sum(p["values_checked"] for p in pr) == 6001215 * 16
     assert cfg["verified_values_bit_exact"] == 6001215 * 16 and cfg["verified_mismatches"] == 0
     assert out["value"] > 0 and sum(p["values"] for p in pr) == 6001215 * 16 * 3
+
+
+def test_dump_blocks_fixed_sample():
+    n = 600037902
+    b = bench.dump_blocks(n)
+    assert b == bench.dump_blocks(n)                                      # the same rows every run
+    assert len(b) == bench.DUMP_BLOCKS and b == sorted(set(b))
+    assert b[0] == (0, bench.DUMP_BLOCK_ROWS) and b[-1] == (n - bench.DUMP_BLOCK_ROWS, bench.DUMP_BLOCK_ROWS)
+    assert all(0 <= s and s + k <= n for s, k in b)
+    # 16 numeric columns as float64 plus l_comment's bytes (< 48 B a row) as float32: far below 64 MB
+    assert sum(k for _, k in b) * (16 * 8 + 48 * 4) < 64e6
+    small = bench.DUMP_BLOCKS * bench.DUMP_BLOCK_ROWS
+    assert bench.dump_blocks(small) == [(0, small)] and bench.dump_blocks(7) == [(0, 7)]
+    assert bench.dump_blocks(0) == []
+    assert len(bench.dump_blocks(small + 1)) == bench.DUMP_BLOCKS
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_what_the_steps_decoded(_built, fl, tmp_path):
+    """A plain run (no --full) times the steps and nothing else, and
+    --dump-outputs writes the decoded columns: at SF0.01 (60,175 rows, fewer
+    than the sample) every row, checked here against the seeded generator."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", "1", "--scale", "0.01",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, env=env, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(60175 * 16 / (line["ms_per_step"] * 1e-3))
+    assert line["full"] is False and line["e2e"] is None and line["cpu_baseline"] is None
+    assert line["roofline"]["traffic"] is None and line["config"]["verified_values_bit_exact"] == 0
+    t = fl.Connection([0]).read_image(fl.gen_image("lineitem_full", 0.01))
+    files = []
+    for c, (name, ty, _, _, _) in enumerate(t.schema()):
+        if ty in fl.STRING_TYPES:
+            want = fl.gen_strings("lineitem_full", c, 0, 60175, 0.01)
+            lens, chars = np.load(out / f"{name}.len.npy"), np.load(out / f"{name}.bytes.npy")
+            assert lens.dtype == np.float64 and chars.dtype == np.float32
+            assert lens.tolist() == [len(s) for s in want], name
+            assert chars.astype(np.uint8).tobytes() == b"".join(want), name
+            files += [f"{name}.len.npy", f"{name}.bytes.npy"]
+        else:
+            got = np.load(out / f"{name}.npy")
+            assert got.dtype == np.float64
+            want = fl.gen_values("lineitem_full", c, 0, 60175, fl.NP_DTYPE[ty], 0.01)
+            assert np.array_equal(got, want.astype(np.float64)), name
+            files.append(f"{name}.npy")
+    assert sorted(p.name for p in out.iterdir()) == sorted(files) == sorted(line["dump"]["files"])
+    assert line["dump"]["rows"] == 60175
 
 
 def test_wait_ranks_stops_the_others_when_one_fails():
