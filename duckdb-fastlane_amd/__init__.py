@@ -73,6 +73,21 @@ OPS = {"=": EQ, "==": EQ, "!=": NE, "<>": NE, "<": LT, "<=": LE, ">": GT, ">=": 
        "is_null": IS_NULL, "is_not_null": IS_NOT_NULL, "false": 8}
 
 
+# fls_agg_fn / fls_aggregate_spec / fls_aggregate_value (include/flsgpu.h)
+AGG_FNS = {"count_star": 0, "count": 1, "sum": 2, "min": 3, "max": 4, "sum_product": 5}
+AGGV_NULL, AGGV_INT, AGGV_DOUBLE = 0, 1, 2
+
+
+class AggregateSpec(C.Structure):
+    _fields_ = [("fn", C.c_uint8), ("pad", C.c_uint8 * 3), ("col", C.c_uint32), ("col2", C.c_uint32),
+                ("pad2", C.c_uint32)]
+
+
+class AggregateValue(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("lo", C.c_uint64), ("hi", C.c_uint64), ("kind", C.c_uint8),
+                ("pad", C.c_uint8 * 7)]
+
+
 class DecodeStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("values", C.c_uint64), ("packed_bytes", C.c_uint64),
                 ("meta_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("launches", C.c_uint32),
@@ -124,6 +139,8 @@ _sig("fls_scan_acquire", C.c_int, _P, C.POINTER(RowGroup))
 _sig("fls_scan_release", C.c_int, _P, C.c_uint32)
 _sig("fls_scan_filter", C.c_int, _P, C.POINTER(Predicate), C.c_uint32)
 _sig("fls_scan_pruned", C.c_int, _P)
+_sig("fls_aggregate", C.c_int, _P, C.POINTER(AggregateSpec), C.c_uint32, C.c_uint32, C.c_uint32,
+     C.POINTER(AggregateValue))
 _sig("fls_table_zonemap", C.c_int, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
      C.POINTER(C.c_uint32))
 _sig("fls_scan_dict_codes", C.c_int, _P, C.c_int)
@@ -720,6 +737,48 @@ class Table:
                 yield out.rowgroup, out.first_row, sel, self._rg_arrays(out)
         finally:
             _check(_lib.fls_scan_filter(self.h, None, 0))
+
+    # -- aggregates reduced on the GPU
+    def aggregate_raw(self, aggs, rg_begin=0, rg_end=None) -> list[AggregateValue]:
+        """fls_aggregate under the filter currently set (set_filter): the raw
+        fls_aggregate_value records.  aggs as for aggregate(); a first element
+        that is an int is passed through as the function code."""
+        if rg_end is None:
+            rg_end = self.nrowgroups
+        arr = (AggregateSpec * max(1, len(aggs)))()
+        for i, a in enumerate(aggs[:len(arr)]):
+            fn = a[0]
+            if isinstance(fn, str):
+                fn = AGG_FNS["count_star" if fn == "count" and len(a) == 1 else fn]
+            arr[i].fn = fn
+            arr[i].col = a[1] if len(a) > 1 else 0
+            arr[i].col2 = a[2] if len(a) > 2 else 0
+        out = (AggregateValue * max(1, len(aggs)))()
+        _check(_lib.fls_aggregate(self.h, arr, len(aggs), rg_begin, rg_end, out))
+        return list(out)[:len(aggs)]
+
+    def aggregate(self, aggs, filt=None, rg_begin=0, rg_end=None) -> list:
+        """Ungrouped aggregates evaluated on the GPU (fls_aggregate).  aggs: a
+        list of ("count",) [count(*)], ("count", col), ("sum", col),
+        ("min", col), ("max", col), ("sum_product", a, b); filt as
+        scan_filtered takes it.  Returns per aggregate an int (counts, integer
+        sums at full 128-bit precision, integer MIN / MAX), a float (FLOAT /
+        DOUBLE sums, MIN, MAX) or None (SUM / MIN / MAX over no row)."""
+        self.set_filter(filt)
+        try:
+            vals = self.aggregate_raw(aggs, rg_begin, rg_end)
+        finally:
+            _check(_lib.fls_scan_filter(self.h, None, 0))
+        out = []
+        for v in vals:
+            if v.kind == AGGV_NULL:
+                out.append(None)
+            elif v.kind == AGGV_DOUBLE:
+                out.append(float(np.array([v.lo], dtype=np.uint64).view(np.float64)[0]))
+            else:
+                x = (v.hi << 64) | v.lo
+                out.append(x - (1 << 128) if x >> 127 else x)
+        return out
 
     # -- device-resident decode (bench)
     def device_upload(self, rg_begin=0, rg_end=None):

@@ -25,10 +25,12 @@
 #include <memory>
 #include <string>
 #include <chrono>
+#include <cmath>
 #include <thread>
 #include <vector>
 
 #include "../../include/flsgpu.h"
+#include "fls_agg.hpp"
 #include "fls_common.hpp"
 #include "fls_config.hpp"
 #include "fls_decode.hpp"
@@ -376,6 +378,7 @@ struct HostBatch {
     std::atomic<bool> prof_pending{false};  // the batch's times not yet counted (its first acquire does)
     std::atomic<bool> upload_resident{false};  // the batch uploads into the resident image (marked present once done)
     PinBuf<uint32_t> h_err;               // the device error flags, copied after the batch's kernels
+    PinBuf<AggRec> h_agg;                 // aggregate scan: nvec x naggs partial records (vector-major)
     HostBatch() = default;
     HostBatch(const HostBatch &) = delete;
     HostBatch &operator=(const HostBatch &) = delete;
@@ -408,10 +411,15 @@ struct Slot {                       // one batch of row groups in flight
     DevBuf<uint32_t> d_counts;      // selected rows per vector
     PinBuf<uint8_t> h_fdesc;        // DevTerm[] + DevOut[] + constant strings
     DevBuf<uint8_t> d_fdesc;
-    std::vector<DevBuf<uint64_t>> d_valid;  // per filtered column with a NULL: batch validity words
+    std::vector<DevBuf<uint64_t>> d_valid;  // per filtered / aggregated column with a NULL: batch validity words
+    std::vector<uint8_t> valid_staged;      // per column: d_valid[c] holds this batch's words (stage_validity)
     std::vector<DevBuf<uint8_t>> d_narrow;  // per narrowed column: its narrowed copy
     PinBuf<uint8_t> h_ndesc;                // DevNarrow[] + per-row-group bases
     DevBuf<uint8_t> d_ndesc;
+    // aggregate batches (fls_aggregate)
+    PinBuf<DevAgg> h_adesc;
+    DevBuf<DevAgg> d_adesc;
+    DevBuf<AggRec> d_agg;           // partial records of the batch
 };
 
 // One GPU's scan pipeline: streams, the two device slots and the pinned
@@ -467,11 +475,20 @@ struct HostTerm {
     std::string str;
 };
 
+// One aggregate of fls_aggregate, host side.
+struct HostAgg {
+    uint8_t fn = 0;                 // AggFn
+    uint32_t col = 0, col2 = 0;
+};
+
 struct ScanCtx {
     bool active = false;
     std::vector<uint8_t> mask;      // delivered columns
     std::vector<uint8_t> dmask;     // decoded columns (delivered + filter columns)
     std::vector<HostTerm> terms;    // filter of this scan, sorted by clause (empty: none)
+    // aggregate scan (fls_aggregate; empty: a delivering scan): no column is
+    // delivered, each batch's partial records ride in its HostBatch
+    std::vector<HostAgg> aggs;
     bool dict_codes = false;        // deliver DICT string chunks as codes + dictionary
     bool narrow = false;            // deliver integer columns narrowed to their row groups' ranges
     bool defer_records = false;     // FSST-as-lengths records built by fls_scan_build_records, not scan_acquire
@@ -503,7 +520,7 @@ struct ScanCtx {
 
 // Pinned bytes a host batch holds (its columns, FSST heaps, selection).
 size_t pinned_bytes(const HostBatch &b) {
-    size_t t = b.h_counts.n * sizeof(uint32_t) + b.h_sel.n * sizeof(uint32_t);
+    size_t t = b.h_counts.n * sizeof(uint32_t) + b.h_sel.n * sizeof(uint32_t) + b.h_agg.n * sizeof(AggRec);
     for (auto &x : b.h_out) t += x.n;
     for (auto &x : b.h_heap) t += x.n;
     return t;
@@ -511,7 +528,8 @@ size_t pinned_bytes(const HostBatch &b) {
 size_t pinned_bytes(const ScanDev &d) {
     size_t t = 0;
     for (auto &b : d.batches) t += pinned_bytes(*b);
-    for (auto &sl : d.slots) t += sl.h_chunks.n * sizeof(DevChunk) + sl.h_stage.n + sl.h_fdesc.n;
+    for (auto &sl : d.slots)
+        t += sl.h_chunks.n * sizeof(DevChunk) + sl.h_stage.n + sl.h_fdesc.n + sl.h_adesc.n * sizeof(DevAgg);
     return t;
 }
 
@@ -777,7 +795,7 @@ struct fls_table {
     uint32_t launches = 0;
 
     ScanCtx scan, mat;
-    std::vector<HostTerm> filter;   // fls_scan_filter: applies to the next fls_scan_begin
+    std::vector<HostTerm> filter;   // fls_scan_filter: applies to the next fls_scan_begin / fls_aggregate
     bool dict_codes = false;        // fls_scan_dict_codes: applies to the next fls_scan_begin
     bool narrow = false;            // fls_scan_narrow: applies to the next fls_scan_begin
     bool defer_records = false;     // fls_scan_defer_records: applies to the next fls_scan_begin
@@ -1482,7 +1500,7 @@ std::shared_ptr<DevImage> resident_image(fls_table *t, int dev, uint32_t g, uint
 }
 
 int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uint8_t *col_mask, uint32_t rg0,
-               uint32_t rg1, const std::vector<HostTerm> *filter) {
+               uint32_t rg1, const std::vector<HostTerm> *filter, const std::vector<HostAgg> *aggs = nullptr) {
     ProfTimer prof(PROF_SETUP);
     t->profiled = t->profiled || ScanProf::on();
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
@@ -1514,6 +1532,17 @@ int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uin
     s.dmask = s.mask;
     for (auto &h : s.terms)
         if (h.op < OP_IS_NULL) s.dmask[h.col] = 1;
+    s.aggs.clear();
+    if (aggs) {
+        // an aggregate scan delivers nothing and decodes the filter's columns
+        // and the numeric operands (a COUNT reads its column's validity only)
+        s.aggs = *aggs;
+        s.dict_codes = s.narrow = s.defer_records = false;
+        for (auto &a : s.aggs) {
+            if (a.fn >= AGG_SUM) s.dmask[a.col] = 1;
+            if (a.fn == AGG_SUM_PRODUCT) s.dmask[a.col2] = 1;
+        }
+    }
     // row-group pruning on zone maps / dictionaries
     s.rgs.clear();
     s.pruned = 0;
@@ -1604,25 +1633,20 @@ int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uin
     return 0;
 }
 
-// Filter descriptors of a batch: the terms over the slot's decoded columns,
-// the delivered columns' compaction targets, then the constant strings.
-int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo, uint64_t in_len) {
+// Validity words of the batch rows (HBM, sl.d_valid[c]) for every column the
+// filter's terms or the aggregates' operands read that has a NULL in the
+// batch (row groups start at whole vectors: rows / 64 words apart);
+// sl.valid_staged[c] ends up 1 for the columns staged.
+int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    std::vector<DevOut> outs;
-    for (uint32_t c = 0; c < ncols; ++c) {
-        if (!col_selected(s.mask, c)) continue;
-        DevOut o;
-        memset(&o, 0, sizeof(o));
-        o.src = sl.hb->narrowed[c] ? sl.d_narrow[c].p : sl.d_out[c].p;
-        o.dst = sl.hb->h_out[c].p;
-        o.ob = sl.hb->ob[c];
-        outs.push_back(o);
-    }
-    // validity words of the batch rows for every filtered column with a NULL
-    // in the batch (row groups start at whole vectors: rows / 64 words apart)
     sl.d_valid.resize(ncols);
-    std::vector<uint8_t> need(ncols, 0);
+    std::vector<uint8_t> &need = sl.valid_staged;
+    need.assign(ncols, 0);
     for (auto &h : s.terms) need[h.col] = 1;
+    for (auto &a : s.aggs) {
+        if (a.fn != AGG_COUNT_STAR) need[a.col] = 1;
+        if (a.fn == AGG_SUM_PRODUCT) need[a.col2] = 1;
+    }
     for (uint32_t c = 0; c < ncols; ++c) {
         bool any = false;
         for (uint32_t r = sl.rg0; need[c] && r < sl.rg0 + sl.nrg; ++r)
@@ -1643,6 +1667,25 @@ int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
                 HIP_TRY(hipMemsetAsync(dst, 0xFF, bytes, sl.stream));
         }
     }
+    return 0;
+}
+
+// Filter descriptors of a batch: the terms over the slot's decoded columns,
+// the delivered columns' compaction targets, then the constant strings.
+int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo, uint64_t in_len) {
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    std::vector<DevOut> outs;
+    for (uint32_t c = 0; c < ncols; ++c) {
+        if (!col_selected(s.mask, c)) continue;
+        DevOut o;
+        memset(&o, 0, sizeof(o));
+        o.src = sl.hb->narrowed[c] ? sl.d_narrow[c].p : sl.d_out[c].p;
+        o.dst = sl.hb->h_out[c].p;
+        o.ob = sl.hb->ob[c];
+        outs.push_back(o);
+    }
+    if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
+    const std::vector<uint8_t> &need = sl.valid_staged;
     const size_t nt = s.terms.size(), no = outs.size();
     size_t str_bytes = 0;
     for (auto &h : s.terms) str_bytes += (h.str.size() + 15) & ~size_t(15);
@@ -1685,15 +1728,61 @@ int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
     hb.nvec = (uint32_t)((rows + 1023) / 1024);
     HIP_TRY(sl.d_mask.alloc(d.dev, (size_t)hb.nvec * 16));
     HIP_TRY(sl.d_counts.alloc(d.dev, hb.nvec));
-    HIP_TRY(hb.h_counts.alloc(hb.nvec));
-    HIP_TRY(hb.h_sel.alloc(std::max<uint64_t>(rows, 1)));
     HIP_TRY(launch_filter((const DevTerm *)sl.d_fdesc.p, (uint32_t)nt, (uint32_t)rows, sl.d_mask.p, sl.d_counts.p,
                           d.err.p, sl.stream));
+    if (!s.aggs.empty()) return 0;  // an aggregate scan reduces under the mask: nothing is compacted or delivered
+    HIP_TRY(hb.h_counts.alloc(hb.nvec));
+    HIP_TRY(hb.h_sel.alloc(std::max<uint64_t>(rows, 1)));
     HIP_TRY(launch_compact((const DevOut *)(sl.d_fdesc.p + nt * sizeof(DevTerm)), (uint32_t)no, sl.d_mask.p,
                            sl.d_counts.p, (uint32_t)rows, t->meta.rowgroup_size, hb.h_sel.p, sl.stream));
     HIP_TRY(hipMemcpyAsync(hb.h_counts.p, sl.d_counts.p, hb.nvec * sizeof(uint32_t), hipMemcpyDeviceToHost,
                            sl.stream));
     hb.sel_ready = false;
+    return 0;
+}
+
+// Aggregate descriptors of a batch and the launch that reduces it: one
+// partial record per (vector, aggregate) into sl.d_agg, copied to the host
+// batch on the slot's stream.  The selection mask is the filter kernel's
+// (enqueue_filter ran before) or none.
+int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
+    HostBatch &hb = *sl.hb;
+    const bool filtered = !s.terms.empty();
+    if (!filtered)  // (enqueue_filter staged the filter's and the operands' validity together)
+        if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
+    const std::vector<uint8_t> &need = sl.valid_staged;
+    const uint32_t na = (uint32_t)s.aggs.size();
+    hb.nvec = (uint32_t)((rows + 1023) / 1024);
+    HIP_TRY(sl.h_adesc.alloc(na));
+    HIP_TRY(sl.d_adesc.alloc(d.dev, na));
+    HIP_TRY(sl.d_agg.alloc(d.dev, (size_t)hb.nvec * na));
+    HIP_TRY(hb.h_agg.alloc((size_t)hb.nvec * na));
+    auto kind_of = [&](uint32_t c) -> uint8_t {
+        const uint8_t ty = t->meta.cols[c].type;
+        return type_is_float(ty) ? FK_FLOAT : type_is_signed(ty) ? FK_INT : FK_UINT;
+    };
+    for (uint32_t i = 0; i < na; ++i) {
+        const HostAgg &a = s.aggs[i];
+        DevAgg &da = sl.h_adesc.p[i];
+        memset(&da, 0, sizeof(da));
+        da.fn = a.fn;
+        if (a.fn == AGG_COUNT_STAR) continue;
+        da.valid = need[a.col] ? sl.d_valid[a.col].p : nullptr;
+        if (a.fn == AGG_COUNT) continue;
+        da.col = sl.d_out[a.col].p;
+        da.ob = (uint8_t)out_bytes_of(t, a.col);
+        da.kind = kind_of(a.col);
+        if (a.fn != AGG_SUM_PRODUCT) continue;
+        da.col2 = sl.d_out[a.col2].p;
+        da.ob2 = (uint8_t)out_bytes_of(t, a.col2);
+        da.kind2 = kind_of(a.col2);
+        da.valid2 = need[a.col2] ? sl.d_valid[a.col2].p : nullptr;
+    }
+    HIP_TRY(hipMemcpyAsync(sl.d_adesc.p, sl.h_adesc.p, na * sizeof(DevAgg), hipMemcpyHostToDevice, sl.stream));
+    HIP_TRY(launch_aggregate(sl.d_adesc.p, na, (uint32_t)rows, filtered ? sl.d_mask.p : nullptr, sl.d_agg.p,
+                             sl.stream));
+    HIP_TRY(hipMemcpyAsync(hb.h_agg.p, sl.d_agg.p, (size_t)hb.nvec * na * sizeof(AggRec), hipMemcpyDeviceToHost,
+                           sl.stream));
     return 0;
 }
 
@@ -1966,8 +2055,10 @@ int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     // integer-only scans, nor cost every refill an environment parse)
     if (fsst.total_vecs() > 0)
         if (const int rc = fsst_config_check(policy)) return rc;
-    HIP_TRY(launch_all(sl.d_chunks.p, nmain, (uint32_t)k, fsst, d.err.p, bc.geom, sl.stream, sl.queue.p, policy,
-                       plan));
+    // (an aggregate scan of counts without a filter decodes no column)
+    if (kk || s.aggs.empty())
+        HIP_TRY(launch_all(sl.d_chunks.p, nmain, (uint32_t)k, fsst, d.err.p, bc.geom, sl.stream, sl.queue.p, policy,
+                           plan));
     const uint64_t rows = t->meta.rgs[sl.rg0 + sl.nrg - 1].first_row + t->meta.rgs[sl.rg0 + sl.nrg - 1].nrows -
                           t->meta.rgs[sl.rg0].first_row;
     // 2b. narrowed columns: value - base into their narrow copies
@@ -2004,6 +2095,9 @@ int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
         int rc = enqueue_filter(t, s, d, sl, rows, lo, hi - lo);
         if (rc) return rc;
     }
+    // 3b. aggregate scan: reduce under the mask; the partial records are the batch's only D2H
+    if (!s.aggs.empty())
+        if (int rc = enqueue_aggregate(t, s, d, sl, rows, lo)) return rc;
     // 3. D2H into pinned host columns (and string heaps)
     if (hb.pt[1]) HIP_TRY(hipEventRecord(hb.pt[1], sl.stream));
     hb.prof_d2h = 0;
@@ -2239,7 +2333,7 @@ int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
     out->ncols = ncols;
     out->nrows_scanned = out->nrows;
     out->sel = nullptr;
-    if (!s.terms.empty()) {
+    if (!s.terms.empty() && s.aggs.empty()) {
         batch_selection(t, s, *hb);
         const uint32_t i = rg - hb->rg0;
         out->nrows = hb->sel_off[i + 1] - hb->sel_off[i];
@@ -2686,6 +2780,158 @@ int fls_scan_filter(fls_table *t, const fls_predicate *preds, uint32_t n) {
     int rc = to_terms(t, preds, n, terms);
     if (rc) return rc;
     t->filter.swap(terms);
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Largest magnitude of column c's non-NULL values in row group rg: from the
+// zone map, else the type's range.
+uint64_t max_magnitude(const fls_table *t, uint32_t rg, uint32_t c) {
+    const uint8_t ty = t->meta.cols[c].type;
+    const bool sign = type_is_signed(ty);
+    const auto &zs = t->meta.rgs[rg].zones;
+    if (!zs.empty() && (zs[c].flags & ZM_ALL_NULL)) return 0;
+    if (zs.empty() || !(zs[c].flags & ZM_VALID)) {
+        const int bits = type_value_bits(ty);
+        return sign ? 1ull << (bits - 1) : (bits == 64 ? ~0ull : (1ull << bits) - 1);
+    }
+    if (!sign) return std::max(zs[c].min, zs[c].max);
+    auto mag = [](uint64_t v) { return (int64_t)v < 0 ? 0 - v : v; };
+    return std::max(mag(zs[c].min), mag(zs[c].max));
+}
+
+// a * b rounded upwards (a, b >= 0)
+double mul_up(double a, double b) { return std::nextafter(a * b, HUGE_VAL); }
+// an upper bound of v as a double
+double dbl_up(uint64_t v) { return v == 0 ? 0.0 : std::nextafter((double)v, HUGE_VAL); }
+
+}  // namespace
+
+extern "C" {
+
+int fls_aggregate(fls_table *t, const fls_aggregate_spec *aggs, uint32_t n, uint32_t rg_begin, uint32_t rg_end,
+                  fls_aggregate_value *out) {
+    if (!t || !aggs || !out) return fail(FLS_ERR_ARG, "fls_aggregate: NULL argument");
+    if (n == 0 || n > kMaxAggs) return fail(FLS_ERR_ARG, "fls_aggregate: %u aggregates (1 to %u per call)", n, kMaxAggs);
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    if (rg_end > t->meta.rgs.size() || rg_begin > rg_end)
+        return fail(FLS_ERR_ARG, "row-group range [%u,%u) out of bounds", rg_begin, rg_end);
+    std::vector<HostAgg> ha(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const fls_aggregate_spec &a = aggs[i];
+        if (a.fn > FLS_AGG_SUM_PRODUCT) return fail(FLS_ERR_ARG, "aggregate %u: unknown function %u", i, a.fn);
+        ha[i].fn = a.fn;
+        if (a.fn == FLS_AGG_COUNT_STAR) continue;
+        if (a.col >= ncols) return fail(FLS_ERR_ARG, "aggregate %u: column %u out of range", i, a.col);
+        ha[i].col = a.col;
+        if (a.fn == FLS_AGG_COUNT) continue;
+        const uint8_t ty = t->meta.cols[a.col].type;
+        if (type_is_string(ty))
+            return fail(FLS_ERR_ARG, "aggregate %u: SUM / MIN / MAX of string column %u is not supported", i, a.col);
+        if (a.fn != FLS_AGG_SUM_PRODUCT) continue;
+        if (a.col2 >= ncols) return fail(FLS_ERR_ARG, "aggregate %u: column %u out of range", i, a.col2);
+        ha[i].col2 = a.col2;
+        const uint8_t ty2 = t->meta.cols[a.col2].type;
+        if (type_is_string(ty2))
+            return fail(FLS_ERR_ARG, "aggregate %u: SUM_PRODUCT of string column %u is not supported", i, a.col2);
+        if (type_is_float(ty) || type_is_float(ty2))
+            return fail(FLS_ERR_ARG, "aggregate %u: SUM_PRODUCT of a FLOAT / DOUBLE column is not supported", i);
+    }
+    // SUM_PRODUCT must stay below 2^127: bound it over the row groups the scan
+    // will read (rounded upwards) before anything is decoded
+    for (uint32_t i = 0; i < n; ++i) {
+        if (ha[i].fn != AGG_SUM_PRODUCT) continue;
+        double bound = 0;
+        for (uint32_t r = rg_begin; r < rg_end; ++r) {
+            if (!t->filter.empty() && !rowgroup_may_match(t, r, t->filter)) continue;
+            const double term = mul_up(mul_up(dbl_up(t->meta.rgs[r].nrows), dbl_up(max_magnitude(t, r, ha[i].col))),
+                                       dbl_up(max_magnitude(t, r, ha[i].col2)));
+            bound = std::nextafter(bound + term, HUGE_VAL);
+        }
+        if (bound >= 0x1p127)
+            return fail(FLS_ERR_ARG, "aggregate %u: SUM_PRODUCT of columns %u and %u may overflow 128 bits", i, ha[i].col,
+                        ha[i].col2);
+    }
+    const std::vector<uint8_t> none(std::max(1u, ncols), 0);  // nothing is delivered
+    ScanCtx &s = t->scan;
+    int rc = scan_setup(t, s, t->devices, none.data(), rg_begin, rg_end, &t->filter, &ha);
+    if (!rc) rc = scan_start(t, s);
+    if (rc) return rc;
+    // fold the per-vector records in row order
+    struct Acc {
+        uint64_t count = 0;
+        unsigned __int128 sum = 0;
+        double fsum = -0.0;
+        uint64_t key = 0;
+    };
+    std::vector<Acc> acc(n);
+    for (uint32_t i = 0; i < n; ++i)
+        if (ha[i].fn == AGG_MIN) acc[i].key = ~0ull;
+    auto is_float = [&](uint32_t i) { return ha[i].fn >= AGG_SUM && type_is_float(t->meta.cols[ha[i].col].type); };
+    fls_rowgroup rg;
+    while ((rc = scan_next(t, s, &rg)) == 1) {
+        const HostBatch *hb = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(s.mu);
+            for (const auto &o : s.out)
+                if (o.first == rg.rowgroup) hb = o.second;
+        }
+        if (!hb) return fail(FLS_ERR_STATE, "internal: aggregate batch of row group %u not found", rg.rowgroup);
+        const uint64_t v0 = (t->meta.rgs[rg.rowgroup].first_row - t->meta.rgs[hb->rg0].first_row) / kVectorSize;
+        const uint64_t nv = (t->meta.rgs[rg.rowgroup].nrows + kVectorSize - 1) / kVectorSize;
+        for (uint64_t v = v0; v < v0 + nv && v < hb->nvec; ++v)
+            for (uint32_t i = 0; i < n; ++i) {
+                const AggRec &r = hb->h_agg.p[v * n + i];
+                Acc &a = acc[i];
+                a.count += r.count;
+                if (r.count == 0) continue;
+                switch (ha[i].fn) {
+                case AGG_SUM:
+                case AGG_SUM_PRODUCT:
+                    if (is_float(i)) a.fsum += as_double(r.lo);
+                    else a.sum += ((unsigned __int128)r.hi << 64) | r.lo;
+                    break;
+                case AGG_MIN: a.key = std::min(a.key, r.lo); break;
+                case AGG_MAX: a.key = std::max(a.key, r.lo); break;
+                default: break;
+                }
+            }
+    }
+    if (rc < 0) return rc;
+    for (uint32_t i = 0; i < n; ++i) {
+        fls_aggregate_value &o = out[i];
+        memset(&o, 0, sizeof(o));
+        const Acc &a = acc[i];
+        o.count = a.count;
+        if (ha[i].fn <= AGG_COUNT) {
+            o.kind = FLS_AGGV_INT;
+            o.lo = a.count;
+            continue;
+        }
+        if (a.count == 0) continue;  // FLS_AGGV_NULL
+        const bool flt = is_float(i);
+        o.kind = flt ? FLS_AGGV_DOUBLE : FLS_AGGV_INT;
+        if (ha[i].fn == AGG_SUM || ha[i].fn == AGG_SUM_PRODUCT) {
+            if (flt) {
+                memcpy(&o.lo, &a.fsum, 8);
+            } else {
+                o.lo = (uint64_t)a.sum;
+                o.hi = (uint64_t)(a.sum >> 64);
+            }
+        } else if (flt) {
+            const double d = agg_unkey_float(a.key);
+            memcpy(&o.lo, &d, 8);
+        } else if (type_is_signed(t->meta.cols[ha[i].col].type)) {
+            const int64_t v = agg_unkey_int(a.key);
+            o.lo = (uint64_t)v;
+            o.hi = v < 0 ? ~0ull : 0ull;
+        } else {
+            o.lo = a.key;
+        }
+    }
     return 0;
 }
 

@@ -80,6 +80,10 @@ class NotImplementedException : public Exception {
 public:
     explicit NotImplementedException(const string &msg) : Exception(msg) {}
 };
+class OutOfRangeException : public Exception {
+public:
+    explicit OutOfRangeException(const string &msg) : Exception("Out of Range Error: " + msg) {}
+};
 
 // ---- types -----------------------------------------------------------------
 enum class LogicalTypeId : uint8_t {

@@ -4,8 +4,8 @@
 // reference wrote but never registered (:44-90): the SQL scalar
 // `fastlane_version()` (:32-42, used at examples/basic_usage.sql:8), the typed
 // GPU scan (here `read_fastlanes`, VARCHAR and LIST(VARCHAR)), the
-// .fls/.fastlane replacement scan, and the COPY TO (FORMAT fls | fastlane)
-// writer.
+// .fls/.fastlane replacement scan, the COPY TO (FORMAT fls | fastlane)
+// writer, and `fastlanes_aggregate` (ungrouped aggregates reduced on the GPU).
 #define DUCKDB_EXTENSION_MAIN
 
 #include "fastlane_extension.hpp"
@@ -13,6 +13,7 @@
 #include "duckdb.hpp"
 #include "gpu_devices.hpp"
 #include "scan_fastlanes.hpp"
+#include "table_function/fastlanes_aggregate.hpp"
 #include "table_function/read_fastlanes.hpp"
 #include "writer/copy_fastlanes.hpp"
 
@@ -43,6 +44,7 @@ void FastlaneExtension::Load(DuckDB &db) {
         *db.instance, ScalarFunction("fastlane_release_memory", {}, LogicalType::BIGINT, FastlaneReleaseMemoryFn));
     ScanFastLanes::Register(*db.instance);
     ext_fastlane::RegisterReadFastlanes(*db.instance);
+    ext_fastlane::RegisterFastlanesAggregate(*db.instance);
     ext_fastlane::RegisterFastlaneCopyFunction(*db.instance);
 }
 

@@ -1,0 +1,507 @@
+// fastlanes_aggregate.cpp -- `fastlanes_aggregate(path, aggregates[, filter])`.
+//
+// A table function that returns exactly one row: the ungrouped aggregates of
+// one FastLanes file, reduced on the GPU under the filter (fls_aggregate), so
+// only per-vector partial results cross PCIe instead of the qualifying rows.
+//
+//   aggregates: comma-separated `count(*)`, `count(c)`, `sum(c)`, `sum(a * b)`,
+//               `min(c)`, `max(c)`; each output column is named by the trimmed
+//               text of its item.
+//   filter:     `term AND term ...`, a term `column op literal` (op one of
+//               = != <> < <= > >=) or `column IS [NOT] NULL`.  Literals by
+//               column type: integers, decimal numbers the column's scale
+//               represents exactly, DATE 'YYYY-MM-DD', floats, single-quoted
+//               strings ('' escapes a quote).  No OR, no parentheses.
+//
+// Output types: counts and integer sums BIGINT, sums of DECIMAL(w, s)
+// DECIMAL(18, s), sum(a * b) DECIMAL(18, s1 + s2) when an operand is DECIMAL,
+// float sums DOUBLE, min / max the column's own type.  The engine's sums are
+// 128-bit; one that does not fit its output type raises OutOfRangeException
+// (there is no HUGEINT here).  Everything unparsable, unknown or ill-typed is a
+// BinderException quoting the offending text, raised at bind from the footer
+// alone (no GPU).  DuckDB has no aggregate-pushdown hook for table functions:
+// rewriting `SELECT sum(x) FROM read_fastlanes(...) WHERE ...` into this
+// function would need an optimizer extension and is not attempted.
+#include <cctype>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <memory>
+#include <mutex>
+
+#include "../../../../include/flsgpu.h"
+#include "../../../../include/flswriter.h"
+#include "../gpu_devices.hpp"
+#include "duckdb/common/exception.hpp"
+#include "duckdb/common/string_util.hpp"
+#include "duckdb/main/extension_util.hpp"
+#include "table_function/fastlanes_aggregate.hpp"
+#include "type_mapping.hpp"
+
+namespace duckdb {
+namespace ext_fastlane {
+
+namespace {
+
+struct AggTable {
+    fls_table *table = nullptr;
+    ~AggTable() {
+        if (table) fls_table_close(table);
+    }
+};
+
+struct AggBindData : public TableFunctionData {
+    string file;
+    std::vector<fls_aggregate_spec> specs;
+    vector<LogicalType> types;
+    vector<string> names;                // the items' trimmed text
+    std::vector<fls_predicate> preds;
+    std::deque<string> pred_strs;        // VARCHAR constants the predicates point at
+    std::shared_ptr<AggTable> table;     // opened at bind (footer only)
+};
+
+struct AggGlobalState : public GlobalTableFunctionState {
+    std::mutex lock;
+    bool done = false;
+};
+
+string Trim(const string &s) {
+    size_t a = 0, b = s.size();
+    while (a < b && isspace((unsigned char)s[a])) ++a;
+    while (b > a && isspace((unsigned char)s[b - 1])) --b;
+    return s.substr(a, b - a);
+}
+
+bool IsIdent(const string &s) {
+    if (s.empty() || !(isalpha((unsigned char)s[0]) || s[0] == '_')) return false;
+    for (char c : s)
+        if (!(isalnum((unsigned char)c) || c == '_')) return false;
+    return true;
+}
+
+struct Schema {
+    std::vector<fls_column_info> cols;
+    vector<string> names;
+    vector<LogicalType> types;
+    // exact name first, then case-insensitively (DuckDB's identifier matching)
+    int Find(string name) const {
+        if (name.size() >= 2 && name.front() == '"' && name.back() == '"') name = name.substr(1, name.size() - 2);
+        for (size_t c = 0; c < names.size(); ++c)
+            if (names[c] == name) return (int)c;
+        const string low = StringUtil::Lower(name);
+        for (size_t c = 0; c < names.size(); ++c)
+            if (StringUtil::Lower(names[c]) == low) return (int)c;
+        return -1;
+    }
+};
+
+bool IsString(uint8_t t) { return t == FLS_VARCHAR || t == FLS_BLOB; }
+bool IsFloat(uint8_t t) { return t == FLS_FLOAT || t == FLS_DOUBLE; }
+
+int ColumnOf(const Schema &sch, const string &name, const string &item) {
+    const string n = Trim(name);
+    if (!(IsIdent(n) || (n.size() >= 2 && n.front() == '"' && n.back() == '"')))
+        throw BinderException("fastlanes_aggregate: cannot parse \"" + n + "\" in aggregate \"" + item + "\"");
+    const int c = sch.Find(n);
+    if (c < 0) throw BinderException("fastlanes_aggregate: column \"" + n + "\" of aggregate \"" + item + "\" not found");
+    return c;
+}
+
+// one item of the aggregate list -> spec and output type
+void ParseAggregate(const Schema &sch, const string &item, fls_aggregate_spec &spec, LogicalType &type) {
+    memset(&spec, 0, sizeof(spec));
+    const size_t open = item.find('(');
+    if (open == string::npos || item.back() != ')')
+        throw BinderException("fastlanes_aggregate: cannot parse aggregate \"" + item + "\"");
+    const string fn = StringUtil::Lower(Trim(item.substr(0, open)));
+    const string arg = Trim(item.substr(open + 1, item.size() - open - 2));
+    if (arg.find('(') != string::npos || arg.find(')') != string::npos || arg.empty())
+        throw BinderException("fastlanes_aggregate: cannot parse aggregate \"" + item + "\"");
+    if (fn == "count") {
+        type = LogicalType::BIGINT;
+        if (arg == "*") {
+            spec.fn = FLS_AGG_COUNT_STAR;
+            return;
+        }
+        spec.fn = FLS_AGG_COUNT;
+        spec.col = (uint32_t)ColumnOf(sch, arg, item);
+        return;
+    }
+    if (fn != "sum" && fn != "min" && fn != "max")
+        throw BinderException("fastlanes_aggregate: unknown aggregate function \"" + fn + "\" in \"" + item + "\"");
+    const size_t star = arg.find('*');
+    if (star != string::npos) {
+        if (fn != "sum") throw BinderException("fastlanes_aggregate: a product is only supported in sum(): \"" + item + "\"");
+        const int a = ColumnOf(sch, arg.substr(0, star), item), b = ColumnOf(sch, arg.substr(star + 1), item);
+        for (int c : {a, b})
+            if (IsString(sch.cols[c].type) || IsFloat(sch.cols[c].type))
+                throw BinderException("fastlanes_aggregate: sum of a product needs integer or DECIMAL columns, \"" +
+                                      sch.names[c] + "\" is " + sch.types[c].ToString() + " in \"" + item + "\"");
+        spec.fn = FLS_AGG_SUM_PRODUCT;
+        spec.col = (uint32_t)a;
+        spec.col2 = (uint32_t)b;
+        const bool dec = sch.cols[a].type == FLS_DECIMAL || sch.cols[b].type == FLS_DECIMAL;
+        const unsigned scale = (sch.cols[a].type == FLS_DECIMAL ? sch.cols[a].scale : 0u) +
+                               (sch.cols[b].type == FLS_DECIMAL ? sch.cols[b].scale : 0u);
+        if (scale > 18)
+            throw BinderException("fastlanes_aggregate: the scale of \"" + item + "\" exceeds DECIMAL(18)");
+        type = dec ? LogicalType::DECIMAL(18, (uint8_t)scale) : LogicalType::BIGINT;
+        return;
+    }
+    const int c = ColumnOf(sch, arg, item);
+    if (IsString(sch.cols[c].type))
+        throw BinderException("fastlanes_aggregate: " + fn + " of " + sch.types[c].ToString() + " column \"" + sch.names[c] +
+                              "\" is not supported in \"" + item + "\"");
+    spec.col = (uint32_t)c;
+    if (fn == "sum") {
+        spec.fn = FLS_AGG_SUM;
+        type = IsFloat(sch.cols[c].type)           ? LogicalType::DOUBLE
+               : sch.cols[c].type == FLS_DECIMAL ? LogicalType::DECIMAL(18, sch.cols[c].scale)
+                                                 : LogicalType::BIGINT;
+    } else {
+        spec.fn = fn == "min" ? FLS_AGG_MIN : FLS_AGG_MAX;
+        type = sch.types[c];
+    }
+}
+
+// ---- the filter text ------------------------------------------------------
+struct Token {
+    enum Kind { END, WORD, NUMBER, STRING, OP } kind = END;
+    string text;   // WORD as written, NUMBER digits, STRING unescaped contents, OP the operator
+};
+
+struct Lexer {
+    const string &s;
+    size_t pos = 0;
+    explicit Lexer(const string &text) : s(text) {}
+    Token Next() {
+        while (pos < s.size() && isspace((unsigned char)s[pos])) ++pos;
+        Token t;
+        if (pos >= s.size()) return t;
+        const char c = s[pos];
+        if (isalpha((unsigned char)c) || c == '_') {
+            const size_t a = pos;
+            while (pos < s.size() && (isalnum((unsigned char)s[pos]) || s[pos] == '_')) ++pos;
+            t.kind = Token::WORD;
+            t.text = s.substr(a, pos - a);
+            return t;
+        }
+        if (c == '"') {
+            const size_t e = s.find('"', pos + 1);
+            if (e == string::npos) throw BinderException("fastlanes_aggregate: unterminated identifier in filter \"" + s + "\"");
+            t.kind = Token::WORD;
+            t.text = s.substr(pos, e + 1 - pos);
+            pos = e + 1;
+            return t;
+        }
+        if (c == '\'') {
+            t.kind = Token::STRING;
+            for (++pos;; ++pos) {
+                if (pos >= s.size()) throw BinderException("fastlanes_aggregate: unterminated string in filter \"" + s + "\"");
+                if (s[pos] == '\'') {
+                    if (pos + 1 < s.size() && s[pos + 1] == '\'') {
+                        t.text += '\'';
+                        ++pos;
+                        continue;
+                    }
+                    ++pos;
+                    return t;
+                }
+                t.text += s[pos];
+            }
+        }
+        if (isdigit((unsigned char)c) || c == '.' || ((c == '-' || c == '+') && pos + 1 < s.size() &&
+                                                      (isdigit((unsigned char)s[pos + 1]) || s[pos + 1] == '.'))) {
+            const size_t a = pos++;
+            while (pos < s.size() && (isalnum((unsigned char)s[pos]) || s[pos] == '.' ||
+                                      ((s[pos] == '-' || s[pos] == '+') && (s[pos - 1] == 'e' || s[pos - 1] == 'E'))))
+                ++pos;
+            t.kind = Token::NUMBER;
+            t.text = s.substr(a, pos - a);
+            return t;
+        }
+        for (const char *op : {"<>", "!=", "<=", ">=", "=", "<", ">"})
+            if (s.compare(pos, strlen(op), op) == 0) {
+                t.kind = Token::OP;
+                t.text = op;
+                pos += strlen(op);
+                return t;
+            }
+        throw BinderException("fastlanes_aggregate: cannot parse \"" + s.substr(pos, 1) + "\" in filter \"" + s + "\"");
+    }
+};
+
+int64_t DaysFromCivil(int64_t y, unsigned m, unsigned d) {
+    y -= m <= 2;
+    const int64_t era = (y >= 0 ? y : y - 399) / 400;
+    const unsigned yoe = (unsigned)(y - era * 400);
+    const unsigned doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1;
+    const unsigned doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
+    return era * 146097 + (int64_t)doe - 719468;
+}
+
+bool AllDigits(const string &s) {
+    if (s.empty()) return false;
+    for (char c : s)
+        if (!isdigit((unsigned char)c)) return false;
+    return true;
+}
+
+// the literal of a comparison in the column's physical type (fls_predicate.value / str)
+void SetLiteral(const Schema &sch, int col, Lexer &lex, Token lit, const string &filter, fls_predicate &p,
+                std::deque<string> &strs) {
+    const fls_column_info &ci = sch.cols[col];
+    const string cname = sch.names[col];
+    bool date_kw = false;
+    if (lit.kind == Token::WORD && StringUtil::Lower(lit.text) == "date") {
+        date_kw = true;
+        lit = lex.Next();
+        if (lit.kind != Token::STRING)
+            throw BinderException("fastlanes_aggregate: DATE needs a 'YYYY-MM-DD' string in filter \"" + filter + "\"");
+    }
+    auto bad = [&](const char *want) {
+        return BinderException("fastlanes_aggregate: \"" + (lit.kind == Token::STRING ? "'" + lit.text + "'" : lit.text) +
+                               "\" is not " + want + " for " + sch.types[col].ToString() + " column \"" + cname +
+                               "\" in filter \"" + filter + "\"");
+    };
+    if (lit.kind == Token::END || lit.kind == Token::OP)
+        throw BinderException("fastlanes_aggregate: a literal is missing after column \"" + cname + "\" in filter \"" +
+                              filter + "\"");
+    if (date_kw != (ci.type == FLS_DATE)) throw bad(ci.type == FLS_DATE ? "a DATE 'YYYY-MM-DD' literal" : "a literal");
+    switch (ci.type) {
+    case FLS_DATE: {
+        int y = 0, n = 0;
+        unsigned m = 0, d = 0;
+        if (sscanf(lit.text.c_str(), "%d-%u-%u%n", &y, &m, &d, &n) != 3 || (size_t)n != lit.text.size() || m < 1 ||
+            m > 12 || d < 1 || d > 31)
+            throw bad("a DATE 'YYYY-MM-DD' literal");
+        p.value = (uint64_t)DaysFromCivil(y, m, d);
+        return;
+    }
+    case FLS_VARCHAR: case FLS_BLOB:
+        if (lit.kind != Token::STRING) throw bad("a quoted string");
+        strs.push_back(lit.text);
+        p.str = strs.back().data();
+        p.str_len = strs.back().size();
+        return;
+    case FLS_FLOAT: case FLS_DOUBLE: {
+        if (lit.kind == Token::STRING) throw bad("a number");
+        char *end = nullptr;
+        const double d = std::strtod(lit.text.c_str(), &end);
+        if (end == lit.text.c_str() || *end) throw bad("a number");
+        if (ci.type == FLS_FLOAT) {
+            const float f = (float)d;
+            uint32_t b;
+            memcpy(&b, &f, 4);
+            p.value = b;
+        } else {
+            memcpy(&p.value, &d, 8);
+        }
+        return;
+    }
+    case FLS_BOOLEAN:
+        if (lit.kind == Token::WORD && (StringUtil::Lower(lit.text) == "true" || StringUtil::Lower(lit.text) == "false")) {
+            p.value = StringUtil::Lower(lit.text) == "true";
+            return;
+        }
+        if (lit.kind != Token::NUMBER || (lit.text != "0" && lit.text != "1")) throw bad("true, false, 0 or 1");
+        p.value = lit.text == "1";
+        return;
+    default: break;
+    }
+    // integers and DECIMAL: exact decimal text -> (scaled) integer
+    if (lit.kind != Token::NUMBER) throw bad("a number");
+    string t = lit.text;
+    const bool neg = t[0] == '-';
+    if (t[0] == '-' || t[0] == '+') t = t.substr(1);
+    const size_t dot = t.find('.');
+    string ip = dot == string::npos ? t : t.substr(0, dot), fp = dot == string::npos ? "" : t.substr(dot + 1);
+    if ((!ip.empty() && !AllDigits(ip)) || (!fp.empty() && !AllDigits(fp)) || (ip.empty() && fp.empty()))
+        throw bad("a number");
+    while (!fp.empty() && fp.back() == '0') fp.pop_back();
+    const unsigned scale = ci.type == FLS_DECIMAL ? ci.scale : 0;
+    if (fp.size() > scale)
+        throw bad(ci.type == FLS_DECIMAL ? "exactly representable (too many fractional digits)" : "an integer");
+    fp.resize(scale, '0');
+    const string digits = ip + fp;
+    const bool is_unsigned = ci.type >= FLS_UINT8 && ci.type <= FLS_UINT64;
+    unsigned __int128 v = 0;
+    for (char c : digits) {
+        v = v * 10 + (unsigned)(c - '0');
+        if (v > ((unsigned __int128)1 << 64)) throw bad("in range");
+    }
+    if (is_unsigned) {
+        if ((neg && v != 0) || v > UINT64_MAX) throw bad("in range");
+        p.value = (uint64_t)v;
+    } else {
+        if (v > ((unsigned __int128)1 << 63) - (neg ? 0 : 1)) throw bad("in range");
+        p.value = neg ? (uint64_t)0 - (uint64_t)v : (uint64_t)v;
+    }
+}
+
+void ParseFilter(const Schema &sch, const string &filter, std::vector<fls_predicate> &preds, std::deque<string> &strs) {
+    if (Trim(filter).empty()) return;
+    Lexer lex(filter);
+    uint32_t clause = 0;
+    for (;;) {
+        Token col = lex.Next();
+        if (col.kind != Token::WORD)
+            throw BinderException("fastlanes_aggregate: a column name is expected at \"" + col.text + "\" in filter \"" +
+                                  filter + "\"");
+        const int c = sch.Find(col.text);
+        if (c < 0)
+            throw BinderException("fastlanes_aggregate: column \"" + col.text + "\" of filter \"" + filter + "\" not found");
+        fls_predicate p;
+        memset(&p, 0, sizeof(p));
+        p.col = (uint32_t)c;
+        p.clause = clause++;
+        Token op = lex.Next();
+        if (op.kind == Token::WORD && StringUtil::Lower(op.text) == "is") {
+            Token t = lex.Next();
+            bool is_not = false;
+            if (t.kind == Token::WORD && StringUtil::Lower(t.text) == "not") {
+                is_not = true;
+                t = lex.Next();
+            }
+            if (t.kind != Token::WORD || StringUtil::Lower(t.text) != "null")
+                throw BinderException("fastlanes_aggregate: IS [NOT] NULL is expected after \"" + col.text +
+                                      "\" in filter \"" + filter + "\"");
+            p.op = is_not ? FLS_CMP_IS_NOT_NULL : FLS_CMP_IS_NULL;
+        } else if (op.kind == Token::OP) {
+            p.op = op.text == "="                        ? FLS_CMP_EQ
+                   : (op.text == "!=" || op.text == "<>") ? FLS_CMP_NE
+                   : op.text == "<"                      ? FLS_CMP_LT
+                   : op.text == "<="                     ? FLS_CMP_LE
+                   : op.text == ">"                      ? FLS_CMP_GT
+                                                         : FLS_CMP_GE;
+            SetLiteral(sch, c, lex, lex.Next(), filter, p, strs);
+        } else {
+            throw BinderException("fastlanes_aggregate: a comparison or IS [NOT] NULL is expected after \"" + col.text +
+                                  "\" in filter \"" + filter + "\"");
+        }
+        preds.push_back(p);
+        Token next = lex.Next();
+        if (next.kind == Token::END) return;
+        if (next.kind != Token::WORD || StringUtil::Lower(next.text) != "and")
+            throw BinderException("fastlanes_aggregate: only AND joins filter terms, found \"" + next.text +
+                                  "\" in filter \"" + filter + "\"");
+    }
+}
+
+unique_ptr<FunctionData> AggBind(ClientContext &, TableFunctionBindInput &input, vector<LogicalType> &return_types,
+                                 vector<string> &names) {
+    if (input.inputs.size() < 2 || input.inputs.size() > 3)
+        throw BinderException("fastlanes_aggregate takes (path, aggregates[, filter])");
+    for (auto &v : input.inputs)
+        if (v.IsNull() || v.type() != LogicalType::VARCHAR)
+            throw BinderException("fastlanes_aggregate arguments must be strings");
+    auto bind = make_uniq<AggBindData>();
+    bind->file = input.inputs[0].GetValue<string>();
+    bind->table = std::make_shared<AggTable>();
+    fls_connection *conn = SharedConnection();
+    if (!conn || fls_read_fls(conn, bind->file.c_str(), &bind->table->table) != 0)
+        throw BinderException("Failed to open FastLanes file: " + bind->file);
+    Schema sch;
+    const uint32_t n = fls_table_ncols(bind->table->table);
+    sch.cols.resize(n);
+    for (uint32_t c = 0; c < n; ++c) {
+        fls_table_column(bind->table->table, c, &sch.cols[c]);
+        sch.types.push_back(TypeMapping::FastLanesToDuckDB(sch.cols[c].type, sch.cols[c].width, sch.cols[c].scale));
+        sch.names.emplace_back(sch.cols[c].name);
+    }
+    // the aggregate list: items separated by commas outside parentheses
+    const string list = input.inputs[1].GetValue<string>();
+    vector<string> items;
+    int depth = 0;
+    size_t start = 0;
+    for (size_t i = 0; i <= list.size(); ++i) {
+        if (i < list.size() && list[i] == '(') ++depth;
+        if (i < list.size() && list[i] == ')') --depth;
+        if (i == list.size() || (list[i] == ',' && depth == 0)) {
+            items.push_back(Trim(list.substr(start, i - start)));
+            start = i + 1;
+        }
+    }
+    for (auto &item : items) {
+        if (item.empty()) throw BinderException("fastlanes_aggregate: empty item in aggregate list \"" + list + "\"");
+        fls_aggregate_spec spec;
+        LogicalType type;
+        ParseAggregate(sch, item, spec, type);
+        bind->specs.push_back(spec);
+        bind->types.push_back(type);
+        names.push_back(item);
+        bind->names.push_back(item);
+    }
+    if (bind->specs.size() > 32)
+        throw BinderException("fastlanes_aggregate: at most 32 aggregates per call, \"" + list + "\" holds " +
+                              std::to_string(bind->specs.size()));
+    if (input.inputs.size() == 3) ParseFilter(sch, input.inputs[2].GetValue<string>(), bind->preds, bind->pred_strs);
+    return_types = bind->types;
+    return std::move(bind);
+}
+
+unique_ptr<GlobalTableFunctionState> AggInitGlobal(ClientContext &, TableFunctionInitInput &) {
+    return make_uniq<AggGlobalState>();
+}
+
+// the 128-bit value as an int64, or OutOfRangeException
+int64_t Narrow(const fls_aggregate_value &v, const string &name, const LogicalType &type) {
+    const bool fits = v.hi == ((v.lo >> 63) ? ~0ull : 0ull);
+    const int64_t x = (int64_t)v.lo;
+    const bool dec_ok = type.id() != LogicalTypeId::DECIMAL || (x > -1000000000000000000ll && x < 1000000000000000000ll);
+    if (!fits || !dec_ok)
+        throw OutOfRangeException("fastlanes_aggregate: " + name + " does not fit " + type.ToString() +
+                                  " (the 128-bit sum is available through fls_aggregate)");
+    return x;
+}
+
+void AggScan(ClientContext &, TableFunctionInput &data, DataChunk &output) {
+    const auto &bind = data.bind_data->Cast<AggBindData>();
+    auto &g = data.global_state->Cast<AggGlobalState>();
+    output.Reset();
+    {
+        std::lock_guard<std::mutex> guard(g.lock);
+        if (g.done) {
+            output.SetCardinality(0);
+            return;
+        }
+        g.done = true;
+    }
+    fls_table *t = bind.table->table;
+    std::vector<fls_aggregate_value> vals(bind.specs.size());
+    if (fls_scan_filter(t, bind.preds.data(), (uint32_t)bind.preds.size()) != 0)
+        throw IOException(string("FastLanes aggregate failed: ") + fls_last_error());
+    const int rc = fls_aggregate(t, bind.specs.data(), (uint32_t)bind.specs.size(), 0, fls_table_nrowgroups(t), vals.data());
+    const string err = rc ? fls_last_error() : "";
+    fls_scan_filter(t, nullptr, 0);
+    if (rc == FLS_ERR_ARG) throw OutOfRangeException("fastlanes_aggregate: " + err);  // the SUM_PRODUCT bound
+    if (rc) throw IOException("FastLanes aggregate failed: " + err);
+    for (idx_t j = 0; j < output.ColumnCount() && j < vals.size(); ++j) {
+        const fls_aggregate_value &v = vals[j];
+        Vector &vec = output.data[j];
+        if (v.kind == FLS_AGGV_NULL) {
+            vec.SetValue(0, Value());
+        } else if (v.kind == FLS_AGGV_DOUBLE) {
+            double d;
+            memcpy(&d, &v.lo, 8);
+            vec.SetValue(0, Value::DOUBLE(d));
+        } else if (bind.specs[j].fn == FLS_AGG_MIN || bind.specs[j].fn == FLS_AGG_MAX) {
+            vec.SetValue(0, Value::BIGINT((int64_t)v.lo));  // the column's own type: its low bytes
+        } else {
+            vec.SetValue(0, Value::BIGINT(Narrow(v, bind.names[j], bind.types[j])));
+        }
+    }
+    output.SetCardinality(1);
+}
+
+}  // namespace
+
+void RegisterFastlanesAggregate(DatabaseInstance &db) {
+    TableFunction fn("fastlanes_aggregate", {LogicalType::VARCHAR, LogicalType::VARCHAR}, AggScan, AggBind, AggInitGlobal);
+    ExtensionUtil::RegisterFunction(db, fn);
+    fn.arguments = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR};
+    ExtensionUtil::RegisterFunction(db, fn);
+}
+
+}  // namespace ext_fastlane
+}  // namespace duckdb

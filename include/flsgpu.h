@@ -203,14 +203,49 @@ int fls_scan_begin(fls_table *t, const uint8_t *col_mask, uint32_t rg_begin, uin
 /* 1 = a row group was delivered into *out, 0 = end of scan, <0 = error.
  * The previous row group's buffers are released by the call. */
 int fls_scan_next(fls_table *t, fls_rowgroup *out);
-/* Filter for the following fls_scan_begin calls on this table (n = 0
- * clears).  The scan then skips row groups whose zone maps / dictionaries
+/* Filter for the following fls_scan_begin and fls_aggregate calls on this
+ * table (n = 0 clears).  The scan then skips row groups whose zone maps / dictionaries
  * rule every row out, evaluates the filter per row on the GPU and delivers
  * only qualifying rows (fls_rowgroup.nrows / sel), in row order.  The
  * filter's columns are decoded whether or not col_mask delivers them. */
 int fls_scan_filter(fls_table *t, const fls_predicate *preds, uint32_t n);
 /* Row groups the current scan skipped by zone maps / dictionaries. */
 int fls_scan_pruned(const fls_table *t);
+
+/* Ungrouped aggregates evaluated on the GPU over row groups [rg_begin, rg_end)
+ * under the filter set by fls_scan_filter: the operand columns are decoded
+ * into HBM, reduced there per 1024-row vector (csrc/fls_agg.hip), and only
+ * the per-vector partial results cross PCIe; the call folds them in row order
+ * and is synchronous.  A row contributes to an aggregate when the filter
+ * selects it and the aggregate's operand column(s) are not NULL there.
+ * Integer sums (INT*, UINT*, BOOLEAN, DATE, DECIMAL scaled) are exact 128-bit
+ * two's-complement values; FLOAT / DOUBLE sums are binary64 (FLOAT widened
+ * exactly) with IEEE propagation of NaN and infinities; float MIN / MAX use
+ * the filter's order (NaN above every number, -0 == 0).  Every result,
+ * binary64 sums included, is bit-identical whatever the batch size, slot
+ * count or number of GPUs.  Row groups the filter's zone maps / dictionaries
+ * rule out are skipped (fls_scan_pruned); when none is left the call does no
+ * device work.  The call replaces a scan in progress on the table, as
+ * fls_scan_begin does.  FLS_ERR_ARG (the message names the aggregate's index)
+ * before any device work: n == 0 or n > 32, a column out of range, an unknown
+ * function, SUM / MIN / MAX / SUM_PRODUCT of a VARCHAR / BLOB column,
+ * SUM_PRODUCT with a FLOAT / DOUBLE operand, and a SUM_PRODUCT whose zone-map
+ * bound (sum over the scanned row groups of rows * max|a| * max|b|) reaches
+ * 2^127.  Not in the reference, which delivers every decoded row to DuckDB. */
+typedef enum fls_agg_fn { FLS_AGG_COUNT_STAR = 0, FLS_AGG_COUNT = 1, FLS_AGG_SUM = 2,
+                          FLS_AGG_MIN = 3, FLS_AGG_MAX = 4, FLS_AGG_SUM_PRODUCT = 5 } fls_agg_fn;
+typedef struct fls_aggregate_spec { uint8_t fn; uint8_t pad[3]; uint32_t col; uint32_t col2; uint32_t pad2; } fls_aggregate_spec;
+typedef enum fls_agg_kind { FLS_AGGV_NULL = 0, FLS_AGGV_INT = 1, FLS_AGGV_DOUBLE = 2 } fls_agg_kind;
+typedef struct fls_aggregate_value {
+    uint64_t count;   /* rows that contributed */
+    uint64_t lo, hi;  /* INT: 128-bit two's complement (counts, integer sums, integer MIN/MAX sign- or
+                         zero-extended); DOUBLE: binary64 bits in lo (float sums; FLOAT/DOUBLE MIN/MAX widened
+                         to double as fls_table_zonemap does) */
+    uint8_t kind;     /* NULL: SUM/MIN/MAX with no contributing row (DuckDB's NULL); counts are never NULL */
+    uint8_t pad[7];
+} fls_aggregate_value;
+int fls_aggregate(fls_table *t, const fls_aggregate_spec *aggs, uint32_t n,
+                  uint32_t rg_begin, uint32_t rg_end, fls_aggregate_value *out);
 /* Zone map of column col in row group rg: 1 and *min / *max (int64, uint64
  * or double bits by column type, see fls_predicate.value; FLOAT widened to
  * double) and *flags (1 valid, 2 / 4 has / all NaN, 8 / 16 has / all NULL;
