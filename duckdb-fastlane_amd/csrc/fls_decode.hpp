@@ -186,6 +186,29 @@ bool fused_x_built(int x);
 // through DevChunk.vec_base (fls_fsst.hip).
 hipError_t launch_fsst_sp(const DevChunk *d_chunks, uint32_t nchunks, uint32_t nvecs, uint32_t *d_err,
                           hipStream_t stream);
+// Dictionary-string decode in the linear-fill shape (fls_dictstr.hip
+// dictstr_decode_kernel): one 256-thread workgroup per vector, in ascending
+// output address.  The host flattens the eligible chunks (dictstr_eligible)
+// into one DictVec per vector, so a workgroup reads 32 bytes instead of
+// chasing the chunk descriptor and its VecMeta array.
+struct DictVec {               // 32 B
+    const uint8_t *packed;     // HBM address of the vector's packed codes (128 W bytes, T = 32)
+    const uint8_t *tab;        // the chunk's string_t table (16-byte aligned)
+    uint8_t *out;              // HBM address of the vector's first string_t
+    uint32_t base;             // FFOR base of the codes
+    uint32_t info;             // nvals (bits 0-10) | W << 11 (bits 11-16) | dict_count << 17
+};
+static_assert(sizeof(DictVec) == 32, "DictVec is 32 B");
+// Largest dictionary the kernel stages (string_t entries, 1 KiB of LDS; a
+// workgroup loads the whole table for 16 KiB of output).  Larger ones stay on
+// the main decode (PathDict).
+constexpr uint32_t kDictWgMaxEntries = 64;
+inline bool dictstr_eligible(const DevChunk &c) {
+    return c.enc == 3 /*DICT*/ && c.ob == 16 && c.T == 32 && c.nvec > 0 && c.dict_count >= 1 &&
+           c.dict_count <= kDictWgMaxEntries && c.dict && ((uintptr_t)c.dict & 15) == 0 && ((uintptr_t)c.out & 15) == 0 &&
+           (((uintptr_t)c.chunk + c.packed_off) & 15) == 0;
+}
+hipError_t launch_dictstr(const DictVec *d_vecs, uint32_t nvecs, uint32_t *d_err, hipStream_t stream);
 // Resident-grid size of the v2 kernel for the given dynamic LDS per block.
 int decode_grid_size(uint32_t shmem_per_block);
 // The current device's CU count and a kernel's resident blocks per CU

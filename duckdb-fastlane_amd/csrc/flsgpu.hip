@@ -676,6 +676,14 @@ struct Resident {
     std::vector<DevChunk> h_chunks;
     std::vector<uint8_t> mask;         // column mask h_chunks was built for
     uint32_t nmain = 0;                // h_chunks[0, nmain) main kernel, the rest FSST
+    DevBuf<DictVec> d_dictvecs;        // the dictionary-string grid's vectors (launch_dictstr), built with h_chunks
+    uint32_t ndictvecs = 0;            // ... and how many (their chunks are not in h_chunks)
+    bool list_built = false;           // h_chunks / d_dictvecs describe the current mask, policy and outputs
+    void invalidate() {                // a new mask, policy or set of outputs: rebuild both at the next decode
+        h_chunks.clear();
+        ndictvecs = 0;
+        list_built = false;
+    }
     int64_t policy = -1;               // decode_policy() h_chunks was ordered for
     int64_t lpolicy = 0;                // ... and the launch policy it resolved to (launch_policy)
     FsstCounts fsst;                   // FSST chunks of h_chunks
@@ -952,6 +960,27 @@ enum : int {
 // rest (bits 16-23, default 2), FLS_BLOCKS_PER_CU (bits 24-30, 0 = unset).
 // Guided tail defaults (FLS_GUIDED_MIN_VECS / FLS_GUIDED_FACTOR, guided_split)
 constexpr int kGuidedMinVecs = 0, kGuidedFactor = 2;
+// The dictionary-string grid (fls_dictstr.hip): FLS_DICT_WG = 0 keeps every
+// chunk on the main decode, 1 (default) moves the eligible DICT VARCHAR
+// chunks of a table decode to their own grid when they hold at least
+// FLS_DICT_WG_MIN_VECS_PER_CU vectors per CU, 2 moves them whatever the size.
+// Below the threshold the second launch's drain outweighs the write rate
+// (lineitem_full, full step, grid forced against off: +3.9 % at 11 vectors per
+// CU, +1.4 % at 23, -1.2 % at 46, -1.5 % at 92, -4.2 % at 183;
+// profiles/r7/abenv_dictwg_small.txt).  FLS_DICT_WG_STREAMS: the grid's write
+// streams (order_for_launch).
+struct DictWgCfg {
+    int mode = 1;
+    uint32_t min_vecs_per_cu = 64;
+    uint32_t streams = 4;
+};
+DictWgCfg dict_wg_cfg() {
+    DictWgCfg c;
+    if (const char *e = getenv("FLS_DICT_WG")) c.mode = std::min(2, std::max(0, atoi(e)));
+    if (const char *e = getenv("FLS_DICT_WG_MIN_VECS_PER_CU")) c.min_vecs_per_cu = (uint32_t)std::min(255, std::max(0, atoi(e)));
+    if (const char *e = getenv("FLS_DICT_WG_STREAMS")) c.streams = (uint32_t)std::min(31, std::max(1, atoi(e)));
+    return c;
+}
 int64_t decode_policy() {
     const char *e = getenv("FLS_DECODE_POLICY");
     const char *sp = getenv("FLS_STATIC_PCT");
@@ -973,8 +1002,13 @@ int64_t decode_policy() {
     const char *gf = getenv("FLS_GUIDED_FACTOR");
     const int64_t gmin = gm ? std::min(64, std::max(0, atoi(gm))) : kGuidedMinVecs;
     const int64_t gfac = gf ? std::min(255, std::max(1, atoi(gf))) : kGuidedFactor;
+    // the dictionary-string grid (FLS_DICT_WG, bits 48-49) and its size
+    // threshold (FLS_DICT_WG_MIN_VECS_PER_CU, bits 50-57) move chunks between
+    // the two launch lists, its write streams (FLS_DICT_WG_STREAMS, bits
+    // 58-62) order its own
+    const DictWgCfg dw = dict_wg_cfg();
     return (int64_t)(((e ? (atoi(e) & 0xFF) : 0) | noseg) | pct << 8 | pieces << 16 | bpc << 24) | gmin << 32 |
-           gfac << 40;
+           gfac << 40 | (int64_t)dw.mode << 48 | (int64_t)dw.min_vecs_per_cu << 50 | (int64_t)dw.streams << 58;
 }
 
 // Policy for one launch: the default (no distribution bits) switches to the
@@ -994,7 +1028,44 @@ int64_t launch_policy(int64_t policy, const std::vector<DevChunk> &v, DecodeGeom
 // FSST chunks go last (their own kernels: string-parallel ones first, then
 // code-parallel ones, each group numbering its vectors through vec_base);
 // returns how many lead (main kernel) and the FSST counts
-uint32_t order_for_launch(std::vector<DevChunk> &v, FsstCounts *fc, int64_t policy) {
+// dictwg (a table decode, decode_part): the chunks the dictionary-string grid
+// takes (dictstr_eligible, FLS_DICT_WG) leave v for it, in the order its
+// workgroups are laid out in: ascending output address, as S interleaved
+// streams (below).
+uint32_t order_for_launch(std::vector<DevChunk> &v, FsstCounts *fc, int64_t policy,
+                          std::vector<DevChunk> *dictwg = nullptr) {
+    if (dictwg) {
+        dictwg->clear();
+        const int mode = (int)((policy >> 48) & 3);
+        uint64_t vecs = 0;
+        for (const DevChunk &d : v)
+            if (dictstr_eligible(d)) vecs += d.nvec;
+        const uint64_t need = mode == 2 ? 1 : (uint64_t)((policy >> 50) & 0xFF) * (uint64_t)device_cus();
+        if (mode > 0 && vecs > 0 && vecs >= need && vecs <= UINT32_MAX) {
+            auto rest = std::stable_partition(v.begin(), v.end(), [](const DevChunk &d) { return !dictstr_eligible(d); });
+            dictwg->assign(rest, v.end());
+            v.erase(rest, v.end());
+            std::stable_sort(dictwg->begin(), dictwg->end(),
+                             [](const DevChunk &a, const DevChunk &b) { return a.out < b.out; });
+            // S write streams (FLS_DICT_WG_STREAMS): the sorted list cut into
+            // S runs of as many chunks, taken round-robin, so S regions fill
+            // at once, each in ascending address.  lineitem_full SF100, the
+            // four string columns: S = 1 / 2 / 4 / 8 -> 6.90 / 5.96 / 5.72 /
+            // 5.74 ms (S = 4: one stream per column); one ascending sequence
+            // over several buffers is no faster than the main decode there
+            // (6.87 ms).  c4: 2.56 / 2.50 / 2.50 / 2.51 ms
+            // (profiles/r7/abenv_dictwg_streams_*.txt)
+            const size_t n = dictwg->size(), S = std::min<size_t>(std::max<size_t>(1, (size_t)((policy >> 58) & 31)), n);
+            if (S > 1) {
+                std::vector<DevChunk> il;
+                il.reserve(n);
+                for (size_t i = 0; il.size() < n; ++i)
+                    for (size_t s = 0; s < S; ++s)
+                        if (s * n / S + i < (s + 1) * n / S) il.push_back((*dictwg)[s * n / S + i]);
+                dictwg->swap(il);
+            }
+        }
+    }
     auto mid = std::stable_partition(v.begin(), v.end(), [](const DevChunk &d) { return d.enc != ENC_FSST; });
     std::stable_sort(mid, v.end(), [](const DevChunk &a, const DevChunk &b) {
         return fsst_group(a.vbits) < fsst_group(b.vbits);
@@ -1254,7 +1325,14 @@ hipError_t launch_cu_split(const DevChunk *d_chunks, uint32_t nmain, const FsstC
 
 hipError_t launch_all(const DevChunk *d_chunks, uint32_t nmain, uint32_t ntotal, const FsstCounts &fc,
                       uint32_t *d_err, const DecodeGeom &geom, hipStream_t stream, uint32_t *d_queue, int64_t policy,
-                      SplitPlan plan, const SideStream *side = nullptr) {
+                      SplitPlan plan, const SideStream *side = nullptr, const DictVec *d_dictvecs = nullptr,
+                      uint32_t ndictvecs = 0) {
+    // the dictionary-string grid first, on the same stream: its chunks are not
+    // in d_chunks, and a launch may consist of it alone
+    if (ndictvecs) {
+        const hipError_t de = launch_dictstr(d_dictvecs, ndictvecs, d_err, stream);
+        if (de != hipSuccess || ntotal == 0) return de;
+    }
     // a guided plan only orders the serial launch: the overlapped and
     // CU-split launches drain whole chunks from a queue several grids share
     const uint32_t *d_split = plan.waves ? reinterpret_cast<const uint32_t *>(d_chunks + ntotal) : nullptr;
@@ -1298,7 +1376,13 @@ hipError_t launch_all(const DevChunk *d_chunks, uint32_t nmain, uint32_t ntotal,
             // 21.79 ms against 21.93 with 5), 5 below 1,000 FSST vectors per
             // CU (SF12.5: 3.115 against 3.133 ms with 6; profiles/r5/)
             FusedLaunch how = fz.how;
-            if (!fz.per16_set) how.fsst_per16 = fsst_vecs < 1000ull * (uint64_t)cus ? 5u : 6u;
+            // With the DICT VARCHAR chunks on their own grid the main queue
+            // holds about half the bytes and the FSST part needs more of the
+            // waves: 8 of 16 (SF100: 20.57 ms against 20.91 with 6 and 20.71
+            // with 9; SF12.5: 2.704 against 2.820 with 5 and 2.714 with 6,
+            // while without the grid 7 and 8 lose to 6;
+            // profiles/r7/abenv_dictwg_fsst16_*.txt)
+            if (!fz.per16_set) how.fsst_per16 = ndictvecs ? 8u : fsst_vecs < 1000ull * (uint64_t)cus ? 5u : 6u;
             return launch_fused(d_chunks, nmain, d_chunks + nmain + fc.first(g), fc.n[g], fc.vecs[g], g == 0, d_err,
                                 geom, stream, d_queue, how);
         }
@@ -3077,7 +3161,7 @@ int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask);
 float decode_rating(fls_table *t, Resident &r) {
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
     const std::vector<uint8_t> mask(ncols, 1);
-    r.h_chunks.clear();  // descriptors point at the current outputs
+    r.invalidate();  // descriptors point at the current outputs
     const uint32_t ev0 = r.ev_used;
     struct RatingScope {
         RatingScope() { rating_launch() = true; }
@@ -3100,7 +3184,7 @@ float decode_rating(fls_table *t, Resident &r) {
     (void)hipGetLastError();
     (void)hipMemset(r.err.p, 0, sizeof(uint32_t));
     r.ev_used = ev0;
-    r.h_chunks.clear();
+    r.invalidate();
     return ok ? ms : -1.0f;
 }
 
@@ -3265,7 +3349,7 @@ int upload_part(fls_table *t, Resident &r) {
             r.h_heap[c].release();
         }
     }
-    r.h_chunks.clear();
+    r.invalidate();
     r.mask.clear();
     if (const int prc = choose_placement(t, r)) return prc;
     if (getenv("FLS_DEBUG")) {  // buffer placement (decode speed by buffer address)
@@ -3283,7 +3367,7 @@ int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask) {
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
     HIP_TRY(hipSetDevice(r.dev));
     const int64_t policy = decode_policy();
-    if (mask != r.mask || r.h_chunks.empty() || policy != r.policy) {
+    if (mask != r.mask || !r.list_built || policy != r.policy) {
         // (re)build the launch descriptor list: column-major task order, so
         // concurrent waves stream one column's consecutive row groups
         std::vector<DevChunk> chunks;
@@ -3302,7 +3386,27 @@ int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask) {
             }
         }
         const int64_t lpol = launch_policy(policy, chunks, bc.geom);
-        r.nmain = order_for_launch(chunks, &r.fsst, lpol);
+        std::vector<DevChunk> dictwg;
+        r.nmain = order_for_launch(chunks, &r.fsst, lpol, &dictwg);
+        // one DictVec per vector of the chunks the dictionary-string grid takes,
+        // from the host image's VecMeta arrays (validated when the file was read)
+        std::vector<DictVec> dvecs;
+        for (const DevChunk &d : dictwg) {
+            const uint8_t *meta = t->img + r.base + (d.chunk - r.img.p) + d.meta_off;
+            for (uint32_t v = 0; v < d.nvec; ++v) {
+                VecMeta vm;
+                memcpy(&vm, meta + 32ull * v, 32);
+                dvecs.push_back(DictVec{d.chunk + d.packed_off + vm.packed_off, d.dict,
+                                        d.out + (size_t)v * kVectorSize * 16, (uint32_t)vm.for_base,
+                                        (uint32_t)vm.nvals | (uint32_t)vm.bw << 11 | d.dict_count << 17});
+            }
+        }
+        if (getenv("FLS_DEBUG")) {
+            size_t kept = 0;
+            for (size_t i = 0; i < r.nmain; ++i) kept += chunks[i].enc == ENC_DICT && chunks[i].ob == 16;
+            fprintf(stderr, "DEBUG: dictstr_decode_kernel takes %zu chunks (%zu vectors), %zu DICT VARCHAR chunks stay "
+                            "on the main decode\n", dictwg.size(), dvecs.size(), kept);
+        }
         r.policy = policy;
         r.lpolicy = lpol;
         const size_t k = chunks.size();
@@ -3310,6 +3414,11 @@ int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask) {
         HIP_TRY(hipStreamSynchronize(r.stream));
         HIP_TRY(r.d_chunks.alloc(r.dev, chunks.size()));
         HIP_TRY(hipMemcpy(r.d_chunks.p, chunks.data(), chunks.size() * sizeof(DevChunk), hipMemcpyHostToDevice));
+        HIP_TRY(r.d_dictvecs.alloc(r.dev, dvecs.size()));
+        if (!dvecs.empty())
+            HIP_TRY(hipMemcpy(r.d_dictvecs.p, dvecs.data(), dvecs.size() * sizeof(DictVec), hipMemcpyHostToDevice));
+        r.ndictvecs = (uint32_t)dvecs.size();
+        r.list_built = true;
         chunks.resize(k);
         r.h_chunks.swap(chunks);
         r.mask = mask;
@@ -3335,7 +3444,7 @@ int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask) {
     r.ev_used += 2;
     HIP_TRY(hipEventRecord(e0, r.stream));
     HIP_TRY(launch_all(r.d_chunks.p, r.nmain, (uint32_t)r.h_chunks.size(), r.fsst, r.err.p, r.bytes.geom, r.stream,
-                       r.queue.p, r.lpolicy, r.split, &r.side));
+                       r.queue.p, r.lpolicy, r.split, &r.side, r.d_dictvecs.p, r.ndictvecs));
     HIP_TRY(hipEventRecord(e1, r.stream));
     return 0;
 }

@@ -78,7 +78,7 @@ def main():
                 st = run(env, sel, a.reps)
                 times[n].append(st.kernel_ms_total / st.timed_launches)
                 algo = st.algo_bytes
-        line = {n: {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4),
+        line = {n: {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4),
                     "GBps": round(algo / statistics.median(v) / 1e6, 1)} for n, v in times.items()}
         if not a.no_verify:  # every arm's output, bit-exact against the seeded generator (on the GPU)
             for n, env in arms:
