@@ -88,6 +88,16 @@ class AggregateValue(C.Structure):
                 ("pad", C.c_uint8 * 7)]
 
 
+# fls_key_kind / fls_group_key (include/flsgpu.h)
+KEYV_NULL, KEYV_INT, KEYV_STRING = 0, 1, 2
+ERR_LIMIT = -8
+
+
+class GroupKey(C.Structure):
+    _fields_ = [("kind", C.c_uint8), ("pad", C.c_uint8 * 7), ("lo", C.c_uint64), ("hi", C.c_uint64),
+                ("str", C.c_void_p), ("str_len", C.c_uint64)]
+
+
 class DecodeStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("values", C.c_uint64), ("packed_bytes", C.c_uint64),
                 ("meta_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("launches", C.c_uint32),
@@ -141,6 +151,12 @@ _sig("fls_scan_filter", C.c_int, _P, C.POINTER(Predicate), C.c_uint32)
 _sig("fls_scan_pruned", C.c_int, _P)
 _sig("fls_aggregate", C.c_int, _P, C.POINTER(AggregateSpec), C.c_uint32, C.c_uint32, C.c_uint32,
      C.POINTER(AggregateValue))
+_sig("fls_aggregate_grouped", C.c_int, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(AggregateSpec), C.c_uint32,
+     C.c_uint32, C.c_uint32, C.POINTER(_P))
+_sig("fls_group_result_ngroups", C.c_uint64, _P)
+_sig("fls_group_result_key", C.c_int, _P, C.c_uint64, C.c_uint32, C.POINTER(GroupKey))
+_sig("fls_group_result_values", C.POINTER(AggregateValue), _P, C.c_uint64)
+_sig("fls_group_result_free", None, _P)
 _sig("fls_table_zonemap", C.c_int, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
      C.POINTER(C.c_uint32))
 _sig("fls_scan_dict_codes", C.c_int, _P, C.c_int)
@@ -512,6 +528,30 @@ def _mask(t: "Table", cols) -> C.Array | None:
     return m
 
 
+def _agg_specs(aggs) -> C.Array:
+    """fls_aggregate_spec[] of aggregate()'s tuples; a first element that is an
+    int is passed through as the function code"""
+    arr = (AggregateSpec * max(1, len(aggs)))()
+    for i, a in enumerate(aggs[:len(arr)]):
+        fn = a[0]
+        if isinstance(fn, str):
+            fn = AGG_FNS["count_star" if fn == "count" and len(a) == 1 else fn]
+        arr[i].fn = fn
+        arr[i].col = a[1] if len(a) > 1 else 0
+        arr[i].col2 = a[2] if len(a) > 2 else 0
+    return arr
+
+
+def _agg_value(v: AggregateValue):
+    """an fls_aggregate_value as aggregate() returns it"""
+    if v.kind == AGGV_NULL:
+        return None
+    if v.kind == AGGV_DOUBLE:
+        return float(np.array([v.lo], dtype=np.uint64).view(np.float64)[0])
+    x = (v.hi << 64) | v.lo
+    return x - (1 << 128) if x >> 127 else x
+
+
 class Table:
     def __init__(self, h, conn):
         self.h, self.conn, self._keep = h, conn, None
@@ -745,14 +785,7 @@ class Table:
         that is an int is passed through as the function code."""
         if rg_end is None:
             rg_end = self.nrowgroups
-        arr = (AggregateSpec * max(1, len(aggs)))()
-        for i, a in enumerate(aggs[:len(arr)]):
-            fn = a[0]
-            if isinstance(fn, str):
-                fn = AGG_FNS["count_star" if fn == "count" and len(a) == 1 else fn]
-            arr[i].fn = fn
-            arr[i].col = a[1] if len(a) > 1 else 0
-            arr[i].col2 = a[2] if len(a) > 2 else 0
+        arr = _agg_specs(aggs)
         out = (AggregateValue * max(1, len(aggs)))()
         _check(_lib.fls_aggregate(self.h, arr, len(aggs), rg_begin, rg_end, out))
         return list(out)[:len(aggs)]
@@ -769,16 +802,46 @@ class Table:
             vals = self.aggregate_raw(aggs, rg_begin, rg_end)
         finally:
             _check(_lib.fls_scan_filter(self.h, None, 0))
-        out = []
-        for v in vals:
-            if v.kind == AGGV_NULL:
-                out.append(None)
-            elif v.kind == AGGV_DOUBLE:
-                out.append(float(np.array([v.lo], dtype=np.uint64).view(np.float64)[0]))
-            else:
-                x = (v.hi << 64) | v.lo
-                out.append(x - (1 << 128) if x >> 127 else x)
-        return out
+        return [_agg_value(v) for v in vals]
+
+    def aggregate_grouped(self, keys, aggs, filt=None, rg_begin=0, rg_end=None) -> list:
+        """GROUP BY keys (1 to 4 column indices of low cardinality) of the
+        aggregates aggregate() takes, evaluated on the GPU
+        (fls_aggregate_grouped).  Returns [(key_tuple, values)] in order of
+        each group's first row; a key element is an int, bytes (a VARCHAR key)
+        or None (NULL, a group of its own), values as aggregate() returns
+        them.  FlsError with code ERR_LIMIT past 64 distinct keys in a
+        1024-row vector or 256 in a row group."""
+        if rg_end is None:
+            rg_end = self.nrowgroups
+        karr = (C.c_uint32 * max(1, len(keys)))(*keys[:max(1, len(keys))])
+        arr = _agg_specs(aggs)
+        res = _P()
+        self.set_filter(filt)
+        try:
+            _check(_lib.fls_aggregate_grouped(self.h, karr, len(keys), arr, len(aggs), rg_begin, rg_end,
+                                              C.byref(res)))
+        finally:
+            _check(_lib.fls_scan_filter(self.h, None, 0))
+        try:
+            out = []
+            k = GroupKey()
+            for g in range(_lib.fls_group_result_ngroups(res)):
+                key = []
+                for q in range(len(keys)):
+                    _check(_lib.fls_group_result_key(res, g, q, C.byref(k)))
+                    if k.kind == KEYV_NULL:
+                        key.append(None)
+                    elif k.kind == KEYV_STRING:
+                        key.append(C.string_at(k.str, k.str_len) if k.str_len else b"")
+                    else:
+                        x = (k.hi << 64) | k.lo
+                        key.append(x - (1 << 128) if x >> 127 else x)
+                vals = _lib.fls_group_result_values(res, g)
+                out.append((tuple(key), [_agg_value(vals[i]) for i in range(len(aggs))]))
+            return out
+        finally:
+            _lib.fls_group_result_free(res)
 
     # -- device-resident decode (bench)
     def device_upload(self, rg_begin=0, rg_end=None):

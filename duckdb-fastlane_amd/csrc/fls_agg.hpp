@@ -34,7 +34,8 @@ struct DevAgg {               // 48 B
     uint8_t fn;               // AggFn
     uint8_t ob, ob2;          // bytes per decoded value
     uint8_t kind, kind2;      // FilterKind of the operands: FK_INT / FK_UINT / FK_FLOAT
-    uint8_t pad[11];
+    uint8_t fslot;            // grouped call: which of the FLOAT / DOUBLE sums this is (fls_groupagg.hpp)
+    uint8_t pad[10];
 };
 static_assert(sizeof(DevAgg) == 48, "DevAgg is 48 B");
 

@@ -27,6 +27,7 @@
 #include <chrono>
 #include <cmath>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/flsgpu.h"
@@ -36,6 +37,7 @@
 #include "fls_decode.hpp"
 #include "fls_filter.hpp"
 #include "fls_format.hpp"
+#include "fls_groupagg.hpp"
 #include "fls_pinned.hpp"
 #include "fls_reader.hpp"
 #include "fls_resident.hpp"
@@ -379,6 +381,10 @@ struct HostBatch {
     std::atomic<bool> upload_resident{false};  // the batch uploads into the resident image (marked present once done)
     PinBuf<uint32_t> h_err;               // the device error flags, copied after the batch's kernels
     PinBuf<AggRec> h_agg;                 // aggregate scan: nvec x naggs partial records (vector-major)
+    // grouped aggregate scan: per row group of the batch its table of groups
+    // (fls_groupagg.hpp, group_rg_stride(naggs, g_nfsum, g_rg_vecs) bytes each)
+    PinBuf<uint8_t> h_grp;
+    uint32_t g_nfsum = 0, g_rg_vecs = 0;
     HostBatch() = default;
     HostBatch(const HostBatch &) = delete;
     HostBatch &operator=(const HostBatch &) = delete;
@@ -420,6 +426,11 @@ struct Slot {                       // one batch of row groups in flight
     PinBuf<DevAgg> h_adesc;
     DevBuf<DevAgg> d_adesc;
     DevBuf<AggRec> d_agg;           // partial records of the batch
+    // grouped aggregate batches (fls_aggregate_grouped)
+    PinBuf<uint8_t> h_gdesc;        // DevKey[kMaxKeys] + per row group its first vector and vector count
+    DevBuf<uint8_t> d_gdesc;
+    DevBuf<uint8_t> d_gvec;         // stage 1: the vectors' groups
+    DevBuf<uint8_t> d_grg;          // stage 2: the row groups' groups
 };
 
 // One GPU's scan pipeline: streams, the two device slots and the pinned
@@ -489,6 +500,9 @@ struct ScanCtx {
     // aggregate scan (fls_aggregate; empty: a delivering scan): no column is
     // delivered, each batch's partial records ride in its HostBatch
     std::vector<HostAgg> aggs;
+    // GROUP BY columns of a grouped aggregate scan (fls_aggregate_grouped;
+    // empty: ungrouped): decoded like operands, VARCHAR keys as dictionary codes
+    std::vector<uint32_t> keys;
     bool dict_codes = false;        // deliver DICT string chunks as codes + dictionary
     bool narrow = false;            // deliver integer columns narrowed to their row groups' ranges
     bool defer_records = false;     // FSST-as-lengths records built by fls_scan_build_records, not scan_acquire
@@ -520,7 +534,7 @@ struct ScanCtx {
 
 // Pinned bytes a host batch holds (its columns, FSST heaps, selection).
 size_t pinned_bytes(const HostBatch &b) {
-    size_t t = b.h_counts.n * sizeof(uint32_t) + b.h_sel.n * sizeof(uint32_t) + b.h_agg.n * sizeof(AggRec);
+    size_t t = b.h_counts.n * sizeof(uint32_t) + b.h_sel.n * sizeof(uint32_t) + b.h_agg.n * sizeof(AggRec) + b.h_grp.n;
     for (auto &x : b.h_out) t += x.n;
     for (auto &x : b.h_heap) t += x.n;
     return t;
@@ -529,7 +543,8 @@ size_t pinned_bytes(const ScanDev &d) {
     size_t t = 0;
     for (auto &b : d.batches) t += pinned_bytes(*b);
     for (auto &sl : d.slots)
-        t += sl.h_chunks.n * sizeof(DevChunk) + sl.h_stage.n + sl.h_fdesc.n + sl.h_adesc.n * sizeof(DevAgg);
+        t += sl.h_chunks.n * sizeof(DevChunk) + sl.h_stage.n + sl.h_fdesc.n + sl.h_adesc.n * sizeof(DevAgg) +
+             sl.h_gdesc.n;
     return t;
 }
 
@@ -1584,7 +1599,8 @@ std::shared_ptr<DevImage> resident_image(fls_table *t, int dev, uint32_t g, uint
 }
 
 int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uint8_t *col_mask, uint32_t rg0,
-               uint32_t rg1, const std::vector<HostTerm> *filter, const std::vector<HostAgg> *aggs = nullptr) {
+               uint32_t rg1, const std::vector<HostTerm> *filter, const std::vector<HostAgg> *aggs = nullptr,
+               const std::vector<uint32_t> *keys = nullptr) {
     ProfTimer prof(PROF_SETUP);
     t->profiled = t->profiled || ScanProf::on();
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
@@ -1625,6 +1641,16 @@ int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uin
         for (auto &a : s.aggs) {
             if (a.fn >= AGG_SUM) s.dmask[a.col] = 1;
             if (a.fn == AGG_SUM_PRODUCT) s.dmask[a.col2] = 1;
+        }
+    }
+    // the GROUP BY columns of a grouped aggregate scan are decoded too
+    s.keys.clear();
+    bool string_key = false;
+    if (aggs && keys) {
+        s.keys = *keys;
+        for (uint32_t c : s.keys) {
+            s.dmask[c] = 1;
+            string_key = string_key || type_is_string(t->meta.cols[c].type);
         }
     }
     // row-group pruning on zone maps / dictionaries
@@ -1692,7 +1718,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uin
             rc = build_strtabs(t, d.dev, d.rg0, d.rg1, d.strtab, d.strtab_off, d.h_strtab);
         }
         if (rc) return rc;
-        if (s.dict_codes && !d.ident.p) {
+        if ((s.dict_codes || string_key) && !d.ident.p) {
             std::vector<uint8_t> id(kIdent16 + 2 * 65536);
             for (uint32_t i = 0; i < 256; ++i) id[i] = (uint8_t)i;
             for (uint32_t i = 0; i < 65536; ++i) memcpy(&id[kIdent16 + 2 * i], &i, 2);
@@ -1731,6 +1757,7 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
         if (a.fn != AGG_COUNT_STAR) need[a.col] = 1;
         if (a.fn == AGG_SUM_PRODUCT) need[a.col2] = 1;
     }
+    for (uint32_t c : s.keys) need[c] = 1;
     for (uint32_t c = 0; c < ncols; ++c) {
         bool any = false;
         for (uint32_t r = sl.rg0; need[c] && r < sl.rg0 + sl.nrg; ++r)
@@ -1825,22 +1852,14 @@ int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
     return 0;
 }
 
-// Aggregate descriptors of a batch and the launch that reduces it: one
-// partial record per (vector, aggregate) into sl.d_agg, copied to the host
-// batch on the slot's stream.  The selection mask is the filter kernel's
-// (enqueue_filter ran before) or none.
-int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
-    HostBatch &hb = *sl.hb;
-    const bool filtered = !s.terms.empty();
-    if (!filtered)  // (enqueue_filter staged the filter's and the operands' validity together)
-        if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
+// The aggregates of a batch as the kernels see them (sl.h_adesc -> sl.d_adesc
+// on the slot's stream), over the slot's decoded columns and staged validity.
+int upload_agg_descs(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl) {
     const std::vector<uint8_t> &need = sl.valid_staged;
     const uint32_t na = (uint32_t)s.aggs.size();
-    hb.nvec = (uint32_t)((rows + 1023) / 1024);
     HIP_TRY(sl.h_adesc.alloc(na));
     HIP_TRY(sl.d_adesc.alloc(d.dev, na));
-    HIP_TRY(sl.d_agg.alloc(d.dev, (size_t)hb.nvec * na));
-    HIP_TRY(hb.h_agg.alloc((size_t)hb.nvec * na));
+    uint8_t nfsum = 0;
     auto kind_of = [&](uint32_t c) -> uint8_t {
         const uint8_t ty = t->meta.cols[c].type;
         return type_is_float(ty) ? FK_FLOAT : type_is_signed(ty) ? FK_INT : FK_UINT;
@@ -1856,6 +1875,7 @@ int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t r
         da.col = sl.d_out[a.col].p;
         da.ob = (uint8_t)out_bytes_of(t, a.col);
         da.kind = kind_of(a.col);
+        if (a.fn == AGG_SUM && da.kind == FK_FLOAT) da.fslot = nfsum++;
         if (a.fn != AGG_SUM_PRODUCT) continue;
         da.col2 = sl.d_out[a.col2].p;
         da.ob2 = (uint8_t)out_bytes_of(t, a.col2);
@@ -1863,10 +1883,104 @@ int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t r
         da.valid2 = need[a.col2] ? sl.d_valid[a.col2].p : nullptr;
     }
     HIP_TRY(hipMemcpyAsync(sl.d_adesc.p, sl.h_adesc.p, na * sizeof(DevAgg), hipMemcpyHostToDevice, sl.stream));
+    return 0;
+}
+
+// Aggregate descriptors of a batch and the launch that reduces it: one
+// partial record per (vector, aggregate) into sl.d_agg, copied to the host
+// batch on the slot's stream.  The selection mask is the filter kernel's
+// (enqueue_filter ran before) or none.
+int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
+    HostBatch &hb = *sl.hb;
+    const bool filtered = !s.terms.empty();
+    if (!filtered)  // (enqueue_filter staged the filter's and the operands' validity together)
+        if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
+    const uint32_t na = (uint32_t)s.aggs.size();
+    hb.nvec = (uint32_t)((rows + 1023) / 1024);
+    HIP_TRY(sl.d_agg.alloc(d.dev, (size_t)hb.nvec * na));
+    HIP_TRY(hb.h_agg.alloc((size_t)hb.nvec * na));
+    if (int rc = upload_agg_descs(t, s, d, sl)) return rc;
     HIP_TRY(launch_aggregate(sl.d_adesc.p, na, (uint32_t)rows, filtered ? sl.d_mask.p : nullptr, sl.d_agg.p,
                              sl.stream));
     HIP_TRY(hipMemcpyAsync(hb.h_agg.p, sl.d_agg.p, (size_t)hb.nvec * na * sizeof(AggRec), hipMemcpyDeviceToHost,
                            sl.stream));
+    return 0;
+}
+
+// Bit layout of the packed key of a grouped aggregate (fls_groupagg.hpp): key
+// q's value at shift[q] in bits[q] bits -- 8 x the decoded value's bytes, 16
+// for a VARCHAR key's dictionary code -- then one NULL bit per key.
+struct KeyLayout {
+    uint32_t shift[kMaxKeys] = {}, bits[kMaxKeys] = {}, null_bit[kMaxKeys] = {};
+    uint32_t total = 0;
+};
+KeyLayout key_layout(const fls_table *t, const std::vector<uint32_t> &keys) {
+    KeyLayout L;
+    for (size_t q = 0; q < keys.size() && q < kMaxKeys; ++q) {
+        const uint8_t ty = t->meta.cols[keys[q]].type;
+        L.shift[q] = L.total;
+        L.bits[q] = type_is_string(ty) ? 16 : (uint32_t)type_value_bits(ty);
+        L.total += L.bits[q];
+    }
+    for (size_t q = 0; q < keys.size() && q < kMaxKeys; ++q) L.null_bit[q] = L.total++;
+    return L;
+}
+
+// The grouped counterpart of enqueue_aggregate: stage 1 reduces every vector
+// per distinct key into sl.d_gvec, stage 2 merges the vectors of each row
+// group into sl.d_grg, and the row groups' tables are the batch's only D2H.
+int enqueue_group_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
+    HostBatch &hb = *sl.hb;
+    const bool filtered = !s.terms.empty();
+    if (!filtered)  // (enqueue_filter staged the filter's, the operands' and the keys' validity together)
+        if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
+    const std::vector<uint8_t> &need = sl.valid_staged;
+    const uint32_t na = (uint32_t)s.aggs.size(), nk = (uint32_t)s.keys.size();
+    hb.nvec = (uint32_t)((rows + 1023) / 1024);
+    if (int rc = upload_agg_descs(t, s, d, sl)) return rc;
+    uint32_t nfsum = 0, rg_vecs = 1;
+    for (uint32_t i = 0; i < na; ++i) nfsum += s.aggs[i].fn == AGG_SUM && sl.h_adesc.p[i].kind == FK_FLOAT;
+    for (uint32_t r = sl.rg0; r < sl.rg0 + sl.nrg; ++r)
+        rg_vecs = std::max(rg_vecs, (t->meta.rgs[r].nrows + kVectorSize - 1) / kVectorSize);
+    hb.g_nfsum = nfsum;
+    hb.g_rg_vecs = rg_vecs;
+    const size_t gd_bytes = kMaxKeys * sizeof(DevKey) + 2ull * sl.nrg * sizeof(uint32_t);
+    HIP_TRY(sl.h_gdesc.alloc(gd_bytes));
+    HIP_TRY(sl.d_gdesc.alloc(d.dev, gd_bytes));
+    memset(sl.h_gdesc.p, 0, gd_bytes);
+    DevKey *dk = (DevKey *)sl.h_gdesc.p;
+    uint32_t *rgvec = (uint32_t *)(sl.h_gdesc.p + kMaxKeys * sizeof(DevKey));
+    const KeyLayout L = key_layout(t, s.keys);
+    for (uint32_t q = 0; q < nk; ++q) {
+        const uint32_t c = s.keys[q];
+        // hb.ob: the decode's bytes per row (a VARCHAR key: its codes' width in this batch)
+        if (hb.ob[c] * 8u > L.bits[q])
+            return fail(FLS_ERR_STATE, "internal: key column %u decoded %u bytes wide", c, hb.ob[c]);
+        dk[q].col = sl.d_out[c].p;
+        dk[q].valid = need[c] ? sl.d_valid[c].p : nullptr;
+        dk[q].ob = hb.ob[c];
+        dk[q].shift = (uint8_t)L.shift[q];
+        dk[q].null_bit = (uint8_t)L.null_bit[q];
+    }
+    uint64_t vecs = 0;
+    for (uint32_t r = 0; r < sl.nrg; ++r) {
+        const RowGroupMeta &rg = t->meta.rgs[sl.rg0 + r];
+        rgvec[2 * r] = (uint32_t)((rg.first_row - t->meta.rgs[sl.rg0].first_row) / kVectorSize);
+        rgvec[2 * r + 1] = (uint32_t)((rg.nrows + kVectorSize - 1) / kVectorSize);
+        vecs = std::max<uint64_t>(vecs, (uint64_t)rgvec[2 * r] + rgvec[2 * r + 1]);
+    }
+    if (vecs > hb.nvec) return fail(FLS_ERR_STATE, "internal: row groups of a batch past its %u vectors", hb.nvec);
+    const size_t rg_stride = group_rg_stride(na, nfsum, rg_vecs);
+    HIP_TRY(sl.d_gvec.alloc(d.dev, (size_t)hb.nvec * group_vec_stride(na)));
+    HIP_TRY(sl.d_grg.alloc(d.dev, (size_t)sl.nrg * rg_stride));
+    HIP_TRY(hb.h_grp.alloc((size_t)sl.nrg * rg_stride));
+    HIP_TRY(hipMemcpyAsync(sl.d_gdesc.p, sl.h_gdesc.p, gd_bytes, hipMemcpyHostToDevice, sl.stream));
+    HIP_TRY(launch_group_vectors((const DevKey *)sl.d_gdesc.p, nk, sl.d_adesc.p, na, (uint32_t)rows,
+                                 filtered ? sl.d_mask.p : nullptr, sl.d_gvec.p, d.err.p, sl.stream));
+    HIP_TRY(launch_group_rowgroups(sl.d_adesc.p, na, nfsum,
+                                   (const uint32_t *)(sl.d_gdesc.p + kMaxKeys * sizeof(DevKey)), sl.nrg, rg_vecs,
+                                   sl.d_gvec.p, sl.d_grg.p, d.err.p, sl.stream));
+    HIP_TRY(hipMemcpyAsync(hb.h_grp.p, sl.d_grg.p, (size_t)sl.nrg * rg_stride, hipMemcpyDeviceToHost, sl.stream));
     return 0;
 }
 
@@ -1979,11 +2093,16 @@ int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     hb.ob.assign(ncols, 0);
     hb.dict_ptrs.assign((size_t)sl.nrg * ncols, nullptr);
     hb.dict_sizes.assign((size_t)sl.nrg * ncols, 0);
-    std::vector<uint8_t> code_w(ncols, 0), in_term(ncols, 0);
+    // A VARCHAR key of a grouped aggregate is decoded as codes the same way,
+    // whatever is delivered: its key within a row group is the code
+    // (fls_aggregate_grouped has checked the chunks).
+    std::vector<uint8_t> code_w(ncols, 0), in_term(ncols, 0), is_key(ncols, 0);
     for (auto &h : s.terms) in_term[h.col] = 1;
+    for (uint32_t c : s.keys) is_key[c] = 1;
     for (uint32_t c = 0; c < ncols; ++c) {
         hb.ob[c] = (uint8_t)out_bytes_of(t, c);
-        if (!s.dict_codes || !col_selected(s.mask, c) || in_term[c] || !type_is_string(t->meta.cols[c].type)) continue;
+        const bool coded = is_key[c] || (s.dict_codes && col_selected(s.mask, c));
+        if (!coded || in_term[c] || !type_is_string(t->meta.cols[c].type)) continue;
         bool all = true;
         uint32_t maxd = 0;
         for (uint32_t r = sl.rg0; r < sl.rg0 + sl.nrg; ++r) {
@@ -2180,8 +2299,11 @@ int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
         if (rc) return rc;
     }
     // 3b. aggregate scan: reduce under the mask; the partial records are the batch's only D2H
+    // (grouped: the row groups' tables of groups)
     if (!s.aggs.empty())
-        if (int rc = enqueue_aggregate(t, s, d, sl, rows, lo)) return rc;
+        if (int rc = s.keys.empty() ? enqueue_aggregate(t, s, d, sl, rows, lo)
+                                    : enqueue_group_aggregate(t, s, d, sl, rows, lo))
+            return rc;
     // 3. D2H into pinned host columns (and string heaps)
     if (hb.pt[1]) HIP_TRY(hipEventRecord(hb.pt[1], sl.stream));
     hb.prof_d2h = 0;
@@ -2396,6 +2518,15 @@ int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
         if (err & KERR_NARROW)
             return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a narrowed column (flags 0x%x)", err);
         if (err & KERR_LDS_BASE) return fail(FLS_ERR_DEVICE, "FSST kernel: dynamic LDS not at address 0 (flags 0x%x)", err);
+        // a grouped aggregate past its capacity: the kernels stopped before they wrote past a table
+        if (err == KERR_GROUP_RG)
+            return fail(FLS_ERR_LIMIT,
+                        "grouped aggregate: more than %u distinct keys in one row group (kMaxRgGroups); fall back to a "
+                        "scan and group its rows (flags 0x%x)", kMaxRgGroups, err);
+        if (err && !(err & ~(KERR_GROUP_VEC | KERR_GROUP_RG)))
+            return fail(FLS_ERR_LIMIT,
+                        "grouped aggregate: more than %u distinct keys among the selected rows of one 1024-row vector "
+                        "(kMaxVecGroups); fall back to a scan and group its rows (flags 0x%x)", kMaxVecGroups, err);
         if (err) return fail(FLS_ERR_FORMAT, "corrupt chunk detected while decoding (flags 0x%x)", err);
         return 0;
     };
@@ -2892,18 +3023,15 @@ double mul_up(double a, double b) { return std::nextafter(a * b, HUGE_VAL); }
 // an upper bound of v as a double
 double dbl_up(uint64_t v) { return v == 0 ? 0.0 : std::nextafter((double)v, HUGE_VAL); }
 
-}  // namespace
-
-extern "C" {
-
-int fls_aggregate(fls_table *t, const fls_aggregate_spec *aggs, uint32_t n, uint32_t rg_begin, uint32_t rg_end,
-                  fls_aggregate_value *out) {
-    if (!t || !aggs || !out) return fail(FLS_ERR_ARG, "fls_aggregate: NULL argument");
-    if (n == 0 || n > kMaxAggs) return fail(FLS_ERR_ARG, "fls_aggregate: %u aggregates (1 to %u per call)", n, kMaxAggs);
+// The argument checks fls_aggregate and fls_aggregate_grouped (`who`) share:
+// the aggregates into ha, or FLS_ERR_ARG before any device work.
+int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_spec *aggs, uint32_t n,
+                     uint32_t rg_begin, uint32_t rg_end, std::vector<HostAgg> &ha) {
+    if (n == 0 || n > kMaxAggs) return fail(FLS_ERR_ARG, "%s: %u aggregates (1 to %u per call)", who, n, kMaxAggs);
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
     if (rg_end > t->meta.rgs.size() || rg_begin > rg_end)
         return fail(FLS_ERR_ARG, "row-group range [%u,%u) out of bounds", rg_begin, rg_end);
-    std::vector<HostAgg> ha(n);
+    ha.assign(n, HostAgg());
     for (uint32_t i = 0; i < n; ++i) {
         const fls_aggregate_spec &a = aggs[i];
         if (a.fn > FLS_AGG_SUM_PRODUCT) return fail(FLS_ERR_ARG, "aggregate %u: unknown function %u", i, a.fn);
@@ -2939,85 +3067,297 @@ int fls_aggregate(fls_table *t, const fls_aggregate_spec *aggs, uint32_t n, uint
             return fail(FLS_ERR_ARG, "aggregate %u: SUM_PRODUCT of columns %u and %u may overflow 128 bits", i, ha[i].col,
                         ha[i].col2);
     }
+    return 0;
+}
+
+// The running value of one aggregate (of one group) on the host.
+struct AggAcc {
+    uint64_t count = 0;
+    unsigned __int128 sum = 0;
+    double fsum = -0.0;
+    uint64_t key = 0;
+    explicit AggAcc(uint8_t fn = 0) : key(fn == AGG_MIN ? ~0ull : 0ull) {}
+};
+
+bool agg_is_float(const fls_table *t, const HostAgg &h) {
+    return h.fn >= AGG_SUM && type_is_float(t->meta.cols[h.col].type);
+}
+
+// The grouped fold's addition of a vector's partial binary64 sum onto the
+// running sum.  It differs from acc + x only in which NaN comes back when both
+// are NaN: the partial's, which is what fls_aggregate's `fsum += x` returns as
+// built (x86 keeps its first operand's NaN, and that is the record); the
+// one-group test compares the two calls' NaN bits
+// (tests/test_group_aggregate.py).  fold_record keeps the plain expression.
+inline double add_partial(double acc, double x) { return x != x ? x : acc + x; }
+
+// One partial record into the running value; the records come in row order.
+void fold_record(AggAcc &a, uint8_t fn, bool flt, const AggRec &r) {
+    a.count += r.count;
+    if (r.count == 0) return;
+    switch (fn) {
+    case AGG_SUM:
+    case AGG_SUM_PRODUCT:
+        if (flt) a.fsum += as_double(r.lo);
+        else a.sum += ((unsigned __int128)r.hi << 64) | r.lo;
+        break;
+    case AGG_MIN: a.key = std::min(a.key, r.lo); break;
+    case AGG_MAX: a.key = std::max(a.key, r.lo); break;
+    default: break;
+    }
+}
+
+// The running value as the caller sees it.
+void finish_value(const fls_table *t, const HostAgg &h, const AggAcc &a, fls_aggregate_value &o) {
+    memset(&o, 0, sizeof(o));
+    o.count = a.count;
+    if (h.fn <= AGG_COUNT) {
+        o.kind = FLS_AGGV_INT;
+        o.lo = a.count;
+        return;
+    }
+    if (a.count == 0) return;  // FLS_AGGV_NULL
+    const bool flt = agg_is_float(t, h);
+    o.kind = flt ? FLS_AGGV_DOUBLE : FLS_AGGV_INT;
+    if (h.fn == AGG_SUM || h.fn == AGG_SUM_PRODUCT) {
+        if (flt) {
+            memcpy(&o.lo, &a.fsum, 8);
+        } else {
+            o.lo = (uint64_t)a.sum;
+            o.hi = (uint64_t)(a.sum >> 64);
+        }
+    } else if (flt) {
+        const double d = agg_unkey_float(a.key);
+        memcpy(&o.lo, &d, 8);
+    } else if (type_is_signed(t->meta.cols[h.col].type)) {
+        const int64_t v = agg_unkey_int(a.key);
+        o.lo = (uint64_t)v;
+        o.hi = v < 0 ? ~0ull : 0ull;
+    } else {
+        o.lo = a.key;
+    }
+}
+
+// The host batch that holds row group rg of the aggregate scan s.
+const HostBatch *held_batch(ScanCtx &s, uint32_t rg) {
+    std::lock_guard<std::mutex> lk(s.mu);
+    for (const auto &o : s.out)
+        if (o.first == rg) return o.second;
+    return nullptr;
+}
+
+}  // namespace
+
+// One group's key values and running aggregates; the strings are copies.
+struct fls_group_result {
+    struct Key {
+        uint8_t kind = FLS_KEYV_NULL;
+        uint64_t lo = 0, hi = 0;
+        std::string str;
+    };
+    uint32_t nkeys = 0, naggs = 0;
+    std::vector<Key> keys;                    // ngroups x nkeys
+    std::vector<fls_aggregate_value> values;  // ngroups x naggs
+};
+
+extern "C" {
+
+int fls_aggregate(fls_table *t, const fls_aggregate_spec *aggs, uint32_t n, uint32_t rg_begin, uint32_t rg_end,
+                  fls_aggregate_value *out) {
+    if (!t || !aggs || !out) return fail(FLS_ERR_ARG, "fls_aggregate: NULL argument");
+    std::vector<HostAgg> ha;
+    if (int rc = check_aggregates(t, "fls_aggregate", aggs, n, rg_begin, rg_end, ha)) return rc;
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
     const std::vector<uint8_t> none(std::max(1u, ncols), 0);  // nothing is delivered
     ScanCtx &s = t->scan;
     int rc = scan_setup(t, s, t->devices, none.data(), rg_begin, rg_end, &t->filter, &ha);
     if (!rc) rc = scan_start(t, s);
     if (rc) return rc;
     // fold the per-vector records in row order
-    struct Acc {
-        uint64_t count = 0;
-        unsigned __int128 sum = 0;
-        double fsum = -0.0;
-        uint64_t key = 0;
-    };
-    std::vector<Acc> acc(n);
-    for (uint32_t i = 0; i < n; ++i)
-        if (ha[i].fn == AGG_MIN) acc[i].key = ~0ull;
-    auto is_float = [&](uint32_t i) { return ha[i].fn >= AGG_SUM && type_is_float(t->meta.cols[ha[i].col].type); };
+    std::vector<AggAcc> acc;
+    for (uint32_t i = 0; i < n; ++i) acc.emplace_back(ha[i].fn);
     fls_rowgroup rg;
     while ((rc = scan_next(t, s, &rg)) == 1) {
-        const HostBatch *hb = nullptr;
-        {
-            std::lock_guard<std::mutex> lk(s.mu);
-            for (const auto &o : s.out)
-                if (o.first == rg.rowgroup) hb = o.second;
-        }
+        const HostBatch *hb = held_batch(s, rg.rowgroup);
         if (!hb) return fail(FLS_ERR_STATE, "internal: aggregate batch of row group %u not found", rg.rowgroup);
         const uint64_t v0 = (t->meta.rgs[rg.rowgroup].first_row - t->meta.rgs[hb->rg0].first_row) / kVectorSize;
         const uint64_t nv = (t->meta.rgs[rg.rowgroup].nrows + kVectorSize - 1) / kVectorSize;
         for (uint64_t v = v0; v < v0 + nv && v < hb->nvec; ++v)
-            for (uint32_t i = 0; i < n; ++i) {
-                const AggRec &r = hb->h_agg.p[v * n + i];
-                Acc &a = acc[i];
-                a.count += r.count;
-                if (r.count == 0) continue;
-                switch (ha[i].fn) {
-                case AGG_SUM:
-                case AGG_SUM_PRODUCT:
-                    if (is_float(i)) a.fsum += as_double(r.lo);
-                    else a.sum += ((unsigned __int128)r.hi << 64) | r.lo;
-                    break;
-                case AGG_MIN: a.key = std::min(a.key, r.lo); break;
-                case AGG_MAX: a.key = std::max(a.key, r.lo); break;
-                default: break;
-                }
-            }
+            for (uint32_t i = 0; i < n; ++i) fold_record(acc[i], ha[i].fn, agg_is_float(t, ha[i]), hb->h_agg.p[v * n + i]);
     }
     if (rc < 0) return rc;
-    for (uint32_t i = 0; i < n; ++i) {
-        fls_aggregate_value &o = out[i];
-        memset(&o, 0, sizeof(o));
-        const Acc &a = acc[i];
-        o.count = a.count;
-        if (ha[i].fn <= AGG_COUNT) {
-            o.kind = FLS_AGGV_INT;
-            o.lo = a.count;
-            continue;
+    for (uint32_t i = 0; i < n; ++i) finish_value(t, ha[i], acc[i], out[i]);
+    return 0;
+}
+
+int fls_aggregate_grouped(fls_table *t, const uint32_t *keys, uint32_t nkeys, const fls_aggregate_spec *aggs,
+                          uint32_t n, uint32_t rg_begin, uint32_t rg_end, fls_group_result **out) {
+    if (!t || !out || (!keys && nkeys) || !aggs) return fail(FLS_ERR_ARG, "fls_aggregate_grouped: NULL argument");
+    *out = nullptr;
+    if (nkeys == 0 || nkeys > kMaxKeys)
+        return fail(FLS_ERR_ARG, "fls_aggregate_grouped: %u keys (1 to %u per call)", nkeys, kMaxKeys);
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    if (rg_end > t->meta.rgs.size() || rg_begin > rg_end)
+        return fail(FLS_ERR_ARG, "row-group range [%u,%u) out of bounds", rg_begin, rg_end);
+    std::vector<uint32_t> hk(keys, keys + nkeys);
+    for (uint32_t q = 0; q < nkeys; ++q) {
+        const uint32_t c = hk[q];
+        if (c >= ncols) return fail(FLS_ERR_ARG, "key %u: column %u out of range", q, c);
+        for (uint32_t p = 0; p < q; ++p)
+            if (hk[p] == c) return fail(FLS_ERR_ARG, "key %u: column %u is key %u already", q, c, p);
+        const uint8_t ty = t->meta.cols[c].type;
+        if (type_is_float(ty) || ty == TY_BLOB)
+            return fail(FLS_ERR_ARG, "key %u: a FLOAT / DOUBLE / BLOB column (%u) cannot be a GROUP BY key", q, c);
+        if (ty != TY_VARCHAR) continue;
+        for (const HostTerm &h : t->filter)
+            if (h.col == c)
+                return fail(FLS_ERR_ARG,
+                            "key %u: VARCHAR column %u is read by a filter term, which needs it decoded as strings, "
+                            "not as the dictionary codes a key is made of", q, c);
+        // the row groups the scan will read (the same set the SUM_PRODUCT bound walks)
+        for (uint32_t r = rg_begin; r < rg_end; ++r) {
+            if (!t->filter.empty() && !rowgroup_may_match(t, r, t->filter)) continue;
+            const ChunkHeader &h = t->meta.rgs[r].chunks[c].hdr;
+            if (h.enc != ENC_DICT)
+                return fail(FLS_ERR_ARG, "key %u: VARCHAR column %u is not dictionary-encoded in row group %u", q, c, r);
+            if (h.dict_count > 65536)
+                return fail(FLS_ERR_ARG, "key %u: the dictionary of VARCHAR column %u has %u entries in row group %u "
+                            "(at most 65536)", q, c, h.dict_count, r);
         }
-        if (a.count == 0) continue;  // FLS_AGGV_NULL
-        const bool flt = is_float(i);
-        o.kind = flt ? FLS_AGGV_DOUBLE : FLS_AGGV_INT;
-        if (ha[i].fn == AGG_SUM || ha[i].fn == AGG_SUM_PRODUCT) {
-            if (flt) {
-                memcpy(&o.lo, &a.fsum, 8);
-            } else {
-                o.lo = (uint64_t)a.sum;
-                o.hi = (uint64_t)(a.sum >> 64);
+    }
+    const KeyLayout L = key_layout(t, hk);
+    if (L.total > 128)
+        for (uint32_t q = 0, bits = nkeys; q < nkeys; ++q)
+            if ((bits += L.bits[q]) > 128)
+                return fail(FLS_ERR_ARG, "key %u: the packed key needs %u bits (at most 128: 8 x value bytes per integer "
+                            "key, 16 per VARCHAR key, 1 per key for NULL)", q, L.total);
+    std::vector<HostAgg> ha;
+    if (int rc = check_aggregates(t, "fls_aggregate_grouped", aggs, n, rg_begin, rg_end, ha)) return rc;
+    const std::vector<uint8_t> none(std::max(1u, ncols), 0);  // nothing is delivered
+    ScanCtx &s = t->scan;
+    int rc = scan_setup(t, s, t->devices, none.data(), rg_begin, rg_end, &t->filter, &ha, &hk);
+    if (!rc) rc = scan_start(t, s);
+    if (rc) return rc;
+    auto res = std::make_unique<fls_group_result>();
+    res->nkeys = nkeys;
+    res->naggs = n;
+    // the table's groups in first-occurrence order, found by key VALUE: per key
+    // its kind, then the integer's 16 bytes or the string's length and bytes
+    std::unordered_map<std::string, uint64_t> index;
+    std::vector<AggAcc> acc;  // ngroups x n
+    std::vector<uint32_t> fslot(n, 0);  // the FLOAT / DOUBLE sums, numbered as upload_agg_descs numbers them
+    for (uint32_t i = 0, k = 0; i < n; ++i)
+        if (ha[i].fn == AGG_SUM && agg_is_float(t, ha[i])) fslot[i] = k++;
+    std::vector<fls_group_result::Key> kv(nkeys);
+    std::string ser;
+    fls_rowgroup rg;
+    while ((rc = scan_next(t, s, &rg)) == 1) {
+        const HostBatch *hb = held_batch(s, rg.rowgroup);
+        if (!hb) return fail(FLS_ERR_STATE, "internal: aggregate batch of row group %u not found", rg.rowgroup);
+        const uint32_t nfsum = hb->g_nfsum, rg_vecs = hb->g_rg_vecs;
+        const uint8_t *base = hb->h_grp.p + (size_t)(rg.rowgroup - hb->rg0) * group_rg_stride(n, nfsum, rg_vecs);
+        GroupHdr hdr;
+        memcpy(&hdr, base, sizeof(hdr));
+        if (hdr.overflow || hdr.ngroups > kMaxRgGroups)  // (the device flag fails the batch's acquire first)
+            return fail(FLS_ERR_LIMIT, "grouped aggregate: row group %u exceeds the group capacity; fall back to a scan",
+                        rg.rowgroup);
+        const uint64_t *gkeys = (const uint64_t *)(base + sizeof(GroupHdr));
+        const AggRec *recs = (const AggRec *)(base + group_rg_recs_off());
+        const double *fvec = (const double *)(base + group_rg_fvec_off(n));
+        const uint32_t nv = (t->meta.rgs[rg.rowgroup].nrows + kVectorSize - 1) / kVectorSize;
+        for (uint32_t g = 0; g < hdr.ngroups; ++g) {
+            const unsigned __int128 pk = ((unsigned __int128)gkeys[2 * g + 1] << 64) | gkeys[2 * g];
+            ser.clear();
+            for (uint32_t q = 0; q < nkeys; ++q) {
+                fls_group_result::Key &k = kv[q];
+                k = fls_group_result::Key();
+                const uint8_t ty = t->meta.cols[hk[q]].type;
+                if (!((pk >> L.null_bit[q]) & 1)) {
+                    const uint64_t raw = (uint64_t)(pk >> L.shift[q]) & (L.bits[q] >= 64 ? ~0ull : (1ull << L.bits[q]) - 1);
+                    if (ty == TY_VARCHAR) {
+                        // the code through this row group's dictionary in the file image
+                        const ChunkRef &ch = t->meta.rgs[rg.rowgroup].chunks[hk[q]];
+                        if (raw >= ch.hdr.dict_count)
+                            return fail(FLS_ERR_FORMAT, "corrupt chunk: dictionary code %llu of %u in key column %u",
+                                        (unsigned long long)raw, ch.hdr.dict_count, hk[q]);
+                        const uint8_t *p;
+                        uint32_t len;
+                        dict_string(t->img + ch.off + ch.hdr.aux_off, ch.hdr.dict_count, (uint32_t)raw, p, len);
+                        k.kind = FLS_KEYV_STRING;
+                        k.str.assign((const char *)p, len);
+                    } else {
+                        k.kind = FLS_KEYV_INT;
+                        k.lo = raw;
+                        if (type_is_signed(ty) && L.bits[q] < 64 && ((raw >> (L.bits[q] - 1)) & 1)) k.lo |= ~0ull << L.bits[q];
+                        k.hi = type_is_signed(ty) && (int64_t)k.lo < 0 ? ~0ull : 0ull;
+                    }
+                }
+                ser.push_back((char)k.kind);
+                if (k.kind == FLS_KEYV_INT) {
+                    ser.append((const char *)&k.lo, 8);
+                } else if (k.kind == FLS_KEYV_STRING) {
+                    const uint64_t len = k.str.size();
+                    ser.append((const char *)&len, 8);
+                    ser.append(k.str);
+                }
             }
-        } else if (flt) {
-            const double d = agg_unkey_float(a.key);
-            memcpy(&o.lo, &d, 8);
-        } else if (type_is_signed(t->meta.cols[ha[i].col].type)) {
-            const int64_t v = agg_unkey_int(a.key);
-            o.lo = (uint64_t)v;
-            o.hi = v < 0 ? ~0ull : 0ull;
-        } else {
-            o.lo = a.key;
+            auto it = index.find(ser);
+            uint64_t gi;
+            if (it == index.end()) {
+                gi = index.size();
+                index.emplace(ser, gi);
+                for (uint32_t q = 0; q < nkeys; ++q) res->keys.push_back(kv[q]);
+                for (uint32_t i = 0; i < n; ++i) acc.emplace_back(ha[i].fn);
+            } else {
+                gi = it->second;
+            }
+            for (uint32_t i = 0; i < n; ++i) {
+                const AggRec &r = recs[(size_t)g * n + i];
+                AggAcc &a = acc[gi * n + i];
+                if (ha[i].fn == AGG_SUM && agg_is_float(t, ha[i])) {
+                    // the vectors' sums one after the other, as the ungrouped fold adds them
+                    // (-0.0, which changes nothing, where the group has no row)
+                    a.count += r.count;
+                    const double *fv = fvec + ((size_t)g * nfsum + fslot[i]) * rg_vecs;
+                    for (uint32_t v = 0; v < nv && v < rg_vecs; ++v) a.fsum = add_partial(a.fsum, fv[v]);
+                } else {
+                    fold_record(a, ha[i].fn, false, r);
+                }
+            }
         }
+    }
+    if (rc < 0) return rc;
+    const uint64_t ngroups = index.size();
+    res->values.resize(ngroups * n);
+    for (uint64_t g = 0; g < ngroups; ++g)
+        for (uint32_t i = 0; i < n; ++i) finish_value(t, ha[i], acc[g * n + i], res->values[g * n + i]);
+    *out = res.release();
+    return 0;
+}
+
+uint64_t fls_group_result_ngroups(const fls_group_result *r) { return r && r->nkeys ? r->keys.size() / r->nkeys : 0; }
+
+int fls_group_result_key(const fls_group_result *r, uint64_t group, uint32_t key, fls_group_key *out) {
+    if (!r || !out || key >= r->nkeys || group >= fls_group_result_ngroups(r))
+        return fail(FLS_ERR_ARG, "fls_group_result_key: key %u of group %llu out of range", key, (unsigned long long)group);
+    const fls_group_result::Key &k = r->keys[group * r->nkeys + key];
+    memset(out, 0, sizeof(*out));
+    out->kind = k.kind;
+    out->lo = k.lo;
+    out->hi = k.hi;
+    if (k.kind == FLS_KEYV_STRING) {
+        out->str = k.str.data();
+        out->str_len = k.str.size();
     }
     return 0;
 }
+
+const fls_aggregate_value *fls_group_result_values(const fls_group_result *r, uint64_t group) {
+    if (!r || group >= fls_group_result_ngroups(r)) return nullptr;
+    return r->values.data() + group * r->naggs;
+}
+
+void fls_group_result_free(fls_group_result *r) { delete r; }
 
 int fls_scan_pruned(const fls_table *t) {
     if (!t) return fail(FLS_ERR_ARG, "fls_scan_pruned: NULL table");

@@ -13,6 +13,15 @@
 //               represents exactly, DATE 'YYYY-MM-DD', floats, single-quoted
 //               strings ('' escapes a quote).  No OR, no parentheses.
 //
+// `fastlanes_aggregate(path, aggregates, filter, group_by)` returns one row per
+// group of a low-cardinality GROUP BY (fls_aggregate_grouped): group_by is a
+// comma-separated list of 1 to 4 column names (integer-like, or dictionary-
+// encoded VARCHAR), an empty or blank filter means none.  The key columns come
+// first, named and typed as the table's, then the aggregates; rows are in
+// order of each group's first row, in chunks of STANDARD_VECTOR_SIZE.  Past
+// the engine's capacities (64 keys per 1024-row vector, 256 per row group) the
+// query fails and the message points at read_fastlanes with a GROUP BY.
+//
 // Output types: counts and integer sums BIGINT, sums of DECIMAL(w, s)
 // DECIMAL(18, s), sum(a * b) DECIMAL(18, s1 + s2) when an operand is DECIMAL,
 // float sums DOUBLE, min / max the column's own type.  The engine's sums are
@@ -58,11 +67,17 @@ struct AggBindData : public TableFunctionData {
     std::vector<fls_predicate> preds;
     std::deque<string> pred_strs;        // VARCHAR constants the predicates point at
     std::shared_ptr<AggTable> table;     // opened at bind (footer only)
+    std::vector<uint32_t> keys;          // the group_by columns (empty: ungrouped, one row)
 };
 
 struct AggGlobalState : public GlobalTableFunctionState {
     std::mutex lock;
     bool done = false;
+    fls_group_result *groups = nullptr;  // grouped: the result, emitted in chunks from `next`
+    uint64_t next = 0;
+    ~AggGlobalState() override {
+        if (groups) fls_group_result_free(groups);
+    }
 };
 
 string Trim(const string &s) {
@@ -388,10 +403,38 @@ void ParseFilter(const Schema &sch, const string &filter, std::vector<fls_predic
     }
 }
 
+// the group_by text: 1 to 4 column names separated by commas
+void ParseGroupBy(const Schema &sch, const string &list, std::vector<uint32_t> &keys, vector<string> &names,
+                  vector<LogicalType> &types) {
+    size_t start = 0;
+    for (size_t i = 0; i <= list.size(); ++i) {
+        if (i < list.size() && list[i] != ',') continue;
+        const string item = Trim(list.substr(start, i - start));
+        start = i + 1;
+        if (item.empty()) throw BinderException("fastlanes_aggregate: empty item in group_by list \"" + list + "\"");
+        const int c = sch.Find(item);
+        if (c < 0)
+            throw BinderException("fastlanes_aggregate: column \"" + item + "\" of group_by \"" + list + "\" not found");
+        const uint8_t ty = sch.cols[c].type;
+        if (IsFloat(ty) || ty == FLS_BLOB)
+            throw BinderException("fastlanes_aggregate: group_by key \"" + item + "\" is " + sch.types[c].ToString() +
+                                  ": FLOAT, DOUBLE and BLOB columns cannot be keys, in \"" + list + "\"");
+        for (uint32_t k : keys)
+            if (k == (uint32_t)c)
+                throw BinderException("fastlanes_aggregate: group_by key \"" + item + "\" is listed twice in \"" + list + "\"");
+        keys.push_back((uint32_t)c);
+        names.push_back(sch.names[c]);
+        types.push_back(sch.types[c]);
+    }
+    if (keys.size() > 4)
+        throw BinderException("fastlanes_aggregate: at most 4 group_by keys, \"" + list + "\" holds " +
+                              std::to_string(keys.size()));
+}
+
 unique_ptr<FunctionData> AggBind(ClientContext &, TableFunctionBindInput &input, vector<LogicalType> &return_types,
                                  vector<string> &names) {
-    if (input.inputs.size() < 2 || input.inputs.size() > 3)
-        throw BinderException("fastlanes_aggregate takes (path, aggregates[, filter])");
+    if (input.inputs.size() < 2 || input.inputs.size() > 4)
+        throw BinderException("fastlanes_aggregate takes (path, aggregates[, filter[, group_by]])");
     for (auto &v : input.inputs)
         if (v.IsNull() || v.type() != LogicalType::VARCHAR)
             throw BinderException("fastlanes_aggregate arguments must be strings");
@@ -435,8 +478,16 @@ unique_ptr<FunctionData> AggBind(ClientContext &, TableFunctionBindInput &input,
     if (bind->specs.size() > 32)
         throw BinderException("fastlanes_aggregate: at most 32 aggregates per call, \"" + list + "\" holds " +
                               std::to_string(bind->specs.size()));
-    if (input.inputs.size() == 3) ParseFilter(sch, input.inputs[2].GetValue<string>(), bind->preds, bind->pred_strs);
+    if (input.inputs.size() >= 3) ParseFilter(sch, input.inputs[2].GetValue<string>(), bind->preds, bind->pred_strs);
     return_types = bind->types;
+    if (input.inputs.size() == 4) {
+        // the key columns come first, named and typed as the table's columns
+        vector<string> key_names;
+        vector<LogicalType> key_types;
+        ParseGroupBy(sch, input.inputs[3].GetValue<string>(), bind->keys, key_names, key_types);
+        names.insert(names.begin(), key_names.begin(), key_names.end());
+        return_types.insert(return_types.begin(), key_types.begin(), key_types.end());
+    }
     return std::move(bind);
 }
 
@@ -455,10 +506,68 @@ int64_t Narrow(const fls_aggregate_value &v, const string &name, const LogicalTy
     return x;
 }
 
+// one aggregate value into row `row` of its output column
+void EmitValue(const AggBindData &bind, idx_t j, const fls_aggregate_value &v, Vector &vec, idx_t row) {
+    if (v.kind == FLS_AGGV_NULL) {
+        vec.SetValue(row, Value());
+    } else if (v.kind == FLS_AGGV_DOUBLE) {
+        double d;
+        memcpy(&d, &v.lo, 8);
+        vec.SetValue(row, Value::DOUBLE(d));
+    } else if (bind.specs[j].fn == FLS_AGG_MIN || bind.specs[j].fn == FLS_AGG_MAX) {
+        vec.SetValue(row, Value::BIGINT((int64_t)v.lo));  // the column's own type: its low bytes
+    } else {
+        vec.SetValue(row, Value::BIGINT(Narrow(v, bind.names[j], bind.types[j])));
+    }
+}
+
+// The grouped form: the first call runs fls_aggregate_grouped, every call
+// emits the next STANDARD_VECTOR_SIZE groups at most, in the C call's order.
+void AggScanGrouped(const AggBindData &bind, AggGlobalState &g, DataChunk &output) {
+    std::lock_guard<std::mutex> guard(g.lock);
+    fls_table *t = bind.table->table;
+    if (!g.done) {
+        g.done = true;
+        if (fls_scan_filter(t, bind.preds.data(), (uint32_t)bind.preds.size()) != 0)
+            throw IOException(string("FastLanes aggregate failed: ") + fls_last_error());
+        const int rc = fls_aggregate_grouped(t, bind.keys.data(), (uint32_t)bind.keys.size(), bind.specs.data(),
+                                             (uint32_t)bind.specs.size(), 0, fls_table_nrowgroups(t), &g.groups);
+        const string err = rc ? fls_last_error() : "";
+        fls_scan_filter(t, nullptr, 0);
+        if (rc == FLS_ERR_LIMIT)
+            throw InvalidInputException("fastlanes_aggregate: " + err +
+                                        "; use SELECT ... FROM read_fastlanes(...) GROUP BY ... instead");
+        if (rc == FLS_ERR_ARG) throw InvalidInputException("fastlanes_aggregate: " + err);  // a key's chunks, the SUM_PRODUCT bound
+        if (rc) throw IOException("FastLanes aggregate failed: " + err);
+    }
+    const uint64_t total = fls_group_result_ngroups(g.groups);
+    const idx_t nk = bind.keys.size();
+    idx_t n = 0;
+    for (; n < STANDARD_VECTOR_SIZE && g.next < total; ++n, ++g.next) {
+        for (idx_t q = 0; q < nk; ++q) {
+            fls_group_key k;
+            if (fls_group_result_key(g.groups, g.next, (uint32_t)q, &k) != 0)
+                throw IOException(string("FastLanes aggregate failed: ") + fls_last_error());
+            Vector &vec = output.data[q];
+            if (k.kind == FLS_KEYV_NULL) vec.SetValue(n, Value());
+            else if (k.kind == FLS_KEYV_STRING) vec.SetValue(n, Value(string(k.str ? k.str : "", (size_t)k.str_len)));
+            else vec.SetValue(n, Value::BIGINT((int64_t)k.lo));  // the column's own type: its low bytes
+        }
+        const fls_aggregate_value *vals = fls_group_result_values(g.groups, g.next);
+        for (idx_t j = 0; j < bind.specs.size() && nk + j < output.ColumnCount(); ++j)
+            EmitValue(bind, j, vals[j], output.data[nk + j], n);
+    }
+    output.SetCardinality(n);
+}
+
 void AggScan(ClientContext &, TableFunctionInput &data, DataChunk &output) {
     const auto &bind = data.bind_data->Cast<AggBindData>();
     auto &g = data.global_state->Cast<AggGlobalState>();
     output.Reset();
+    if (!bind.keys.empty()) {
+        AggScanGrouped(bind, g, output);
+        return;
+    }
     {
         std::lock_guard<std::mutex> guard(g.lock);
         if (g.done) {
@@ -476,21 +585,7 @@ void AggScan(ClientContext &, TableFunctionInput &data, DataChunk &output) {
     fls_scan_filter(t, nullptr, 0);
     if (rc == FLS_ERR_ARG) throw OutOfRangeException("fastlanes_aggregate: " + err);  // the SUM_PRODUCT bound
     if (rc) throw IOException("FastLanes aggregate failed: " + err);
-    for (idx_t j = 0; j < output.ColumnCount() && j < vals.size(); ++j) {
-        const fls_aggregate_value &v = vals[j];
-        Vector &vec = output.data[j];
-        if (v.kind == FLS_AGGV_NULL) {
-            vec.SetValue(0, Value());
-        } else if (v.kind == FLS_AGGV_DOUBLE) {
-            double d;
-            memcpy(&d, &v.lo, 8);
-            vec.SetValue(0, Value::DOUBLE(d));
-        } else if (bind.specs[j].fn == FLS_AGG_MIN || bind.specs[j].fn == FLS_AGG_MAX) {
-            vec.SetValue(0, Value::BIGINT((int64_t)v.lo));  // the column's own type: its low bytes
-        } else {
-            vec.SetValue(0, Value::BIGINT(Narrow(v, bind.names[j], bind.types[j])));
-        }
-    }
+    for (idx_t j = 0; j < output.ColumnCount() && j < vals.size(); ++j) EmitValue(bind, j, vals[j], output.data[j], 0);
     output.SetCardinality(1);
 }
 
@@ -500,6 +595,8 @@ void RegisterFastlanesAggregate(DatabaseInstance &db) {
     TableFunction fn("fastlanes_aggregate", {LogicalType::VARCHAR, LogicalType::VARCHAR}, AggScan, AggBind, AggInitGlobal);
     ExtensionUtil::RegisterFunction(db, fn);
     fn.arguments = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR};
+    ExtensionUtil::RegisterFunction(db, fn);
+    fn.arguments = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR};
     ExtensionUtil::RegisterFunction(db, fn);
 }
 

@@ -50,7 +50,8 @@ typedef enum fls_status {
     FLS_ERR_DEVICE = -4,    /* HIP runtime error or no usable GPU */
     FLS_ERR_STATE = -5,     /* call out of order (e.g. decode before upload) */
     FLS_ERR_NOMEM = -6,
-    FLS_ERR_CONFIG = -7     /* an FLS_* tuning variable names a kernel this build does not hold */
+    FLS_ERR_CONFIG = -7,    /* an FLS_* tuning variable names a kernel this build does not hold */
+    FLS_ERR_LIMIT = -8      /* a documented capacity was exceeded (fls_aggregate_grouped) */
 } fls_status;
 
 typedef struct fls_connection fls_connection;
@@ -246,6 +247,52 @@ typedef struct fls_aggregate_value {
 } fls_aggregate_value;
 int fls_aggregate(fls_table *t, const fls_aggregate_spec *aggs, uint32_t n,
                   uint32_t rg_begin, uint32_t rg_end, fls_aggregate_value *out);
+/* GROUP BY keys[0..nkeys) of the same aggregates, for low-cardinality keys:
+ * fls_aggregate's functions, filter, pruning, argument checks and numeric
+ * results, per group.  The batch is reduced in HBM per (1024-row vector, key)
+ * and merged per row group (csrc/fls_groupagg.hip); one table of at most 256
+ * groups per row group crosses PCIe, and the call merges the row groups'
+ * tables by key value.  A row belongs to a group when the filter selects it;
+ * a key no selected row carries makes no group.  Within a group a row counts
+ * for an aggregate exactly as in fls_aggregate.  Key columns (1 to 4): INT*,
+ * UINT*, BOOLEAN, DATE, DECIMAL of at most 64 bits in any encoding (the key is
+ * the decoded value), or a VARCHAR column whose chunk is DICT with at most
+ * 65536 entries in every row group the scan reads (the key is the string; the
+ * dictionaries may differ per row group).  A NULL key is a group of its own.
+ * The packed key -- 8 x value bytes per integer key, 16 bits per VARCHAR key,
+ * one NULL bit per key -- holds at most 128 bits.  Groups come in order of
+ * first occurrence in table row order.  Every value, binary64 sums included,
+ * is bit-identical whatever the batch size, slot count or number of GPUs, and
+ * with a single group equals fls_aggregate's.  No row group to read (an empty
+ * range, everything pruned): zero groups, no device work.
+ * FLS_ERR_ARG before any device work, naming the key's index ("key 1: ..."):
+ * nkeys == 0 or > 4, a key column out of range or listed twice, a FLOAT /
+ * DOUBLE / BLOB key, a VARCHAR key with a non-DICT chunk (or a dictionary of
+ * more than 65536 entries) in range, a VARCHAR key a filter term reads, a
+ * packed key of more than 128 bits; and everything fls_aggregate refuses.
+ * FLS_ERR_LIMIT: more than 64 distinct keys among one vector's selected rows,
+ * or more than 256 in one row group (the kernels check before they write; fall
+ * back to a scan).  The table stays usable.  The number of groups over the
+ * table is not limited.
+ * *out is owned by the caller (fls_group_result_free), strings included. */
+typedef struct fls_group_result fls_group_result;
+typedef enum fls_key_kind { FLS_KEYV_NULL = 0, FLS_KEYV_INT = 1, FLS_KEYV_STRING = 2 } fls_key_kind;
+typedef struct fls_group_key {
+    uint8_t kind;       /* fls_key_kind */
+    uint8_t pad[7];
+    uint64_t lo, hi;    /* INT: the value, sign- or zero-extended to 128 bits by column type */
+    const char *str;    /* STRING: str_len bytes (not NUL-terminated), owned by the result */
+    uint64_t str_len;
+} fls_group_key;
+int fls_aggregate_grouped(fls_table *t, const uint32_t *keys, uint32_t nkeys,
+                          const fls_aggregate_spec *aggs, uint32_t n,
+                          uint32_t rg_begin, uint32_t rg_end, fls_group_result **out);
+uint64_t fls_group_result_ngroups(const fls_group_result *r);
+/* key `key` (0 .. nkeys-1) of group `group`; FLS_ERR_ARG out of range */
+int fls_group_result_key(const fls_group_result *r, uint64_t group, uint32_t key, fls_group_key *out);
+/* the group's n values in the aggregates' order; NULL out of range */
+const fls_aggregate_value *fls_group_result_values(const fls_group_result *r, uint64_t group);
+void fls_group_result_free(fls_group_result *r);
 /* Zone map of column col in row group rg: 1 and *min / *max (int64, uint64
  * or double bits by column type, see fls_predicate.value; FLOAT widened to
  * double) and *flags (1 valid, 2 / 4 has / all NaN, 8 / 16 has / all NULL;

@@ -12,9 +12,14 @@ clock around the synchronous call):
   unfiltered  A: Table.aggregate([sum(l_quantity), min(l_shipdate), max(l_shipdate), count(*)])
               B: scan(cols=[l_quantity, l_shipdate]) + numpy
 
+  Q1          A: Table.aggregate_grouped by l_returnflag, l_linestatus of the Q1 aggregates under the shipdate term
+              B: scan_filtered of the same five columns + a numpy group-by (the only way without the grouped call)
+              C: Table.aggregate of the same aggregates and filter, ungrouped: the floor the grouping is paid on top of
+
 The arms' answers are compared before anything is printed.
 
-    python scripts/agg_rate.py --scale 10 --reps 5 > profiles/agg/agg_rate_sf10.txt
+    python scripts/agg_rate.py --scale 10 --reps 5 > all.txt        (--query picks one of them)
+    python scripts/agg_rate.py --scale 10 --reps 5 --query q1 > profiles/agg/group_rate_sf10.txt
 """
 import argparse
 import os
@@ -63,6 +68,91 @@ def plain_scan(t):
     return [total, lo, hi, rows]
 
 
+# ---- TPC-H Q1: the grouped call (profiles/agg/group_rate_sf10.txt)
+C_RFLAG, C_STATUS = 8, 9
+Q1_DAY = 10471                      # 1998-09-02 as DATE days
+Q1 = [(C_SHIPDATE, "<=", Q1_DAY)]
+Q1_KEYS = [C_RFLAG, C_STATUS]
+Q1_AGGS = [("sum", C_QTY), ("sum", C_PRICE), ("sum_product", C_PRICE, C_DISC), ("sum", C_DISC), ("count",)]
+
+
+def q1_grouped(t):
+    return [(list(k), v) for k, v in t.aggregate_grouped(Q1_KEYS, Q1_AGGS, filt=Q1)]
+
+
+def q1_ungrouped(t):
+    return t.aggregate(Q1_AGGS, filt=Q1)
+
+
+def _short_strings(rec):
+    """string_t records of strings of at most 8 bytes -> (lengths, their bytes as one uint64 each)"""
+    rec = rec.reshape(-1, 16)
+    lens = rec[:, :4].copy().view(np.uint32).reshape(-1)
+    assert len(lens) == 0 or int(lens.max()) <= 8
+    return lens, rec[:, 4:12].copy().view(np.uint64).reshape(-1)
+
+
+def q1_scan(t):
+    """the qualifying rows of the five columns over the link, grouped with numpy;
+    groups in order of their first row, as the grouped call returns them"""
+    groups = {}
+    for _, _, sel, arrays in t.scan_filtered(Q1, cols=[C_QTY, C_PRICE, C_DISC, C_RFLAG, C_STATUS]):
+        if len(sel) == 0:
+            continue
+        qty, price, disc = (arrays[c].view(np.int64) for c in (C_QTY, C_PRICE, C_DISC))
+        (la, ka), (lb, kb) = _short_strings(arrays[C_RFLAG]), _short_strings(arrays[C_STATUS])
+        if int(la.max()) <= 4 and int(lb.max()) <= 4:   # both keys in one word: one sort
+            combo, first, inv = np.unique(ka | (kb << np.uint64(32)), return_index=True, return_inverse=True)
+        else:
+            ua, ia = np.unique(ka, return_inverse=True)
+            ub, ib = np.unique(kb, return_inverse=True)
+            combo, first, inv = np.unique(ia * len(ub) + ib, return_index=True, return_inverse=True)
+        prod = price * disc                  # < 2^63 per row group: 65,536 x 1.1e7 x 10
+        for g in np.argsort(first):
+            m = inv == g
+            r = int(first[g])
+            key = (bytes(ka[r:r + 1].view(np.uint8)[:la[r]]), bytes(kb[r:r + 1].view(np.uint8)[:lb[r]]))
+            acc = groups.setdefault(key, [0, 0, 0, 0, 0])
+            for i, x in enumerate((qty, price, prod, disc)):
+                acc[i] += int(x[m].sum())
+            acc[4] += int(m.sum())
+    return [(list(k), v) for k, v in groups.items()]
+
+
+def q1_arm(fl, t, nrows, reps):
+    arms = (("A Table.aggregate_grouped      ", q1_grouped), ("B scan_filtered + numpy group", q1_scan),
+            ("C Table.aggregate (ungrouped)  ", q1_ungrouped))
+    want = [fn(t) for _, fn in arms]         # warm-up: the image becomes resident, buffers are allocated
+    if want[0] != want[1]:
+        raise SystemExit(f"Q1: the arms disagree: grouped {want[0]}, scan {want[1]}")
+    if [sum(v[i] for _, v in want[0]) for i in range(len(Q1_AGGS))] != want[2]:
+        raise SystemExit(f"Q1: the groups do not add up to the ungrouped call: {want[0]}, {want[2]}")
+    times = [[] for _ in arms]
+    for _ in range(max(1, reps)):
+        for k, (_, fn) in enumerate(arms):
+            s, out = timed(fn, t)
+            assert out == want[k], (k, out, want[k])
+            times[k].append(s)
+    med = [statistics.median(x) for x in times]
+    bytes_res, _ = fl.Connection.resident_info(0)
+    print("Q1: group by l_returnflag, l_linestatus of sum(l_quantity), sum(l_extendedprice), "
+          "sum(l_extendedprice * l_discount), sum(l_discount), count(*) where l_shipdate <= 1998-09-02")
+    for k, v in want[0]:
+        print(f"Q1: group {[x.decode() for x in k]}: {v}")
+    for (name, _), m, x in zip(arms, med, times):
+        print(f"Q1: {name} median {1e3 * m:9.3f} ms  ({nrows / m:.3e} rows/s)  all {' '.join(f'{1e3 * y:.3f}' for y in x)}")
+    print(f"Q1: B / A = {med[1] / med[0]:.2f}   A / C = {med[0] / med[2]:.2f}  (resident image {bytes_res / 1e9:.3f} GB)")
+    # where B's time goes: its scan alone, the rows delivered and dropped
+    alone = []
+    for _ in range(max(1, reps)):
+        t0 = time.perf_counter()
+        rows = sum(len(sel) for _, _, sel, _ in t.scan_filtered(Q1, cols=[C_QTY, C_PRICE, C_DISC, C_RFLAG, C_STATUS]))
+        alone.append(time.perf_counter() - t0)
+    m = statistics.median(alone)
+    print(f"Q1: (B's scan_filtered alone, {rows} rows delivered, no grouping: median {1e3 * m:9.3f} ms; "
+          f"the rest of B is numpy)")
+
+
 def timed(fn, t):
     t0 = time.perf_counter()
     out = fn(t)
@@ -74,6 +164,7 @@ def main():
     ap.add_argument("--scale", type=float, default=10)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--threads", type=int, default=16, help="generator threads")
+    ap.add_argument("--query", choices=["all", "q1", "q6", "unfiltered"], default="all")
     a = ap.parse_args()
     fl = pkgload.load()
     fd, path = tempfile.mkstemp(suffix=".fls", dir=os.environ.get("TMPDIR", "/tmp"))
@@ -85,7 +176,11 @@ def main():
         nrows = t.nrows
         print(f"# lineitem SF{a.scale:g}: {nrows} rows, {t.nrowgroups} row groups, {os.path.getsize(path) / 1e9:.3f} GB file, "
               f"1 GPU, {a.reps} repetitions per arm after one warm-up each, arms alternating")
+        if a.query in ("all", "q1"):
+            q1_arm(fl, t, nrows, a.reps)
         for name, agg, scan in (("Q6", q6_aggregate, q6_scan), ("unfiltered", plain_aggregate, plain_scan)):
+            if a.query not in ("all", name.lower()):
+                continue
             ra, rb = agg(t), scan(t)          # warm-up: the image becomes resident, buffers are allocated
             if ra != rb:
                 raise SystemExit(f"{name}: the arms disagree: aggregate {ra}, scan {rb}")
