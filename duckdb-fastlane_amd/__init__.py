@@ -74,13 +74,21 @@ OPS = {"=": EQ, "==": EQ, "!=": NE, "<>": NE, "<": LT, "<=": LE, ">": GT, ">=": 
 
 
 # fls_agg_fn / fls_aggregate_spec / fls_aggregate_value (include/flsgpu.h)
-AGG_FNS = {"count_star": 0, "count": 1, "sum": 2, "min": 3, "max": 4, "sum_product": 5}
+AGG_FNS = {"count_star": 0, "count": 1, "sum": 2, "min": 3, "max": 4, "sum_product": 5, "sum_expr": 6}
 AGGV_NULL, AGGV_INT, AGGV_DOUBLE = 0, 1, 2
 
 
 class AggregateSpec(C.Structure):
     _fields_ = [("fn", C.c_uint8), ("pad", C.c_uint8 * 3), ("col", C.c_uint32), ("col2", C.c_uint32),
                 ("pad2", C.c_uint32)]
+
+
+class AggFactor(C.Structure):   # fls_agg_factor: k + sign * column
+    _fields_ = [("col", C.c_uint32), ("sign", C.c_int8), ("pad", C.c_uint8 * 3), ("k", C.c_int64)]
+
+
+class AggExpr(C.Structure):     # fls_agg_expr: the product of 1 to 3 factors
+    _fields_ = [("nfactors", C.c_uint32), ("pad", C.c_uint32), ("f", AggFactor * 3)]
 
 
 class AggregateValue(C.Structure):
@@ -151,6 +159,7 @@ _sig("fls_scan_filter", C.c_int, _P, C.POINTER(Predicate), C.c_uint32)
 _sig("fls_scan_pruned", C.c_int, _P)
 _sig("fls_aggregate", C.c_int, _P, C.POINTER(AggregateSpec), C.c_uint32, C.c_uint32, C.c_uint32,
      C.POINTER(AggregateValue))
+_sig("fls_aggregate_exprs", C.c_int, _P, C.POINTER(AggExpr), C.c_uint32)
 _sig("fls_aggregate_grouped", C.c_int, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(AggregateSpec), C.c_uint32,
      C.c_uint32, C.c_uint32, C.POINTER(_P))
 _sig("fls_group_result_ngroups", C.c_uint64, _P)
@@ -528,18 +537,36 @@ def _mask(t: "Table", cols) -> C.Array | None:
     return m
 
 
-def _agg_specs(aggs) -> C.Array:
-    """fls_aggregate_spec[] of aggregate()'s tuples; a first element that is an
-    int is passed through as the function code"""
+def _agg_exprs(exprs) -> C.Array:
+    """fls_agg_expr[] of lists of (k, sign, col) factors, passed as given (the
+    C call checks them)"""
+    arr = (AggExpr * max(1, len(exprs)))()
+    for i, factors in enumerate(exprs):
+        arr[i].nfactors = len(factors)
+        for j, (k, sign, col) in enumerate(factors[:3]):
+            arr[i].f[j].k, arr[i].f[j].sign, arr[i].f[j].col = k, sign, col
+    return arr
+
+
+def _agg_specs(aggs):
+    """fls_aggregate_spec[] of aggregate()'s tuples, and the factor lists of
+    its ("sum_expr", [...]) items in the order their specs index them; a first
+    element that is an int is passed through as the function code"""
     arr = (AggregateSpec * max(1, len(aggs)))()
+    exprs = []
     for i, a in enumerate(aggs[:len(arr)]):
         fn = a[0]
+        if fn == "sum_expr":
+            arr[i].fn = AGG_FNS[fn]
+            arr[i].col = len(exprs)
+            exprs.append(list(a[1]))
+            continue
         if isinstance(fn, str):
             fn = AGG_FNS["count_star" if fn == "count" and len(a) == 1 else fn]
         arr[i].fn = fn
         arr[i].col = a[1] if len(a) > 1 else 0
         arr[i].col2 = a[2] if len(a) > 2 else 0
-    return arr
+    return arr, exprs
 
 
 def _agg_value(v: AggregateValue):
@@ -779,22 +806,39 @@ class Table:
             _check(_lib.fls_scan_filter(self.h, None, 0))
 
     # -- aggregates reduced on the GPU
+    def set_aggregate_exprs(self, exprs):
+        """fls_aggregate_exprs: the expression list function code 6 (sum_expr)
+        indexes in the following aggregate calls; each expression a list of 1
+        to 3 (k, sign, col) factors k + sign * column.  [] or None clears."""
+        exprs = exprs or []
+        _check(_lib.fls_aggregate_exprs(self.h, _agg_exprs(exprs) if exprs else None, len(exprs)))
+
     def aggregate_raw(self, aggs, rg_begin=0, rg_end=None) -> list[AggregateValue]:
         """fls_aggregate under the filter currently set (set_filter): the raw
         fls_aggregate_value records.  aggs as for aggregate(); a first element
-        that is an int is passed through as the function code."""
+        that is an int is passed through as the function code (code 6 then
+        indexes the list set by set_aggregate_exprs).  ("sum_expr", [...])
+        items replace that list for the call and clear it afterwards."""
         if rg_end is None:
             rg_end = self.nrowgroups
-        arr = _agg_specs(aggs)
+        arr, exprs = _agg_specs(aggs)
         out = (AggregateValue * max(1, len(aggs)))()
-        _check(_lib.fls_aggregate(self.h, arr, len(aggs), rg_begin, rg_end, out))
+        if exprs:
+            self.set_aggregate_exprs(exprs)
+        try:
+            _check(_lib.fls_aggregate(self.h, arr, len(aggs), rg_begin, rg_end, out))
+        finally:
+            if exprs:
+                self.set_aggregate_exprs(None)
         return list(out)[:len(aggs)]
 
     def aggregate(self, aggs, filt=None, rg_begin=0, rg_end=None) -> list:
         """Ungrouped aggregates evaluated on the GPU (fls_aggregate).  aggs: a
         list of ("count",) [count(*)], ("count", col), ("sum", col),
-        ("min", col), ("max", col), ("sum_product", a, b); filt as
-        scan_filtered takes it.  Returns per aggregate an int (counts, integer
+        ("min", col), ("max", col), ("sum_product", a, b),
+        ("sum_expr", [(k, sign, col), ...]) [the exact integer sum of the
+        product of 1 to 3 factors k + sign * col, sign +1 or -1, k in the
+        column's physical unit]; filt as scan_filtered takes it.  Returns per aggregate an int (counts, integer
         sums at full 128-bit precision, integer MIN / MAX), a float (FLOAT /
         DOUBLE sums, MIN, MAX) or None (SUM / MIN / MAX over no row)."""
         self.set_filter(filt)
@@ -815,14 +859,18 @@ class Table:
         if rg_end is None:
             rg_end = self.nrowgroups
         karr = (C.c_uint32 * max(1, len(keys)))(*keys[:max(1, len(keys))])
-        arr = _agg_specs(aggs)
+        arr, exprs = _agg_specs(aggs)
         res = _P()
         self.set_filter(filt)
         try:
+            if exprs:
+                self.set_aggregate_exprs(exprs)
             _check(_lib.fls_aggregate_grouped(self.h, karr, len(keys), arr, len(aggs), rg_begin, rg_end,
                                               C.byref(res)))
         finally:
             _check(_lib.fls_scan_filter(self.h, None, 0))
+            if exprs:
+                self.set_aggregate_exprs(None)
         try:
             out = []
             k = GroupKey()

@@ -18,34 +18,6 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t x, int d) {
     return (uint64_t)__shfl_xor((unsigned long long)x, d, 64);
 }
 
-// the operand at p as a 128-bit two's-complement integer (lo, hi)
-__device__ __forceinline__ void load_wide(const uint8_t *p, uint32_t ob, bool sign, uint64_t &lo, uint64_t &hi) {
-    if (sign) {
-        int64_t v;
-        switch (ob) {
-        case 1: v = *(const int8_t *)p; break;
-        case 2: v = *(const int16_t *)p; break;
-        case 4: v = *(const int32_t *)p; break;
-        default: v = *(const int64_t *)p; break;
-        }
-        lo = (uint64_t)v;
-        hi = v < 0 ? ~0ull : 0ull;
-    } else {
-        switch (ob) {
-        case 1: lo = *p; break;
-        case 2: lo = *(const uint16_t *)p; break;
-        case 4: lo = *(const uint32_t *)p; break;
-        default: lo = *(const uint64_t *)p; break;
-        }
-        hi = 0;
-    }
-}
-
-__device__ __forceinline__ void add128(uint64_t &lo, uint64_t &hi, uint64_t blo, uint64_t bhi) {
-    lo += blo;
-    hi += bhi + (lo < blo ? 1 : 0);
-}
-
 __device__ __forceinline__ double load_float(const uint8_t *p, uint32_t ob) {
     return ob == 4 ? (double)*(const float *)p : *(const double *)p;
 }
@@ -66,46 +38,64 @@ __global__ __launch_bounds__(256) void aggregate_kernel(const DevAgg *__restrict
         uint64_t lo = 0, hi = 0;
         double fsum = -0.0;
         if (fn == AGG_MIN) lo = ~0ull;
-        for (uint32_t k = 0; k < 4; ++k) {
-            const uint32_t word = 4 * w + k;
-            const uint64_t base = (uint64_t)v * 1024 + 64 * word;
-            // rows of this word below nrows: no row past the batch is ever selected
-            uint64_t m = base >= nrows ? 0ull : (nrows - base >= 64 ? ~0ull : (1ull << (nrows - base)) - 1);
-            if (mask) m &= mask[(size_t)v * 16 + word];
-            if (fn != AGG_COUNT_STAR) {
-                if (g.valid) m &= g.valid[(size_t)v * 16 + word];
-                if (fn == AGG_SUM_PRODUCT && g.valid2) m &= g.valid2[(size_t)v * 16 + word];
+        if (fn == AGG_SUM_EXPR) {
+            // a loop of its own: as one more case of the loop below it cost the other functions
+            // the schedule that keeps their four rows' loads in flight
+            uint64_t m[4], xl[4], xh[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t word = 4 * w + k;
+                const uint64_t base = (uint64_t)v * 1024 + 64 * word;
+                m[k] = base >= nrows ? 0ull : (nrows - base >= 64 ? ~0ull : (1ull << (nrows - base)) - 1);
+                if (mask) m[k] &= mask[(size_t)v * 16 + word];
+                for (uint32_t i = 0; i < g.nf; ++i)
+                    if (g.f[i].valid) m[k] &= g.f[i].valid[(size_t)v * 16 + word];
+                cnt += (uint64_t)__popcll(m[k]);
             }
-            cnt += (uint64_t)__popcll(m);
-            if (fn <= AGG_COUNT || !((m >> lane) & 1)) continue;
-            const uint64_t row = base + lane;
-            const uint8_t *p = g.col + row * g.ob;
-            if (fn == AGG_SUM) {
-                if (flt) {
-                    fsum += load_float(p, g.ob);
-                } else {
-                    uint64_t xl, xh;
+            expr_values(g, (uint64_t)v * 1024 + 256 * w + lane, m, lane, xl, xh);
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) add128(lo, hi, xl[k], xh[k]);  // (0 for a row that does not contribute)
+        } else {
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t word = 4 * w + k;
+                const uint64_t base = (uint64_t)v * 1024 + 64 * word;
+                // rows of this word below nrows: no row past the batch is ever selected
+                uint64_t m = base >= nrows ? 0ull : (nrows - base >= 64 ? ~0ull : (1ull << (nrows - base)) - 1);
+                if (mask) m &= mask[(size_t)v * 16 + word];
+                if (fn != AGG_COUNT_STAR) {
+                    if (g.valid) m &= g.valid[(size_t)v * 16 + word];
+                    if (fn == AGG_SUM_PRODUCT && g.valid2) m &= g.valid2[(size_t)v * 16 + word];
+                }
+                cnt += (uint64_t)__popcll(m);
+                if (fn <= AGG_COUNT || !((m >> lane) & 1)) continue;
+                const uint64_t row = base + lane;
+                const uint8_t *p = g.col + row * g.ob;
+                if (fn == AGG_SUM) {
+                    if (flt) {
+                        fsum += load_float(p, g.ob);
+                    } else {
+                        uint64_t xl, xh;
+                        load_wide(p, g.ob, g.kind == FK_INT, xl, xh);
+                        add128(lo, hi, xl, xh);
+                    }
+                } else if (fn == AGG_SUM_PRODUCT) {
+                    // the product of the sign- / zero-extended operands mod 2^128
+                    uint64_t xl, xh, yl, yh;
                     load_wide(p, g.ob, g.kind == FK_INT, xl, xh);
+                    load_wide(g.col2 + row * g.ob2, g.ob2, g.kind2 == FK_INT, yl, yh);
+                    mul128(xl, xh, yl, yh);
                     add128(lo, hi, xl, xh);
+                } else {  // MIN / MAX over order keys
+                    uint64_t key;
+                    if (flt) {
+                        key = agg_key_float(load_float(p, g.ob));
+                    } else {
+                        uint64_t xl, xh;
+                        load_wide(p, g.ob, g.kind == FK_INT, xl, xh);
+                        key = g.kind == FK_INT ? agg_key_int((int64_t)xl) : xl;
+                    }
+                    lo = is_min ? (key < lo ? key : lo) : (key > lo ? key : lo);
                 }
-            } else if (fn == AGG_SUM_PRODUCT) {
-                // the product of the sign- / zero-extended operands mod 2^128
-                uint64_t xl, xh, yl, yh;
-                load_wide(p, g.ob, g.kind == FK_INT, xl, xh);
-                load_wide(g.col2 + row * g.ob2, g.ob2, g.kind2 == FK_INT, yl, yh);
-                const uint64_t pl = xl * yl;
-                const uint64_t ph = __umul64hi(xl, yl) + xl * yh + xh * yl;
-                add128(lo, hi, pl, ph);
-            } else {  // MIN / MAX over order keys
-                uint64_t key;
-                if (flt) {
-                    key = agg_key_float(load_float(p, g.ob));
-                } else {
-                    uint64_t xl, xh;
-                    load_wide(p, g.ob, g.kind == FK_INT, xl, xh);
-                    key = g.kind == FK_INT ? agg_key_int((int64_t)xl) : xl;
-                }
-                lo = is_min ? (key < lo ? key : lo) : (key > lo ? key : lo);
             }
         }
         // across the wave (cnt is the same in every lane already)
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(256) void aggregate_kernel(const DevAgg *__restrict
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) fsum += __shfl_xor(fsum, d, 64);
             __builtin_memcpy(&lo, &fsum, 8);
-        } else if (fn == AGG_SUM || fn == AGG_SUM_PRODUCT) {
+        } else if (fn == AGG_SUM || fn == AGG_SUM_PRODUCT || fn == AGG_SUM_EXPR) {
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) {
                 const uint64_t ol = shfl64(lo, d), oh = shfl64(hi, d);
@@ -147,7 +137,7 @@ __global__ __launch_bounds__(256) void aggregate_kernel(const DevAgg *__restrict
             if (g.fn == AGG_SUM && g.kind == FK_FLOAT) {
                 const double s = as_double(r.lo) + as_double(l);
                 __builtin_memcpy(&r.lo, &s, 8);
-            } else if (g.fn == AGG_SUM || g.fn == AGG_SUM_PRODUCT) {
+            } else if (g.fn == AGG_SUM || g.fn == AGG_SUM_PRODUCT || g.fn == AGG_SUM_EXPR) {
                 add128(r.lo, r.hi, l, h);
             } else if (g.fn == AGG_MIN) {
                 r.lo = l < r.lo ? l : r.lo;

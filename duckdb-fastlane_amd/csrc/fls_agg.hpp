@@ -1,6 +1,7 @@
 // fls_agg.hpp -- ungrouped aggregates over a decoded scan batch in HBM
-// (fls_aggregate): COUNT, SUM, MIN, MAX and SUM of products, under the
-// pushed-down filter's selection mask and the columns' validity bitmaps.
+// (fls_aggregate): COUNT, SUM, MIN, MAX, SUM of products and SUM of products
+// of affine terms k + s * column, under the pushed-down filter's selection
+// mask and the columns' validity bitmaps.
 //
 // One launch per batch evaluates every requested aggregate and writes one
 // fixed-size partial record per (1024-row vector, aggregate); the host folds
@@ -13,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "fls_filter.hpp"
@@ -20,12 +22,21 @@
 namespace fls {
 
 enum AggFn : uint8_t {  // fls_agg_fn (flsgpu.h)
-    AGG_COUNT_STAR = 0, AGG_COUNT = 1, AGG_SUM = 2, AGG_MIN = 3, AGG_MAX = 4, AGG_SUM_PRODUCT = 5
+    AGG_COUNT_STAR = 0, AGG_COUNT = 1, AGG_SUM = 2, AGG_MIN = 3, AGG_MAX = 4, AGG_SUM_PRODUCT = 5,
+    AGG_SUM_EXPR = 6
 };
 constexpr uint32_t kMaxAggs = 32;
+constexpr uint32_t kMaxFactors = 3;   // factors of a SUM_EXPR product
+
+// One factor k + sign * column of a SUM_EXPR, evaluated mod 2^128.
+struct DevFactor {            // 24 B
+    const uint8_t *col;       // decoded column of the batch in HBM (row 0 of the batch)
+    const uint64_t *valid;    // its validity words for the batch rows (HBM), or NULL: no NULL in the batch
+    int64_t k;                // the constant, in the column's physical unit
+};
 
 // One aggregate of a batch as the kernel sees it.
-struct DevAgg {               // 48 B
+struct DevAgg {               // 120 B
     const uint8_t *col;       // decoded operand column of the batch in HBM (row 0 of the batch);
                               // unused by the counts
     const uint8_t *col2;      // SUM_PRODUCT: the second operand
@@ -35,14 +46,21 @@ struct DevAgg {               // 48 B
     uint8_t ob, ob2;          // bytes per decoded value
     uint8_t kind, kind2;      // FilterKind of the operands: FK_INT / FK_UINT / FK_FLOAT
     uint8_t fslot;            // grouped call: which of the FLOAT / DOUBLE sums this is (fls_groupagg.hpp)
-    uint8_t pad[10];
+    // SUM_EXPR: the product of f[0..nf); col / col2 / valid / valid2 / ob / kind are unused
+    uint8_t nf;               // 1..kMaxFactors
+    uint8_t fob[kMaxFactors];   // bytes per decoded value of each factor's column
+    uint8_t fkind[kMaxFactors]; // FK_INT / FK_UINT
+    uint8_t fneg[kMaxFactors];  // 1: sign = -1
+    DevFactor f[kMaxFactors];
 };
-static_assert(sizeof(DevAgg) == 48, "DevAgg is 48 B");
+static_assert(sizeof(DevFactor) == 24, "DevFactor is 24 B");
+static_assert(sizeof(DevAgg) == 120 && offsetof(DevAgg, f) == 48, "DevAgg is 48 B + 3 factors");
 
 // Partial result of one aggregate over one vector.
 //   counts:            count only
 //   integer SUM /
-//   SUM_PRODUCT:       lo, hi = the 128-bit two's-complement sum
+//   SUM_PRODUCT /
+//   SUM_EXPR:          lo, hi = the 128-bit two's-complement sum
 //   FLOAT/DOUBLE SUM:  lo = binary64 bits of the sum (-0.0 when count == 0)
 //   MIN / MAX:         lo = order key of the extreme value (agg_key_*), meaningless when count == 0
 struct AggRec {               // 32 B
@@ -69,6 +87,79 @@ __host__ __device__ inline double agg_unkey_float(uint64_t k) {
     const uint64_t b = (k >> 63) ? k ^ (1ull << 63) : ~k;
     return as_double(b);
 }
+
+// The integer arithmetic the two aggregate kernels share (fls_agg.hip,
+// fls_groupagg.hip): 128-bit two's-complement values as (lo, hi).
+#ifdef __HIPCC__
+// the operand at p as a 128-bit two's-complement integer (lo, hi)
+__device__ __forceinline__ void load_wide(const uint8_t *p, uint32_t ob, bool sign, uint64_t &lo, uint64_t &hi) {
+    if (sign) {
+        int64_t v;
+        switch (ob) {
+        case 1: v = *(const int8_t *)p; break;
+        case 2: v = *(const int16_t *)p; break;
+        case 4: v = *(const int32_t *)p; break;
+        default: v = *(const int64_t *)p; break;
+        }
+        lo = (uint64_t)v;
+        hi = v < 0 ? ~0ull : 0ull;
+    } else {
+        switch (ob) {
+        case 1: lo = *p; break;
+        case 2: lo = *(const uint16_t *)p; break;
+        case 4: lo = *(const uint32_t *)p; break;
+        default: lo = *(const uint64_t *)p; break;
+        }
+        hi = 0;
+    }
+}
+
+__device__ __forceinline__ void add128(uint64_t &lo, uint64_t &hi, uint64_t blo, uint64_t bhi) {
+    lo += blo;
+    hi += bhi + (lo < blo ? 1 : 0);
+}
+
+// (lo, hi) *= (blo, bhi) mod 2^128
+__device__ __forceinline__ void mul128(uint64_t &lo, uint64_t &hi, uint64_t blo, uint64_t bhi) {
+    const uint64_t pl = lo * blo;
+    hi = __umul64hi(lo, blo) + lo * bhi + hi * blo;
+    lo = pl;
+}
+
+// SUM_EXPR's operands of a lane's four rows row0 + 64 * k (k = 0..3: the
+// wave's four words), where bit `lane` of m[k] is set: the product of the
+// factors k + sign * column mod 2^128; (0, 0) for the other rows.  The factors
+// go one after the other (not unrolled: the descriptor fields are wave-uniform
+// and one factor's registers are reused by the next), each with its four rows'
+// loads in flight together.
+__device__ __forceinline__ void expr_values(const DevAgg &g, uint64_t row0, const uint64_t m[4], uint32_t lane,
+                                            uint64_t lo[4], uint64_t hi[4]) {
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        lo[k] = (m[k] >> lane) & 1;
+        hi[k] = 0;
+    }
+#pragma unroll 1
+    for (uint32_t i = 0; i < g.nf; ++i) {
+        const uint8_t *col = g.f[i].col;
+        const uint32_t ob = g.fob[i];
+        const bool sign = g.fkind[i] == FK_INT, neg = g.fneg[i] != 0;
+        const int64_t c = g.f[i].k;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            if (!((m[k] >> lane) & 1)) continue;
+            uint64_t xl, xh;
+            load_wide(col + (row0 + 64 * k) * ob, ob, sign, xl, xh);
+            if (neg) {  // two's-complement negation
+                xl = 0 - xl;
+                xh = ~xh + (xl == 0 ? 1 : 0);
+            }
+            add128(xl, xh, (uint64_t)c, c < 0 ? ~0ull : 0ull);
+            mul128(lo[k], hi[k], xl, xh);
+        }
+    }
+}
+#endif
 
 // naggs <= kMaxAggs records per vector, vector-major: d_out[v * naggs + a].
 // d_mask: filter_kernel's selection words (16 per vector), or nullptr = every

@@ -38,34 +38,6 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t x, int d) {
     return (uint64_t)__shfl_xor((unsigned long long)x, d, 64);
 }
 
-// the operand at p as a 128-bit two's-complement integer (lo, hi)
-__device__ __forceinline__ void load_wide(const uint8_t *p, uint32_t ob, bool sign, uint64_t &lo, uint64_t &hi) {
-    if (sign) {
-        int64_t v;
-        switch (ob) {
-        case 1: v = *(const int8_t *)p; break;
-        case 2: v = *(const int16_t *)p; break;
-        case 4: v = *(const int32_t *)p; break;
-        default: v = *(const int64_t *)p; break;
-        }
-        lo = (uint64_t)v;
-        hi = v < 0 ? ~0ull : 0ull;
-    } else {
-        switch (ob) {
-        case 1: lo = *p; break;
-        case 2: lo = *(const uint16_t *)p; break;
-        case 4: lo = *(const uint32_t *)p; break;
-        default: lo = *(const uint64_t *)p; break;
-        }
-        hi = 0;
-    }
-}
-
-__device__ __forceinline__ void add128(uint64_t &lo, uint64_t &hi, uint64_t blo, uint64_t bhi) {
-    lo += blo;
-    hi += bhi + (lo < blo ? 1 : 0);
-}
-
 __device__ __forceinline__ double load_float(const uint8_t *p, uint32_t ob) {
     return ob == 4 ? (double)*(const float *)p : *(const double *)p;
 }
@@ -184,39 +156,52 @@ __global__ __launch_bounds__(256) void group_vector_kernel(const DevKey *__restr
         // the operand, once per contributing row: integer sums (lo, hi), float
         // sums lo = binary64 bits, MIN / MAX lo = order key
         uint64_t cm[4], vlo[4], vhi[4];
+        if (fn == AGG_SUM_EXPR) {
+            // a loop of its own: as one more case of the loop below it cost the other functions
+            // the schedule that keeps their four rows' loads in flight
 #pragma unroll
-        for (uint32_t k = 0; k < 4; ++k) {
-            const uint32_t word = 4 * w + k;
-            uint64_t m = sel[k];
-            if (fn != AGG_COUNT_STAR) {
-                if (g.valid) m &= g.valid[(size_t)v * 16 + word];
-                if (fn == AGG_SUM_PRODUCT && g.valid2) m &= g.valid2[(size_t)v * 16 + word];
+            for (uint32_t k = 0; k < 4; ++k) {
+                cm[k] = sel[k];
+                for (uint32_t i = 0; i < g.nf; ++i)
+                    if (g.f[i].valid) cm[k] &= g.f[i].valid[(size_t)v * 16 + 4 * w + k];
             }
-            cm[k] = m;
-            vlo[k] = vhi[k] = 0;
-            if (fn <= AGG_COUNT || !((m >> lane) & 1)) continue;
-            const uint64_t row = (uint64_t)v * 1024 + 64 * word + lane;
-            const uint8_t *p = g.col + row * g.ob;
-            if (fn == AGG_SUM) {
-                if (flt) {
-                    const double x = load_float(p, g.ob);
-                    __builtin_memcpy(&vlo[k], &x, 8);
-                } else {
-                    load_wide(p, g.ob, g.kind == FK_INT, vlo[k], vhi[k]);
+            expr_values(g, (uint64_t)v * 1024 + 256 * w + lane, cm, lane, vlo, vhi);
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t word = 4 * w + k;
+                uint64_t m = sel[k];
+                if (fn != AGG_COUNT_STAR) {
+                    if (g.valid) m &= g.valid[(size_t)v * 16 + word];
+                    if (fn == AGG_SUM_PRODUCT && g.valid2) m &= g.valid2[(size_t)v * 16 + word];
                 }
-            } else if (fn == AGG_SUM_PRODUCT) {
-                // the product of the sign- / zero-extended operands mod 2^128
-                uint64_t xl, xh, yl, yh;
-                load_wide(p, g.ob, g.kind == FK_INT, xl, xh);
-                load_wide(g.col2 + row * g.ob2, g.ob2, g.kind2 == FK_INT, yl, yh);
-                vlo[k] = xl * yl;
-                vhi[k] = __umul64hi(xl, yl) + xl * yh + xh * yl;
-            } else if (flt) {
-                vlo[k] = agg_key_float(load_float(p, g.ob));
-            } else {
-                uint64_t xl, xh;
-                load_wide(p, g.ob, g.kind == FK_INT, xl, xh);
-                vlo[k] = g.kind == FK_INT ? agg_key_int((int64_t)xl) : xl;
+                cm[k] = m;
+                vlo[k] = vhi[k] = 0;
+                if (fn <= AGG_COUNT || !((m >> lane) & 1)) continue;
+                const uint64_t row = (uint64_t)v * 1024 + 64 * word + lane;
+                const uint8_t *p = g.col + row * g.ob;
+                if (fn == AGG_SUM) {
+                    if (flt) {
+                        const double x = load_float(p, g.ob);
+                        __builtin_memcpy(&vlo[k], &x, 8);
+                    } else {
+                        load_wide(p, g.ob, g.kind == FK_INT, vlo[k], vhi[k]);
+                    }
+                } else if (fn == AGG_SUM_PRODUCT) {
+                    // the product of the sign- / zero-extended operands mod 2^128
+                    uint64_t xl, xh, yl, yh;
+                    load_wide(p, g.ob, g.kind == FK_INT, xl, xh);
+                    load_wide(g.col2 + row * g.ob2, g.ob2, g.kind2 == FK_INT, yl, yh);
+                    mul128(xl, xh, yl, yh);
+                    vlo[k] = xl;
+                    vhi[k] = xh;
+                } else if (flt) {
+                    vlo[k] = agg_key_float(load_float(p, g.ob));
+                } else {
+                    uint64_t xl, xh;
+                    load_wide(p, g.ob, g.kind == FK_INT, xl, xh);
+                    vlo[k] = g.kind == FK_INT ? agg_key_int((int64_t)xl) : xl;
+                }
             }
         }
         __syncthreads();  // the previous aggregate's records are written: part is free
@@ -231,14 +216,14 @@ __global__ __launch_bounds__(256) void group_vector_kernel(const DevKey *__restr
                     cnt += (uint64_t)__popcll(__ballot(c));
                     if (fn > AGG_COUNT && c) {
                         if (fn == AGG_SUM && flt) fsum += as_double(vlo[k]);
-                        else if (fn == AGG_SUM || fn == AGG_SUM_PRODUCT) add128(lo, hi, vlo[k], vhi[k]);
+                        else if (fn == AGG_SUM || fn == AGG_SUM_PRODUCT || fn == AGG_SUM_EXPR) add128(lo, hi, vlo[k], vhi[k]);
                         else lo = is_min ? (vlo[k] < lo ? vlo[k] : lo) : (vlo[k] > lo ? vlo[k] : lo);
                     }
                 }
                 if (fn == AGG_SUM && flt) {
 #pragma unroll
                     for (int d = 32; d >= 1; d >>= 1) fsum += __shfl_xor(fsum, d, 64);
-                } else if (fn == AGG_SUM || fn == AGG_SUM_PRODUCT) {
+                } else if (fn == AGG_SUM || fn == AGG_SUM_PRODUCT || fn == AGG_SUM_EXPR) {
 #pragma unroll
                     for (int d = 32; d >= 1; d >>= 1) {
                         const uint64_t ol = shfl64(lo, d), oh = shfl64(hi, d);
@@ -273,7 +258,7 @@ __global__ __launch_bounds__(256) void group_vector_kernel(const DevKey *__restr
                 if (fn == AGG_SUM && flt) {
                     const double sum = as_double(r.lo) + as_double(l);
                     __builtin_memcpy(&r.lo, &sum, 8);
-                } else if (fn == AGG_SUM || fn == AGG_SUM_PRODUCT) {
+                } else if (fn == AGG_SUM || fn == AGG_SUM_PRODUCT || fn == AGG_SUM_EXPR) {
                     add128(r.lo, r.hi, l, h);
                 } else if (fn == AGG_MIN) {
                     r.lo = l < r.lo ? l : r.lo;
@@ -362,7 +347,7 @@ __global__ __launch_bounds__(256) void group_rowgroup_kernel(const DevAgg *__res
             } else if (rec.count) {
                 AggRec x = *acc;
                 x.count += rec.count;
-                if (g.fn == AGG_SUM_PRODUCT || (g.fn == AGG_SUM && !fsum)) add128(x.lo, x.hi, rec.lo, rec.hi);
+                if (g.fn == AGG_SUM_PRODUCT || g.fn == AGG_SUM_EXPR || (g.fn == AGG_SUM && !fsum)) add128(x.lo, x.hi, rec.lo, rec.hi);
                 else if (g.fn == AGG_MIN) x.lo = rec.lo < x.lo ? rec.lo : x.lo;
                 else if (g.fn == AGG_MAX) x.lo = rec.lo > x.lo ? rec.lo : x.lo;
                 *acc = x;

@@ -1,5 +1,5 @@
 // fls_groupagg.hpp -- grouped aggregates over a decoded scan batch in HBM
-// (fls_aggregate_grouped): fls_agg.hpp's six functions per group of a
+// (fls_aggregate_grouped): fls_agg.hpp's seven functions per group of a
 // low-cardinality GROUP BY over 1 to 4 key columns.
 //
 // Two launches per batch, no global atomics on data, nothing shared between

@@ -490,6 +490,11 @@ struct HostTerm {
 struct HostAgg {
     uint8_t fn = 0;                 // AggFn
     uint32_t col = 0, col2 = 0;
+    // SUM_EXPR: the product of the factors fk + (fneg ? -1 : +1) * column fcol
+    uint32_t nf = 0;
+    uint32_t fcol[kMaxFactors] = {};
+    uint8_t fneg[kMaxFactors] = {};
+    int64_t fk[kMaxFactors] = {};
 };
 
 struct ScanCtx {
@@ -819,6 +824,7 @@ struct fls_table {
 
     ScanCtx scan, mat;
     std::vector<HostTerm> filter;   // fls_scan_filter: applies to the next fls_scan_begin / fls_aggregate
+    std::vector<fls_agg_expr> exprs;  // fls_aggregate_exprs: what FLS_AGG_SUM_EXPR's spec.col indexes
     bool dict_codes = false;        // fls_scan_dict_codes: applies to the next fls_scan_begin
     bool narrow = false;            // fls_scan_narrow: applies to the next fls_scan_begin
     bool defer_records = false;     // fls_scan_defer_records: applies to the next fls_scan_begin
@@ -1639,6 +1645,10 @@ int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uin
         s.aggs = *aggs;
         s.dict_codes = s.narrow = s.defer_records = false;
         for (auto &a : s.aggs) {
+            if (a.fn == AGG_SUM_EXPR) {
+                for (uint32_t i = 0; i < a.nf; ++i) s.dmask[a.fcol[i]] = 1;
+                continue;
+            }
             if (a.fn >= AGG_SUM) s.dmask[a.col] = 1;
             if (a.fn == AGG_SUM_PRODUCT) s.dmask[a.col2] = 1;
         }
@@ -1754,6 +1764,10 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
     need.assign(ncols, 0);
     for (auto &h : s.terms) need[h.col] = 1;
     for (auto &a : s.aggs) {
+        if (a.fn == AGG_SUM_EXPR) {
+            for (uint32_t i = 0; i < a.nf; ++i) need[a.fcol[i]] = 1;
+            continue;
+        }
         if (a.fn != AGG_COUNT_STAR) need[a.col] = 1;
         if (a.fn == AGG_SUM_PRODUCT) need[a.col2] = 1;
     }
@@ -1870,6 +1884,19 @@ int upload_agg_descs(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl) {
         memset(&da, 0, sizeof(da));
         da.fn = a.fn;
         if (a.fn == AGG_COUNT_STAR) continue;
+        if (a.fn == AGG_SUM_EXPR) {
+            da.nf = (uint8_t)a.nf;
+            for (uint32_t k = 0; k < a.nf; ++k) {
+                const uint32_t c = a.fcol[k];
+                da.f[k].col = sl.d_out[c].p;
+                da.f[k].valid = need[c] ? sl.d_valid[c].p : nullptr;
+                da.f[k].k = a.fk[k];
+                da.fob[k] = (uint8_t)out_bytes_of(t, c);
+                da.fkind[k] = kind_of(c);
+                da.fneg[k] = a.fneg[k];
+            }
+            continue;
+        }
         da.valid = need[a.col] ? sl.d_valid[a.col].p : nullptr;
         if (a.fn == AGG_COUNT) continue;
         da.col = sl.d_out[a.col].p;
@@ -2998,6 +3025,29 @@ int fls_scan_filter(fls_table *t, const fls_predicate *preds, uint32_t n) {
     return 0;
 }
 
+int fls_aggregate_exprs(fls_table *t, const fls_agg_expr *exprs, uint32_t n) {
+    if (!t || (!exprs && n)) return fail(FLS_ERR_ARG, "fls_aggregate_exprs: NULL argument");
+    if (n > kMaxAggs) return fail(FLS_ERR_ARG, "fls_aggregate_exprs: %u expressions (at most %u)", n, kMaxAggs);
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    for (uint32_t i = 0; i < n; ++i) {
+        const fls_agg_expr &e = exprs[i];
+        if (e.nfactors == 0 || e.nfactors > kMaxFactors)
+            return fail(FLS_ERR_ARG, "expression %u: %u factors (1 to %u)", i, e.nfactors, kMaxFactors);
+        for (uint32_t k = 0; k < e.nfactors; ++k) {
+            const fls_agg_factor &f = e.f[k];
+            if (f.sign != 1 && f.sign != -1)
+                return fail(FLS_ERR_ARG, "expression %u: factor %u has sign %d (+1 or -1)", i, k, (int)f.sign);
+            if (f.col >= ncols) return fail(FLS_ERR_ARG, "expression %u: column %u out of range", i, f.col);
+            const uint8_t ty = t->meta.cols[f.col].type;
+            if (type_is_string(ty) || type_is_float(ty))
+                return fail(FLS_ERR_ARG, "expression %u: a VARCHAR / BLOB / FLOAT / DOUBLE column (%u) cannot be a factor",
+                            i, f.col);
+        }
+    }
+    t->exprs.assign(exprs, exprs + n);
+    return 0;
+}
+
 }  // extern "C"
 
 namespace {
@@ -3023,6 +3073,35 @@ double mul_up(double a, double b) { return std::nextafter(a * b, HUGE_VAL); }
 // an upper bound of v as a double
 double dbl_up(uint64_t v) { return v == 0 ? 0.0 : std::nextafter((double)v, HUGE_VAL); }
 
+// An upper bound, as a double, of |k + s * x| over column c's non-NULL values
+// in row group rg (s = -1 when neg): the larger magnitude at the two ends of
+// the zone-map range (else the type's range), exact in 128 bits, then rounded
+// upwards.  0 for an all-NULL chunk: no row of it contributes.
+double max_factor(const fls_table *t, uint32_t rg, uint32_t c, bool neg, int64_t k) {
+    const uint8_t ty = t->meta.cols[c].type;
+    const bool sign = type_is_signed(ty);
+    const auto &zs = t->meta.rgs[rg].zones;
+    if (!zs.empty() && (zs[c].flags & ZM_ALL_NULL)) return 0.0;
+    __int128 lo, hi;
+    if (zs.empty() || !(zs[c].flags & ZM_VALID)) {
+        const int bits = type_value_bits(ty);
+        lo = sign ? -((__int128)1 << (bits - 1)) : 0;
+        hi = sign ? ((__int128)1 << (bits - 1)) - 1 : ((__int128)1 << bits) - 1;
+    } else if (sign) {
+        lo = (int64_t)zs[c].min;
+        hi = (int64_t)zs[c].max;
+    } else {
+        lo = zs[c].min;
+        hi = zs[c].max;
+    }
+    auto mag = [&](__int128 x) {
+        const __int128 v = (__int128)k + (neg ? -x : x);
+        return (unsigned __int128)(v < 0 ? -v : v);
+    };
+    const unsigned __int128 m = std::max(mag(lo), mag(hi));  // < 2^65
+    return m == 0 ? 0.0 : std::nextafter((double)m, HUGE_VAL);
+}
+
 // The argument checks fls_aggregate and fls_aggregate_grouped (`who`) share:
 // the aggregates into ha, or FLS_ERR_ARG before any device work.
 int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_spec *aggs, uint32_t n,
@@ -3034,9 +3113,22 @@ int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_sp
     ha.assign(n, HostAgg());
     for (uint32_t i = 0; i < n; ++i) {
         const fls_aggregate_spec &a = aggs[i];
-        if (a.fn > FLS_AGG_SUM_PRODUCT) return fail(FLS_ERR_ARG, "aggregate %u: unknown function %u", i, a.fn);
+        if (a.fn > FLS_AGG_SUM_EXPR) return fail(FLS_ERR_ARG, "aggregate %u: unknown function %u", i, a.fn);
         ha[i].fn = a.fn;
         if (a.fn == FLS_AGG_COUNT_STAR) continue;
+        if (a.fn == FLS_AGG_SUM_EXPR) {  // (fls_aggregate_exprs checked the factors)
+            if (a.col >= t->exprs.size())
+                return fail(FLS_ERR_ARG, "aggregate %u: expression %u out of range (%u set by fls_aggregate_exprs)", i,
+                            a.col, (uint32_t)t->exprs.size());
+            const fls_agg_expr &e = t->exprs[a.col];
+            ha[i].nf = e.nfactors;
+            for (uint32_t k = 0; k < e.nfactors; ++k) {
+                ha[i].fcol[k] = e.f[k].col;
+                ha[i].fneg[k] = e.f[k].sign < 0;
+                ha[i].fk[k] = e.f[k].k;
+            }
+            continue;
+        }
         if (a.col >= ncols) return fail(FLS_ERR_ARG, "aggregate %u: column %u out of range", i, a.col);
         ha[i].col = a.col;
         if (a.fn == FLS_AGG_COUNT) continue;
@@ -3055,6 +3147,21 @@ int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_sp
     // SUM_PRODUCT must stay below 2^127: bound it over the row groups the scan
     // will read (rounded upwards) before anything is decoded
     for (uint32_t i = 0; i < n; ++i) {
+        if (ha[i].fn == AGG_SUM_EXPR) {
+            // the same bound with max|k + s * x| per factor, which an affine
+            // term takes at an end of the column's range
+            double bound = 0;
+            for (uint32_t r = rg_begin; r < rg_end; ++r) {
+                if (!t->filter.empty() && !rowgroup_may_match(t, r, t->filter)) continue;
+                double term = dbl_up(t->meta.rgs[r].nrows);
+                for (uint32_t k = 0; k < ha[i].nf; ++k)
+                    term = mul_up(term, max_factor(t, r, ha[i].fcol[k], ha[i].fneg[k], ha[i].fk[k]));
+                bound = std::nextafter(bound + term, HUGE_VAL);
+            }
+            if (bound >= 0x1p127)
+                return fail(FLS_ERR_ARG, "aggregate %u: SUM_EXPR of expression %u may overflow 128 bits", i, aggs[i].col);
+            continue;
+        }
         if (ha[i].fn != AGG_SUM_PRODUCT) continue;
         double bound = 0;
         for (uint32_t r = rg_begin; r < rg_end; ++r) {
@@ -3080,7 +3187,7 @@ struct AggAcc {
 };
 
 bool agg_is_float(const fls_table *t, const HostAgg &h) {
-    return h.fn >= AGG_SUM && type_is_float(t->meta.cols[h.col].type);
+    return h.fn >= AGG_SUM && h.fn != AGG_SUM_EXPR && type_is_float(t->meta.cols[h.col].type);
 }
 
 // The grouped fold's addition of a vector's partial binary64 sum onto the
@@ -3098,6 +3205,7 @@ void fold_record(AggAcc &a, uint8_t fn, bool flt, const AggRec &r) {
     switch (fn) {
     case AGG_SUM:
     case AGG_SUM_PRODUCT:
+    case AGG_SUM_EXPR:
         if (flt) a.fsum += as_double(r.lo);
         else a.sum += ((unsigned __int128)r.hi << 64) | r.lo;
         break;
@@ -3119,7 +3227,7 @@ void finish_value(const fls_table *t, const HostAgg &h, const AggAcc &a, fls_agg
     if (a.count == 0) return;  // FLS_AGGV_NULL
     const bool flt = agg_is_float(t, h);
     o.kind = flt ? FLS_AGGV_DOUBLE : FLS_AGGV_INT;
-    if (h.fn == AGG_SUM || h.fn == AGG_SUM_PRODUCT) {
+    if (h.fn == AGG_SUM || h.fn == AGG_SUM_PRODUCT || h.fn == AGG_SUM_EXPR) {
         if (flt) {
             memcpy(&o.lo, &a.fsum, 8);
         } else {

@@ -5,8 +5,13 @@
 // only per-vector partial results cross PCIe instead of the qualifying rows.
 //
 //   aggregates: comma-separated `count(*)`, `count(c)`, `sum(c)`, `sum(a * b)`,
-//               `min(c)`, `max(c)`; each output column is named by the trimmed
-//               text of its item.
+//               `min(c)`, `max(c)`, and `sum(F)`, `sum(F * F)`, `sum(F * F * F)`
+//               over factors F: a column, `(literal - column)`,
+//               `(literal + column)`, `(column + literal)` or
+//               `(column - literal)`, the literal written as the filter writes
+//               one for that column (TPC-H Q1's
+//               `sum(l_extendedprice * (1 - l_discount) * (1 + l_tax))`); each
+//               output column is named by the trimmed text of its item.
 //   filter:     `term AND term ...`, a term `column op literal` (op one of
 //               = != <> < <= > >=) or `column IS [NOT] NULL`.  Literals by
 //               column type: integers, decimal numbers the column's scale
@@ -24,7 +29,9 @@
 //
 // Output types: counts and integer sums BIGINT, sums of DECIMAL(w, s)
 // DECIMAL(18, s), sum(a * b) DECIMAL(18, s1 + s2) when an operand is DECIMAL,
-// float sums DOUBLE, min / max the column's own type.  The engine's sums are
+// a sum of factors' product DECIMAL(18, sum of the scales) when a factor's
+// column is DECIMAL (else BIGINT), float sums DOUBLE, min / max the column's
+// own type.  The engine's sums are
 // 128-bit; one that does not fit its output type raises OutOfRangeException
 // (there is no HUGEINT here).  Everything unparsable, unknown or ill-typed is a
 // BinderException quoting the offending text, raised at bind from the footer
@@ -62,6 +69,7 @@ struct AggTable {
 struct AggBindData : public TableFunctionData {
     string file;
     std::vector<fls_aggregate_spec> specs;
+    std::vector<fls_agg_expr> exprs;     // what the FLS_AGG_SUM_EXPR specs index (fls_aggregate_exprs)
     vector<LogicalType> types;
     vector<string> names;                // the items' trimmed text
     std::vector<fls_predicate> preds;
@@ -120,63 +128,6 @@ int ColumnOf(const Schema &sch, const string &name, const string &item) {
     const int c = sch.Find(n);
     if (c < 0) throw BinderException("fastlanes_aggregate: column \"" + n + "\" of aggregate \"" + item + "\" not found");
     return c;
-}
-
-// one item of the aggregate list -> spec and output type
-void ParseAggregate(const Schema &sch, const string &item, fls_aggregate_spec &spec, LogicalType &type) {
-    memset(&spec, 0, sizeof(spec));
-    const size_t open = item.find('(');
-    if (open == string::npos || item.back() != ')')
-        throw BinderException("fastlanes_aggregate: cannot parse aggregate \"" + item + "\"");
-    const string fn = StringUtil::Lower(Trim(item.substr(0, open)));
-    const string arg = Trim(item.substr(open + 1, item.size() - open - 2));
-    if (arg.find('(') != string::npos || arg.find(')') != string::npos || arg.empty())
-        throw BinderException("fastlanes_aggregate: cannot parse aggregate \"" + item + "\"");
-    if (fn == "count") {
-        type = LogicalType::BIGINT;
-        if (arg == "*") {
-            spec.fn = FLS_AGG_COUNT_STAR;
-            return;
-        }
-        spec.fn = FLS_AGG_COUNT;
-        spec.col = (uint32_t)ColumnOf(sch, arg, item);
-        return;
-    }
-    if (fn != "sum" && fn != "min" && fn != "max")
-        throw BinderException("fastlanes_aggregate: unknown aggregate function \"" + fn + "\" in \"" + item + "\"");
-    const size_t star = arg.find('*');
-    if (star != string::npos) {
-        if (fn != "sum") throw BinderException("fastlanes_aggregate: a product is only supported in sum(): \"" + item + "\"");
-        const int a = ColumnOf(sch, arg.substr(0, star), item), b = ColumnOf(sch, arg.substr(star + 1), item);
-        for (int c : {a, b})
-            if (IsString(sch.cols[c].type) || IsFloat(sch.cols[c].type))
-                throw BinderException("fastlanes_aggregate: sum of a product needs integer or DECIMAL columns, \"" +
-                                      sch.names[c] + "\" is " + sch.types[c].ToString() + " in \"" + item + "\"");
-        spec.fn = FLS_AGG_SUM_PRODUCT;
-        spec.col = (uint32_t)a;
-        spec.col2 = (uint32_t)b;
-        const bool dec = sch.cols[a].type == FLS_DECIMAL || sch.cols[b].type == FLS_DECIMAL;
-        const unsigned scale = (sch.cols[a].type == FLS_DECIMAL ? sch.cols[a].scale : 0u) +
-                               (sch.cols[b].type == FLS_DECIMAL ? sch.cols[b].scale : 0u);
-        if (scale > 18)
-            throw BinderException("fastlanes_aggregate: the scale of \"" + item + "\" exceeds DECIMAL(18)");
-        type = dec ? LogicalType::DECIMAL(18, (uint8_t)scale) : LogicalType::BIGINT;
-        return;
-    }
-    const int c = ColumnOf(sch, arg, item);
-    if (IsString(sch.cols[c].type))
-        throw BinderException("fastlanes_aggregate: " + fn + " of " + sch.types[c].ToString() + " column \"" + sch.names[c] +
-                              "\" is not supported in \"" + item + "\"");
-    spec.col = (uint32_t)c;
-    if (fn == "sum") {
-        spec.fn = FLS_AGG_SUM;
-        type = IsFloat(sch.cols[c].type)           ? LogicalType::DOUBLE
-               : sch.cols[c].type == FLS_DECIMAL ? LogicalType::DECIMAL(18, sch.cols[c].scale)
-                                                 : LogicalType::BIGINT;
-    } else {
-        spec.fn = fn == "min" ? FLS_AGG_MIN : FLS_AGG_MAX;
-        type = sch.types[c];
-    }
 }
 
 // ---- the filter text ------------------------------------------------------
@@ -264,7 +215,7 @@ bool AllDigits(const string &s) {
 
 // the literal of a comparison in the column's physical type (fls_predicate.value / str)
 void SetLiteral(const Schema &sch, int col, Lexer &lex, Token lit, const string &filter, fls_predicate &p,
-                std::deque<string> &strs) {
+                std::deque<string> &strs, const char *where = "filter") {
     const fls_column_info &ci = sch.cols[col];
     const string cname = sch.names[col];
     bool date_kw = false;
@@ -272,15 +223,15 @@ void SetLiteral(const Schema &sch, int col, Lexer &lex, Token lit, const string 
         date_kw = true;
         lit = lex.Next();
         if (lit.kind != Token::STRING)
-            throw BinderException("fastlanes_aggregate: DATE needs a 'YYYY-MM-DD' string in filter \"" + filter + "\"");
+            throw BinderException(string("fastlanes_aggregate: DATE needs a 'YYYY-MM-DD' string in ") + where + " \"" + filter + "\"");
     }
     auto bad = [&](const char *want) {
         return BinderException("fastlanes_aggregate: \"" + (lit.kind == Token::STRING ? "'" + lit.text + "'" : lit.text) +
                                "\" is not " + want + " for " + sch.types[col].ToString() + " column \"" + cname +
-                               "\" in filter \"" + filter + "\"");
+                               "\" in " + where + " \"" + filter + "\"");
     };
     if (lit.kind == Token::END || lit.kind == Token::OP)
-        throw BinderException("fastlanes_aggregate: a literal is missing after column \"" + cname + "\" in filter \"" +
+        throw BinderException("fastlanes_aggregate: a literal is missing after column \"" + cname + "\" in " + where + " \"" +
                               filter + "\"");
     if (date_kw != (ci.type == FLS_DATE)) throw bad(ci.type == FLS_DATE ? "a DATE 'YYYY-MM-DD' literal" : "a literal");
     switch (ci.type) {
@@ -351,6 +302,161 @@ void SetLiteral(const Schema &sch, int col, Lexer &lex, Token lit, const string 
     } else {
         if (v > ((unsigned __int128)1 << 63) - (neg ? 0 : 1)) throw bad("in range");
         p.value = neg ? (uint64_t)0 - (uint64_t)v : (uint64_t)v;
+    }
+}
+
+// ---- the aggregate list ---------------------------------------------------
+// One factor of a sum's product: a column, or a parenthesised column and
+// literal joined by + or - (k + sign * column in the column's physical unit).
+// `plain` tells a bare column.
+fls_agg_factor ParseFactor(const Schema &sch, const string &text, const string &item, bool &plain) {
+    fls_agg_factor f;
+    memset(&f, 0, sizeof(f));
+    f.sign = 1;
+    auto check_type = [&](int c) {
+        if (IsString(sch.cols[c].type) || IsFloat(sch.cols[c].type))
+            throw BinderException("fastlanes_aggregate: sum of a product needs integer or DECIMAL columns, \"" +
+                                  sch.names[c] + "\" is " + sch.types[c].ToString() + " in \"" + item + "\"");
+    };
+    plain = text.empty() || text.front() != '(';
+    if (plain) {
+        const int c = ColumnOf(sch, text, item);
+        check_type(c);
+        f.col = (uint32_t)c;
+        return f;
+    }
+    const string inner = Trim(text.substr(1, text.size() - 2));
+    // the operator: the first + or - past the first character (which may be the literal's sign)
+    size_t op = string::npos;
+    for (size_t i = 1; i < inner.size() && op == string::npos; ++i)
+        if (inner[i] == '+' || inner[i] == '-') op = i;
+    if (op == string::npos)
+        throw BinderException("fastlanes_aggregate: cannot parse factor \"" + text + "\" in aggregate \"" + item + "\"");
+    const string lhs = Trim(inner.substr(0, op)), rhs = Trim(inner.substr(op + 1));
+    auto is_col = [&](const string &n) {
+        return (IsIdent(n) || (n.size() >= 2 && n.front() == '"' && n.back() == '"')) && sch.Find(n) >= 0;
+    };
+    const bool lcol = is_col(lhs), rcol = is_col(rhs);
+    if (lcol == rcol)
+        throw BinderException(string("fastlanes_aggregate: a factor needs one column and one literal, \"") + text +
+                              "\" has " + (lcol ? "two columns" : "no column") + " in aggregate \"" + item + "\"");
+    const int c = sch.Find(lcol ? lhs : rhs);
+    check_type(c);
+    f.col = (uint32_t)c;
+    const string lit = lcol ? rhs : lhs;
+    if (lit.empty())
+        throw BinderException("fastlanes_aggregate: cannot parse factor \"" + text + "\" in aggregate \"" + item + "\"");
+    fls_predicate p;
+    memset(&p, 0, sizeof(p));
+    std::deque<string> strs;
+    Lexer lex(lit);
+    SetLiteral(sch, c, lex, lex.Next(), item, p, strs, "aggregate");
+    if (lex.Next().kind != Token::END)
+        throw BinderException("fastlanes_aggregate: cannot parse \"" + lit + "\" in aggregate \"" + item + "\"");
+    const bool is_unsigned = sch.cols[c].type >= FLS_UINT8 && sch.cols[c].type <= FLS_UINT64;
+    const bool minus = inner[op] == '-';
+    // k is an int64: an unsigned literal past it, or the negation of the lowest one, has no place
+    if ((is_unsigned && p.value > (uint64_t)INT64_MAX) || (lcol && minus && p.value == (1ull << 63)))
+        throw BinderException("fastlanes_aggregate: \"" + lit + "\" is not in range for a factor of aggregate \"" + item +
+                              "\"");
+    f.k = (int64_t)p.value;
+    if (lcol && minus) f.k = -f.k;       // (column - literal)
+    if (!lcol && minus) f.sign = -1;     // (literal - column)
+    return f;
+}
+
+// one item of the aggregate list -> spec and output type; a sum of factors
+// that is not a plain column or the product of two appends its expression
+void ParseAggregate(const Schema &sch, const string &item, fls_aggregate_spec &spec, LogicalType &type,
+                    std::vector<fls_agg_expr> &exprs) {
+    memset(&spec, 0, sizeof(spec));
+    const size_t open = item.find('(');
+    if (open == string::npos || item.back() != ')')
+        throw BinderException("fastlanes_aggregate: cannot parse aggregate \"" + item + "\"");
+    const string fn = StringUtil::Lower(Trim(item.substr(0, open)));
+    const string arg = Trim(item.substr(open + 1, item.size() - open - 2));
+    if (arg.empty() || (fn != "sum" && (arg.find('(') != string::npos || arg.find(')') != string::npos)))
+        throw BinderException("fastlanes_aggregate: cannot parse aggregate \"" + item + "\"");
+    if (fn == "count") {
+        type = LogicalType::BIGINT;
+        if (arg == "*") {
+            spec.fn = FLS_AGG_COUNT_STAR;
+            return;
+        }
+        spec.fn = FLS_AGG_COUNT;
+        spec.col = (uint32_t)ColumnOf(sch, arg, item);
+        return;
+    }
+    if (fn != "sum" && fn != "min" && fn != "max")
+        throw BinderException("fastlanes_aggregate: unknown aggregate function \"" + fn + "\" in \"" + item + "\"");
+    // the factors: split at * outside parentheses, which do not nest
+    std::vector<string> parts;
+    {
+        int depth = 0;
+        size_t start = 0;
+        for (size_t i = 0; i <= arg.size(); ++i) {
+            if (i < arg.size() && arg[i] == '(') ++depth;
+            if (i < arg.size() && arg[i] == ')') --depth;
+            if (depth < 0 || depth > 1)
+                throw BinderException("fastlanes_aggregate: unbalanced or nested parentheses in aggregate \"" + item + "\"");
+            if (i == arg.size() || (arg[i] == '*' && depth == 0)) {
+                parts.push_back(Trim(arg.substr(start, i - start)));
+                start = i + 1;
+            }
+        }
+        if (depth != 0)
+            throw BinderException("fastlanes_aggregate: unbalanced or nested parentheses in aggregate \"" + item + "\"");
+    }
+    const bool parens = arg.find('(') != string::npos;
+    if (parts.size() > 1 || parens) {
+        if (fn != "sum") throw BinderException("fastlanes_aggregate: a product is only supported in sum(): \"" + item + "\"");
+        if (parts.size() > 3)
+            throw BinderException("fastlanes_aggregate: at most 3 factors in a product, \"" + item + "\" holds " +
+                                  std::to_string(parts.size()));
+        fls_agg_expr e;
+        memset(&e, 0, sizeof(e));
+        bool all_plain = true, dec = false;
+        unsigned scale = 0;
+        for (const string &part : parts) {
+            if (part.size() >= 2 && part.front() == '(' && part.back() != ')')
+                throw BinderException("fastlanes_aggregate: cannot parse factor \"" + part + "\" in aggregate \"" + item +
+                                      "\"");
+            bool plain;
+            const fls_agg_factor f = ParseFactor(sch, part, item, plain);
+            all_plain = all_plain && plain;
+            e.f[e.nfactors++] = f;
+            if (sch.cols[f.col].type == FLS_DECIMAL) {
+                dec = true;
+                scale += sch.cols[f.col].scale;
+            }
+        }
+        if (scale > 18)
+            throw BinderException("fastlanes_aggregate: the scale of \"" + item + "\" exceeds DECIMAL(18)");
+        type = dec ? LogicalType::DECIMAL(18, (uint8_t)scale) : LogicalType::BIGINT;
+        if (all_plain && e.nfactors == 2) {  // the product of two columns
+            spec.fn = FLS_AGG_SUM_PRODUCT;
+            spec.col = e.f[0].col;
+            spec.col2 = e.f[1].col;
+            return;
+        }
+        spec.fn = FLS_AGG_SUM_EXPR;
+        spec.col = (uint32_t)exprs.size();
+        exprs.push_back(e);
+        return;
+    }
+    const int c = ColumnOf(sch, arg, item);
+    if (IsString(sch.cols[c].type))
+        throw BinderException("fastlanes_aggregate: " + fn + " of " + sch.types[c].ToString() + " column \"" + sch.names[c] +
+                              "\" is not supported in \"" + item + "\"");
+    spec.col = (uint32_t)c;
+    if (fn == "sum") {
+        spec.fn = FLS_AGG_SUM;
+        type = IsFloat(sch.cols[c].type)           ? LogicalType::DOUBLE
+               : sch.cols[c].type == FLS_DECIMAL ? LogicalType::DECIMAL(18, sch.cols[c].scale)
+                                                 : LogicalType::BIGINT;
+    } else {
+        spec.fn = fn == "min" ? FLS_AGG_MIN : FLS_AGG_MAX;
+        type = sch.types[c];
     }
 }
 
@@ -469,7 +575,7 @@ unique_ptr<FunctionData> AggBind(ClientContext &, TableFunctionBindInput &input,
         if (item.empty()) throw BinderException("fastlanes_aggregate: empty item in aggregate list \"" + list + "\"");
         fls_aggregate_spec spec;
         LogicalType type;
-        ParseAggregate(sch, item, spec, type);
+        ParseAggregate(sch, item, spec, type, bind->exprs);
         bind->specs.push_back(spec);
         bind->types.push_back(type);
         names.push_back(item);
@@ -528,12 +634,14 @@ void AggScanGrouped(const AggBindData &bind, AggGlobalState &g, DataChunk &outpu
     fls_table *t = bind.table->table;
     if (!g.done) {
         g.done = true;
-        if (fls_scan_filter(t, bind.preds.data(), (uint32_t)bind.preds.size()) != 0)
+        if (fls_scan_filter(t, bind.preds.data(), (uint32_t)bind.preds.size()) != 0 ||
+            fls_aggregate_exprs(t, bind.exprs.data(), (uint32_t)bind.exprs.size()) != 0)
             throw IOException(string("FastLanes aggregate failed: ") + fls_last_error());
         const int rc = fls_aggregate_grouped(t, bind.keys.data(), (uint32_t)bind.keys.size(), bind.specs.data(),
                                              (uint32_t)bind.specs.size(), 0, fls_table_nrowgroups(t), &g.groups);
         const string err = rc ? fls_last_error() : "";
         fls_scan_filter(t, nullptr, 0);
+        fls_aggregate_exprs(t, nullptr, 0);
         if (rc == FLS_ERR_LIMIT)
             throw InvalidInputException("fastlanes_aggregate: " + err +
                                         "; use SELECT ... FROM read_fastlanes(...) GROUP BY ... instead");
@@ -578,12 +686,14 @@ void AggScan(ClientContext &, TableFunctionInput &data, DataChunk &output) {
     }
     fls_table *t = bind.table->table;
     std::vector<fls_aggregate_value> vals(bind.specs.size());
-    if (fls_scan_filter(t, bind.preds.data(), (uint32_t)bind.preds.size()) != 0)
+    if (fls_scan_filter(t, bind.preds.data(), (uint32_t)bind.preds.size()) != 0 ||
+        fls_aggregate_exprs(t, bind.exprs.data(), (uint32_t)bind.exprs.size()) != 0)
         throw IOException(string("FastLanes aggregate failed: ") + fls_last_error());
     const int rc = fls_aggregate(t, bind.specs.data(), (uint32_t)bind.specs.size(), 0, fls_table_nrowgroups(t), vals.data());
     const string err = rc ? fls_last_error() : "";
     fls_scan_filter(t, nullptr, 0);
-    if (rc == FLS_ERR_ARG) throw OutOfRangeException("fastlanes_aggregate: " + err);  // the SUM_PRODUCT bound
+    fls_aggregate_exprs(t, nullptr, 0);
+    if (rc == FLS_ERR_ARG) throw OutOfRangeException("fastlanes_aggregate: " + err);  // the SUM_PRODUCT / SUM_EXPR bound
     if (rc) throw IOException("FastLanes aggregate failed: " + err);
     for (idx_t j = 0; j < output.ColumnCount() && j < vals.size(); ++j) EmitValue(bind, j, vals[j], output.data[j], 0);
     output.SetCardinality(1);

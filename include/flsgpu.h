@@ -234,7 +234,8 @@ int fls_scan_pruned(const fls_table *t);
  * bound (sum over the scanned row groups of rows * max|a| * max|b|) reaches
  * 2^127.  Not in the reference, which delivers every decoded row to DuckDB. */
 typedef enum fls_agg_fn { FLS_AGG_COUNT_STAR = 0, FLS_AGG_COUNT = 1, FLS_AGG_SUM = 2,
-                          FLS_AGG_MIN = 3, FLS_AGG_MAX = 4, FLS_AGG_SUM_PRODUCT = 5 } fls_agg_fn;
+                          FLS_AGG_MIN = 3, FLS_AGG_MAX = 4, FLS_AGG_SUM_PRODUCT = 5,
+                          FLS_AGG_SUM_EXPR = 6 /* spec.col indexes the table's expression list */ } fls_agg_fn;
 typedef struct fls_aggregate_spec { uint8_t fn; uint8_t pad[3]; uint32_t col; uint32_t col2; uint32_t pad2; } fls_aggregate_spec;
 typedef enum fls_agg_kind { FLS_AGGV_NULL = 0, FLS_AGGV_INT = 1, FLS_AGGV_DOUBLE = 2 } fls_agg_kind;
 typedef struct fls_aggregate_value {
@@ -247,6 +248,26 @@ typedef struct fls_aggregate_value {
 } fls_aggregate_value;
 int fls_aggregate(fls_table *t, const fls_aggregate_spec *aggs, uint32_t n,
                   uint32_t rg_begin, uint32_t rg_end, fls_aggregate_value *out);
+/* Expression list for FLS_AGG_SUM_EXPR in the following fls_aggregate and
+ * fls_aggregate_grouped calls on this table (copied; n = 0 clears; n <= 32;
+ * sticky like fls_scan_filter's terms).  An expression is the product of 1 to
+ * 3 factors k + sign * column: sign is +1 or -1, k an int64 in the column's
+ * physical unit (a DECIMAL constant scaled), the column INT*, UINT*, BOOLEAN,
+ * DATE or DECIMAL; one column may appear in several factors.  SUM_EXPR is the
+ * exact 128-bit two's-complement sum of the product, with SUM_PRODUCT's
+ * filter, pruning and determinism: a row contributes when the filter selects
+ * it and every factor's column is valid there; no such row gives
+ * FLS_AGGV_NULL.  FLS_ERR_ARG naming "expression i" before any device work:
+ * nfactors outside 1..3, a sign other than +1 / -1, a column out of range, a
+ * VARCHAR / BLOB / FLOAT / DOUBLE column.  The aggregate calls refuse, naming
+ * "aggregate i", a spec.col at or past the number of expressions set, and a
+ * SUM_EXPR whose zone-map bound -- sum over the scanned row groups of rows *
+ * prod max|k + sign * x|, the maxima taken at the ends of the zone-map range
+ * (the type's range without a zone map, 0 for an all-NULL chunk), rounded
+ * upwards -- reaches 2^127.  Not in the reference. */
+typedef struct fls_agg_factor { uint32_t col; int8_t sign; uint8_t pad[3]; int64_t k; } fls_agg_factor;   /* k + sign * column */
+typedef struct fls_agg_expr   { uint32_t nfactors; uint32_t pad; fls_agg_factor f[3]; } fls_agg_expr;     /* product of 1..3 factors */
+int fls_aggregate_exprs(fls_table *t, const fls_agg_expr *exprs, uint32_t n);
 /* GROUP BY keys[0..nkeys) of the same aggregates, for low-cardinality keys:
  * fls_aggregate's functions, filter, pruning, argument checks and numeric
  * results, per group.  The batch is reduced in HBM per (1024-row vector, key)

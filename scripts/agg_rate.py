@@ -12,14 +12,20 @@ clock around the synchronous call):
   unfiltered  A: Table.aggregate([sum(l_quantity), min(l_shipdate), max(l_shipdate), count(*)])
               B: scan(cols=[l_quantity, l_shipdate]) + numpy
 
-  Q1          A: Table.aggregate_grouped by l_returnflag, l_linestatus of the Q1 aggregates under the shipdate term
-              B: scan_filtered of the same five columns + a numpy group-by (the only way without the grouped call)
+  Q1          A: Table.aggregate_grouped by l_returnflag, l_linestatus of TPC-H Q1's sums -- sum(l_quantity),
+                 sum(l_extendedprice), sum(l_extendedprice * (1 - l_discount)),
+                 sum(l_extendedprice * (1 - l_discount) * (1 + l_tax)) -- with sum(l_discount) and count(*), from
+                 which the query's averages follow, under the shipdate term
+              B: scan_filtered of the same six columns + a numpy group-by summed in Python integers (the only way
+                 without the grouped call)
               C: Table.aggregate of the same aggregates and filter, ungrouped: the floor the grouping is paid on top of
 
 The arms' answers are compared before anything is printed.
 
     python scripts/agg_rate.py --scale 10 --reps 5 > all.txt        (--query picks one of them)
-    python scripts/agg_rate.py --scale 10 --reps 5 --query q1 > profiles/agg/group_rate_sf10.txt
+    python scripts/agg_rate.py --scale 10 --reps 5 --query q1 > profiles/agg/q1_full_sf10.txt
+(profiles/agg/group_rate_sf10.txt is the same query with sum(l_extendedprice * l_discount) standing in for the
+two products, as the script measured it before the engine had sums of affine factors.)
 """
 import argparse
 import os
@@ -68,12 +74,17 @@ def plain_scan(t):
     return [total, lo, hi, rows]
 
 
-# ---- TPC-H Q1: the grouped call (profiles/agg/group_rate_sf10.txt)
-C_RFLAG, C_STATUS = 8, 9
+# ---- TPC-H Q1: the grouped call (profiles/agg/q1_full_sf10.txt)
+C_TAX, C_RFLAG, C_STATUS = 7, 8, 9
 Q1_DAY = 10471                      # 1998-09-02 as DATE days
 Q1 = [(C_SHIPDATE, "<=", Q1_DAY)]
 Q1_KEYS = [C_RFLAG, C_STATUS]
-Q1_AGGS = [("sum", C_QTY), ("sum", C_PRICE), ("sum_product", C_PRICE, C_DISC), ("sum", C_DISC), ("count",)]
+# DECIMAL(15, 2) columns: 1 is 100 in their unit; sum_disc_price has scale 4, sum_charge scale 6
+Q1_AGGS = [("sum", C_QTY), ("sum", C_PRICE), ("sum_expr", [(0, 1, C_PRICE), (100, -1, C_DISC)]),
+           ("sum_expr", [(0, 1, C_PRICE), (100, -1, C_DISC), (100, 1, C_TAX)]), ("sum", C_DISC), ("count",)]
+
+
+Q1_COLS = [C_QTY, C_PRICE, C_DISC, C_TAX, C_RFLAG, C_STATUS]
 
 
 def q1_grouped(t):
@@ -93,13 +104,13 @@ def _short_strings(rec):
 
 
 def q1_scan(t):
-    """the qualifying rows of the five columns over the link, grouped with numpy;
+    """the qualifying rows of the six columns over the link, grouped with numpy;
     groups in order of their first row, as the grouped call returns them"""
     groups = {}
-    for _, _, sel, arrays in t.scan_filtered(Q1, cols=[C_QTY, C_PRICE, C_DISC, C_RFLAG, C_STATUS]):
+    for _, _, sel, arrays in t.scan_filtered(Q1, cols=Q1_COLS):
         if len(sel) == 0:
             continue
-        qty, price, disc = (arrays[c].view(np.int64) for c in (C_QTY, C_PRICE, C_DISC))
+        qty, price, disc, tax = (arrays[c].view(np.int64) for c in (C_QTY, C_PRICE, C_DISC, C_TAX))
         (la, ka), (lb, kb) = _short_strings(arrays[C_RFLAG]), _short_strings(arrays[C_STATUS])
         if int(la.max()) <= 4 and int(lb.max()) <= 4:   # both keys in one word: one sort
             combo, first, inv = np.unique(ka | (kb << np.uint64(32)), return_index=True, return_inverse=True)
@@ -107,15 +118,16 @@ def q1_scan(t):
             ua, ia = np.unique(ka, return_inverse=True)
             ub, ib = np.unique(kb, return_inverse=True)
             combo, first, inv = np.unique(ia * len(ub) + ib, return_index=True, return_inverse=True)
-        prod = price * disc                  # < 2^63 per row group: 65,536 x 1.1e7 x 10
+        disc_price = price * (100 - disc)    # < 2^63 per row group: 65,536 x 1.1e7 x 100
+        charge = disc_price * (100 + tax)    # ... x 108 = 7.8e15
         for g in np.argsort(first):
             m = inv == g
             r = int(first[g])
             key = (bytes(ka[r:r + 1].view(np.uint8)[:la[r]]), bytes(kb[r:r + 1].view(np.uint8)[:lb[r]]))
-            acc = groups.setdefault(key, [0, 0, 0, 0, 0])
-            for i, x in enumerate((qty, price, prod, disc)):
-                acc[i] += int(x[m].sum())
-            acc[4] += int(m.sum())
+            acc = groups.setdefault(key, [0, 0, 0, 0, 0, 0])
+            for i, x in enumerate((qty, price, disc_price, charge, disc)):
+                acc[i] += int(x[m].sum())    # the row group's sum in int64, the table's in Python integers
+            acc[5] += int(m.sum())
     return [(list(k), v) for k, v in groups.items()]
 
 
@@ -136,17 +148,20 @@ def q1_arm(fl, t, nrows, reps):
     med = [statistics.median(x) for x in times]
     bytes_res, _ = fl.Connection.resident_info(0)
     print("Q1: group by l_returnflag, l_linestatus of sum(l_quantity), sum(l_extendedprice), "
-          "sum(l_extendedprice * l_discount), sum(l_discount), count(*) where l_shipdate <= 1998-09-02")
+          "sum(l_extendedprice * (1 - l_discount)), sum(l_extendedprice * (1 - l_discount) * (1 + l_tax)), "
+          "sum(l_discount), count(*) where l_shipdate <= 1998-09-02")
     for k, v in want[0]:
         print(f"Q1: group {[x.decode() for x in k]}: {v}")
     for (name, _), m, x in zip(arms, med, times):
         print(f"Q1: {name} median {1e3 * m:9.3f} ms  ({nrows / m:.3e} rows/s)  all {' '.join(f'{1e3 * y:.3f}' for y in x)}")
     print(f"Q1: B / A = {med[1] / med[0]:.2f}   A / C = {med[0] / med[2]:.2f}  (resident image {bytes_res / 1e9:.3f} GB)")
+    for (name, _), x in zip(arms, times):
+        print(f"Q1: {name} spread: min {1e3 * min(x):.3f} ms, max {1e3 * max(x):.3f} ms over {len(x)} repetitions")
     # where B's time goes: its scan alone, the rows delivered and dropped
     alone = []
     for _ in range(max(1, reps)):
         t0 = time.perf_counter()
-        rows = sum(len(sel) for _, _, sel, _ in t.scan_filtered(Q1, cols=[C_QTY, C_PRICE, C_DISC, C_RFLAG, C_STATUS]))
+        rows = sum(len(sel) for _, _, sel, _ in t.scan_filtered(Q1, cols=Q1_COLS))
         alone.append(time.perf_counter() - t0)
     m = statistics.median(alone)
     print(f"Q1: (B's scan_filtered alone, {rows} rows delivered, no grouping: median {1e3 * m:9.3f} ms; "
