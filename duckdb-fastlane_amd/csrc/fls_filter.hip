@@ -52,6 +52,10 @@ __device__ __forceinline__ uint64_t load_uint(const uint8_t *p, uint32_t ob) {
     }
 }
 
+__device__ __forceinline__ bool in_range(const StrRange &r, uint64_t hp, uint32_t len) {
+    return hp >= r.host_lo && hp <= r.host_hi && len <= r.host_hi - hp;
+}
+
 // string_t record at p against the term's constant
 __device__ __forceinline__ int cmp_string(const DevTerm &t, const uint8_t *p, bool &bad) {
     const v4u rec = *(const v4u *)p;
@@ -69,12 +73,17 @@ __device__ __forceinline__ int cmp_string(const DevTerm &t, const uint8_t *p, bo
     if (len <= 12) {
         s = p + 4;
     } else {
+        // the batch heap (FSST rows) or the uploaded image (DICT rows); a
+        // pointer inside neither is reported and never dereferenced
         const uint64_t hp = ((uint64_t)rec.w << 32) | rec.z;
-        if (hp < t.host_lo || hp > t.host_hi || len > t.host_hi - hp) {
+        if (in_range(t.heap, hp, len)) {
+            s = (const uint8_t *)(hp + t.heap.dev_delta);
+        } else if (in_range(t.image, hp, len)) {
+            s = (const uint8_t *)(hp + t.image.dev_delta);
+        } else {
             bad = true;
             return 1;
         }
-        s = (const uint8_t *)(hp + t.dev_delta);
     }
     return cmp_bytes(s + 4, len - 4, t.str + 4, t.str_len - 4);
 }

@@ -69,20 +69,31 @@ __host__ __device__ inline int cmp_bytes(const uint8_t *a, uint32_t la, const ui
     return la < lb ? -1 : (la > lb ? 1 : 0);
 }
 
+// A host address range the long strings (> 12 bytes) of a string column point
+// into, and where its bytes are in HBM.  {0, 0, 0} holds no long string.
+struct StrRange {             // 24 B
+    uint64_t host_lo, host_hi;  // [host_lo, host_hi]: a string of len bytes at hp lies inside
+                                // when host_lo <= hp and hp + len <= host_hi
+    int64_t dev_delta;        // device address = host address + dev_delta
+};
+
 // One term of the filter as the kernel sees it, rebuilt per scan batch.
-struct DevTerm {              // 64 B
+struct DevTerm {              // 96 B
     const uint8_t *col;       // decoded column of the batch in HBM (row 0 of the batch)
     const uint8_t *str;       // FK_STR: constant bytes in HBM
     uint64_t value;           // constant: int64 / uint64 / double bits
-    uint64_t host_lo, host_hi;  // FK_STR: host range the long strings' pointers fall in
-    int64_t dev_delta;        // ... and device address = host address + dev_delta
+    // FK_STR: ENC_AUTO chooses DICT or FSST per chunk, so one batch can hold both;
+    // a long string's pointer is accepted from either place
+    StrRange heap;            // the batch's FSST heap of the column (FSST rows), or empty
+    StrRange image;           // the uploaded part of the file image (DICT rows)
     uint32_t str_len;
     uint8_t kind, op, ob;     // FilterKind, FilterOp, bytes per decoded value
     uint8_t end_clause;       // 1 on the last term of a clause
     const uint64_t *valid;    // the column's validity words for the batch rows (HBM), or
                               // NULL when no row of the batch is NULL
+    uint64_t pad;             // DevOut[] follows DevTerm[] in one buffer: keeps it 32-byte aligned
 };
-static_assert(sizeof(DevTerm) == 64, "DevTerm is 64 B");
+static_assert(sizeof(DevTerm) == 96, "DevTerm is 96 B");
 
 // One delivered column of a filtered batch: qualifying rows of src (HBM) are
 // compacted into dst (pinned host memory, written by the kernel over PCIe).

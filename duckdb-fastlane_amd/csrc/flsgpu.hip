@@ -1836,15 +1836,17 @@ int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
             dt.str = sl.d_fdesc.p + so;
             dt.str_len = (uint32_t)h.str.size();
             so += (h.str.size() + 15) & ~size_t(15);
-            if (sl.heap_bytes[h.col]) {  // FSST: long strings live in the batch heap
-                dt.host_lo = (uint64_t)(uintptr_t)sl.hb->h_heap[h.col].p;
-                dt.host_hi = dt.host_lo + sl.heap_bytes[h.col];
-                dt.dev_delta = (int64_t)((uintptr_t)sl.d_heap[h.col].p - (uintptr_t)sl.hb->h_heap[h.col].p);
-            } else {  // DICT: long strings point into the file image, uploaded as d_in
-                dt.host_lo = (uint64_t)(uintptr_t)(t->img + in_lo);
-                dt.host_hi = dt.host_lo + in_len;
-                dt.dev_delta = (int64_t)((uintptr_t)sl.in_dev - (uintptr_t)(t->img + in_lo));
+            // a batch can hold DICT and FSST chunks of the column (ENC_AUTO
+            // chooses per chunk): both ranges, each with its own device offset
+            if (sl.heap_bytes[h.col]) {  // FSST rows: long strings live in the batch heap
+                dt.heap.host_lo = (uint64_t)(uintptr_t)sl.hb->h_heap[h.col].p;
+                dt.heap.host_hi = dt.heap.host_lo + sl.heap_bytes[h.col];
+                dt.heap.dev_delta = (int64_t)((uintptr_t)sl.d_heap[h.col].p - (uintptr_t)sl.hb->h_heap[h.col].p);
             }
+            // DICT rows: long strings point into the file image, uploaded as d_in
+            dt.image.host_lo = (uint64_t)(uintptr_t)(t->img + in_lo);
+            dt.image.host_hi = dt.image.host_lo + in_len;
+            dt.image.dev_delta = (int64_t)((uintptr_t)sl.in_dev - (uintptr_t)(t->img + in_lo));
         }
     }
     memcpy(fd + nt * sizeof(DevTerm), outs.data(), no * sizeof(DevOut));

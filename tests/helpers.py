@@ -143,11 +143,14 @@ def _cmp(a, v):
     return (a > vv).astype(np.int8) - (a < vv).astype(np.int8)
 
 
-def filter_mask(cols: dict, terms, n: int) -> np.ndarray:
+def filter_mask(cols: dict, terms, n: int, valid: dict | None = None) -> np.ndarray:
     """Rows satisfying the conjunction of clauses; terms = (col, op, value[, clause])
-    as in Table.scan_filtered.  cols[c] = numpy values or list of bytes."""
+    as in Table.scan_filtered.  cols[c] = numpy values or list of bytes.
+    valid[c] = bool per row (False = NULL) for the columns that hold NULLs: a
+    NULL row satisfies IS NULL and no comparison."""
     ops = {"=": lambda c: c == 0, "!=": lambda c: c != 0, "<": lambda c: c < 0, "<=": lambda c: c <= 0,
            ">": lambda c: c > 0, ">=": lambda c: c >= 0}
+    valid = valid or {}
     clauses = {}
     for i, t in enumerate(terms):
         clauses.setdefault(t[3] if len(t) > 3 else 1000000 + i, []).append(t)
@@ -155,12 +158,75 @@ def filter_mask(cols: dict, terms, n: int) -> np.ndarray:
     for cl in clauses.values():
         acc = np.zeros(n, dtype=bool)
         for col, op, val, *_ in cl:
+            ok = valid.get(col)
             if op == "is_null":
+                if ok is not None:
+                    acc |= ~ok
                 continue
             if op == "is_not_null":
-                acc[:] = True
+                acc |= True if ok is None else ok
                 continue
             v = val.encode() if isinstance(val, str) else val
-            acc |= ops[op](_cmp(cols[col], v))
+            hit = ops[op](_cmp(cols[col], v))
+            acc |= hit if ok is None else hit & ok
         out &= acc
+    return out
+
+
+def rg_slice(cols: dict, rg: int, rows: int = 65536) -> dict:
+    """the rows of row group rg of every column (numpy array or list)"""
+    return {c: v[rg * rows:(rg + 1) * rows] for c, v in cols.items()}
+
+
+def check_filtered_scan(fl, t, cols, terms, deliver, rowgroup: int = 65536, valid: dict | None = None):
+    """Engine-level filtered scan vs the oracle, per row group: selection and
+    delivered values bit-exact; pruned row groups never delivered.  rowgroup:
+    the table's row-group size; valid: as filter_mask takes it (the delivered
+    values of NULL rows are placeholders and are not compared)."""
+    sch = t.schema()
+    expect_pruned = sum(not t.may_match(rg, terms) for rg in range(t.nrowgroups))
+    seen = set()
+    total = 0
+    for rg, first_row, sel, arrays in t.scan_filtered(terms, cols=deliver):
+        seen.add(rg)
+        part = rg_slice(cols, rg, rowgroup)
+        n = t.rowgroup_rows(rg)
+        want = np.nonzero(filter_mask(part, terms, n, rg_slice(valid, rg, rowgroup) if valid else None))[0]
+        assert np.array_equal(sel, want), (rg, len(sel), len(want))
+        total += len(sel)
+        for c in deliver:
+            ty = sch[c][1]
+            keep = np.ones(len(want), bool) if not valid or c not in valid else valid[c][rg * rowgroup + want]
+            if ty in fl.STRING_TYPES:
+                got = fl.string_t_decode(arrays[c])
+                assert len(got) == len(want), (sch[c][0], rg)
+                assert [g for g, k in zip(got, keep) if k] == [part[c][i] for i in want[keep]], (sch[c][0], rg)
+            else:
+                got = arrays[c].view(fl.NP_DTYPE[ty])
+                assert len(got) == len(want), (sch[c][0], rg)
+                assert np.array_equal(got[keep], part[c][want[keep]]), (sch[c][0], rg)
+    assert t.pruned == expect_pruned
+    assert len(seen) == t.nrowgroups - expect_pruned
+    return total
+
+
+def chunk_encodings(img: bytes) -> list:
+    """[row group][column] -> encoding id of the chunk (footer walk, fls_format.hpp)"""
+    import struct
+    foff, flen = struct.unpack_from("<QI", img, len(img) - 16)
+    p = foff
+    _, nc, _, nrg, _, _ = struct.unpack_from("<IIQIIQ", img, p)
+    p += 32
+    for _ in range(nc):
+        nl = struct.unpack_from("<H", img, p + 4)[0]
+        p += 6 + nl
+    out = []
+    for _ in range(nrg):
+        p += 4
+        row = []
+        for _ in range(nc):
+            off, _ln = struct.unpack_from("<QQ", img, p)
+            p += 16
+            row.append(img[off + 4])
+        out.append(row)
     return out

@@ -155,21 +155,10 @@ def _auto_columns(fl, n, rng):
 
 def _chunk_encodings(img: bytes):
     """{encoding id: count} over the file's chunks (footer walk, fls_format.hpp)"""
-    import struct
-    foff, flen = struct.unpack_from("<QI", img, len(img) - 16)
-    p = foff
-    _, nc, _, nrg, _, _ = struct.unpack_from("<IIQIIQ", img, p)
-    p += 32
-    for _ in range(nc):
-        nl = struct.unpack_from("<H", img, p + 4)[0]
-        p += 6 + nl
+    from helpers import chunk_encodings
     out = {}
-    for _ in range(nrg):
-        p += 4
-        for _ in range(nc):
-            off, _ln = struct.unpack_from("<QQ", img, p)
-            p += 16
-            e = img[off + 4]
+    for row in chunk_encodings(img):
+        for e in row:
             out[e] = out.get(e, 0) + 1
     return out
 

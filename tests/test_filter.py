@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 
 from ext_harness import Ext
-from helpers import filter_mask
+from helpers import check_filtered_scan, filter_mask, rg_slice
 
 SF = 0.1
 WL = "lineitem"
@@ -54,10 +54,6 @@ def ext(_built):
     e = Ext()
     yield e
     e.close()
-
-
-def rg_slice(cols, rg, rows=65536):
-    return {c: v[rg * rows:(rg + 1) * rows] for c, v in cols.items()}
 
 
 Q6 = [(C_SHIPDATE, ">=", DAY_1994), (C_SHIPDATE, "<", DAY_1995), (C_DISC, ">=", 5), (C_DISC, "<=", 7),
@@ -161,31 +157,6 @@ def test_read_fastlanes_unsupported_filter_shape_rows(fl, ext, gpu, tmpfile):
 
 
 # ---------------------------------------------------------------- GPU tests
-def check_filtered_scan(fl, t, cols, terms, deliver):
-    """Engine-level filtered scan vs the oracle, per row group: selection and
-    delivered values bit-exact; pruned row groups never delivered."""
-    sch = t.schema()
-    expect_pruned = sum(not t.may_match(rg, terms) for rg in range(t.nrowgroups))
-    seen = set()
-    total = 0
-    for rg, first_row, sel, arrays in t.scan_filtered(terms, cols=deliver):
-        seen.add(rg)
-        part = rg_slice(cols, rg)
-        n = t.rowgroup_rows(rg)
-        want = np.nonzero(filter_mask(part, terms, n))[0]
-        assert np.array_equal(sel, want), (rg, len(sel), len(want))
-        total += len(sel)
-        for c in deliver:
-            ty = sch[c][1]
-            if ty == fl.VARCHAR:
-                assert fl.string_t_decode(arrays[c]) == [part[c][i] for i in want], (sch[c][0], rg)
-            else:
-                assert np.array_equal(arrays[c].view(fl.NP_DTYPE[ty]), part[c][want]), (sch[c][0], rg)
-    assert t.pruned == expect_pruned
-    assert len(seen) == t.nrowgroups - expect_pruned
-    return total
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(PREDICATES))
 def test_gpu_filtered_scan_bit_exact(fl, gpu, lineitem, name):
