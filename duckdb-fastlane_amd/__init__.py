@@ -106,6 +106,13 @@ class GroupKey(C.Structure):
                 ("str", C.c_void_p), ("str_len", C.c_uint64)]
 
 
+class OrderKey(C.Structure):     # fls_order_key
+    _fields_ = [("col", C.c_uint32), ("desc", C.c_uint8), ("nulls_first", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+MAX_TOPN = 1024
+
+
 class DecodeStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("values", C.c_uint64), ("packed_bytes", C.c_uint64),
                 ("meta_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("launches", C.c_uint32),
@@ -166,6 +173,14 @@ _sig("fls_group_result_ngroups", C.c_uint64, _P)
 _sig("fls_group_result_key", C.c_int, _P, C.c_uint64, C.c_uint32, C.POINTER(GroupKey))
 _sig("fls_group_result_values", C.POINTER(AggregateValue), _P, C.c_uint64)
 _sig("fls_group_result_free", None, _P)
+_sig("fls_topn", C.c_int, _P, C.POINTER(OrderKey), C.c_uint32, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32,
+     C.POINTER(_P))
+_sig("fls_topn_pruned", C.c_int, _P, C.POINTER(OrderKey), C.c_uint32, C.c_uint32, C.c_uint32)
+_sig("fls_topn_result_nrows", C.c_uint64, _P)
+_sig("fls_topn_result_rows", C.POINTER(C.c_uint64), _P)
+_sig("fls_topn_result_column", C.c_int, _P, C.c_uint32, C.POINTER(_P), C.POINTER(C.POINTER(C.c_uint64)))
+_sig("fls_topn_result_times", C.c_int, _P, C.POINTER(C.c_double), C.POINTER(C.c_double))
+_sig("fls_topn_result_free", None, _P)
 _sig("fls_table_zonemap", C.c_int, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
      C.POINTER(C.c_uint32))
 _sig("fls_scan_dict_codes", C.c_int, _P, C.c_int)
@@ -890,6 +905,64 @@ class Table:
             return out
         finally:
             _lib.fls_group_result_free(res)
+
+    # -- ORDER BY key LIMIT k selected on the GPU
+    def topn_pruned(self, order_by: int, k: int, desc=False, nulls_first=False, rg_begin=0, rg_end=None) -> int:
+        """fls_topn_pruned (host only): the row groups topn() with these
+        arguments would not read under the filter currently set (set_filter)"""
+        if rg_end is None:
+            rg_end = self.nrowgroups
+        key = OrderKey(col=order_by, desc=int(bool(desc)), nulls_first=int(bool(nulls_first)))
+        return _check(_lib.fls_topn_pruned(self.h, C.byref(key), k, rg_begin, rg_end))
+
+    def topn(self, order_by: int, k: int, cols=None, filt=None, desc=False, nulls_first=False, rg_begin=0,
+             rg_end=None):
+        """The k best rows (k <= MAX_TOPN) ordered by column order_by, selected
+        on the GPU (fls_topn): ascending or desc, NULL keys last or
+        nulls_first, equal keys by row index; filt as scan_filtered takes it.
+        Returns (rows, values, valid): rows the winners' global row indices
+        (uint64) in result order; values[c] for each delivered column (cols,
+        None = all) a numpy array in NP_DTYPE or a list of bytes for VARCHAR /
+        BLOB, None for the others; valid[c] a bool array (False = NULL) or
+        None when every returned row is valid.  Everything is a copy.
+        self.topn_ms holds the call's (phase 1, phase 2) host-clock times."""
+        if rg_end is None:
+            rg_end = self.nrowgroups
+        key = OrderKey(col=order_by, desc=int(bool(desc)), nulls_first=int(bool(nulls_first)))
+        res = _P()
+        self.set_filter(filt)
+        try:
+            _check(_lib.fls_topn(self.h, C.byref(key), k, _mask(self, cols), rg_begin, rg_end, C.byref(res)))
+        finally:
+            _check(_lib.fls_scan_filter(self.h, None, 0))
+        try:
+            p1, p2 = C.c_double(), C.c_double()
+            _check(_lib.fls_topn_result_times(res, C.byref(p1), C.byref(p2)))
+            self.topn_ms = (p1.value, p2.value)   # the last call's phase 1 / phase 2, host clock
+            n = _lib.fls_topn_result_nrows(res)
+            rows = np.ctypeslib.as_array(_lib.fls_topn_result_rows(res), shape=(n,)).copy() if n else \
+                np.zeros(0, np.uint64)
+            sch = self.schema()
+            values, valid = [None] * len(sch), [None] * len(sch)
+            for c in (range(len(sch)) if cols is None else cols):
+                ty, ob = sch[c][1], sch[c][4]
+                pv, pw = _P(), C.POINTER(C.c_uint64)()
+                _check(_lib.fls_topn_result_column(res, c, C.byref(pv), C.byref(pw)))
+                raw = np.ctypeslib.as_array(C.cast(pv, C.POINTER(C.c_uint8)), shape=(n * ob,)).copy() if n else \
+                    np.zeros(0, np.uint8)
+                if pw and n:
+                    w = np.ctypeslib.as_array(pw, shape=((n + 63) // 64,))
+                    valid[c] = np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
+                if ty in STRING_TYPES:
+                    strs = string_t_decode(raw)
+                    if valid[c] is not None:
+                        strs = [s if ok else b"" for s, ok in zip(strs, valid[c])]
+                    values[c] = strs
+                else:
+                    values[c] = raw.view(NP_DTYPE[ty])
+            return rows, values, valid
+        finally:
+            _lib.fls_topn_result_free(res)
 
     # -- device-resident decode (bench)
     def device_upload(self, rg_begin=0, rg_end=None):

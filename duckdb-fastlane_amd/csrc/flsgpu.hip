@@ -41,6 +41,7 @@
 #include "fls_pinned.hpp"
 #include "fls_reader.hpp"
 #include "fls_resident.hpp"
+#include "fls_topn.hpp"
 
 using namespace fls;
 
@@ -385,6 +386,9 @@ struct HostBatch {
     // (fls_groupagg.hpp, group_rg_stride(naggs, g_nfsum, g_rg_vecs) bytes each)
     PinBuf<uint8_t> h_grp;
     uint32_t g_nfsum = 0, g_rg_vecs = 0;
+    // top-N scan: per row group of the batch its list of candidates
+    // (fls_topn.hpp, topn_stride(k) bytes each)
+    PinBuf<uint8_t> h_topn;
     HostBatch() = default;
     HostBatch(const HostBatch &) = delete;
     HostBatch &operator=(const HostBatch &) = delete;
@@ -431,6 +435,12 @@ struct Slot {                       // one batch of row groups in flight
     DevBuf<uint8_t> d_gdesc;
     DevBuf<uint8_t> d_gvec;         // stage 1: the vectors' groups
     DevBuf<uint8_t> d_grg;          // stage 2: the row groups' groups
+    // top-N batches (fls_topn)
+    PinBuf<uint32_t> h_tdesc;       // per row group its first vector and vector count
+    DevBuf<uint32_t> d_tdesc;
+    DevBuf<uint8_t> d_tvec;         // stage 1: the vectors' candidate lists
+    DevBuf<uint8_t> d_ttmp;         // stage 2: the other side of the merge tree's ping-pong
+    DevBuf<uint8_t> d_trg;          // stage 2: the row groups' candidate lists
 };
 
 // One GPU's scan pipeline: streams, the two device slots and the pinned
@@ -508,6 +518,10 @@ struct ScanCtx {
     // GROUP BY columns of a grouped aggregate scan (fls_aggregate_grouped;
     // empty: ungrouped): decoded like operands, VARCHAR keys as dictionary codes
     std::vector<uint32_t> keys;
+    // top-N scan (fls_topn; tk == 0: none): no column is delivered, each
+    // batch's candidate lists ride in its HostBatch
+    fls_order_key tkey = {};
+    uint32_t tk = 0;
     bool dict_codes = false;        // deliver DICT string chunks as codes + dictionary
     bool narrow = false;            // deliver integer columns narrowed to their row groups' ranges
     bool defer_records = false;     // FSST-as-lengths records built by fls_scan_build_records, not scan_acquire
@@ -539,7 +553,8 @@ struct ScanCtx {
 
 // Pinned bytes a host batch holds (its columns, FSST heaps, selection).
 size_t pinned_bytes(const HostBatch &b) {
-    size_t t = b.h_counts.n * sizeof(uint32_t) + b.h_sel.n * sizeof(uint32_t) + b.h_agg.n * sizeof(AggRec) + b.h_grp.n;
+    size_t t = b.h_counts.n * sizeof(uint32_t) + b.h_sel.n * sizeof(uint32_t) + b.h_agg.n * sizeof(AggRec) + b.h_grp.n +
+               b.h_topn.n;
     for (auto &x : b.h_out) t += x.n;
     for (auto &x : b.h_heap) t += x.n;
     return t;
@@ -549,7 +564,7 @@ size_t pinned_bytes(const ScanDev &d) {
     for (auto &b : d.batches) t += pinned_bytes(*b);
     for (auto &sl : d.slots)
         t += sl.h_chunks.n * sizeof(DevChunk) + sl.h_stage.n + sl.h_fdesc.n + sl.h_adesc.n * sizeof(DevAgg) +
-             sl.h_gdesc.n;
+             sl.h_gdesc.n + sl.h_tdesc.n * sizeof(uint32_t);
     return t;
 }
 
@@ -1533,6 +1548,72 @@ bool rowgroup_may_match(const fls_table *t, uint32_t rg, const std::vector<HostT
     return true;
 }
 
+// Is column c a possible ORDER BY key of fls_topn?
+bool topn_key_type(const ColumnMeta &c) {
+    return !type_is_string(c.type) && type_valid(c.type) && !(c.type == TY_DECIMAL && c.width > 18);
+}
+
+// Zone-map pruning of a top-N scan without a filter, for integer-like keys.
+// In key space (topn_key) a row group with a zone map and no NULL holds `rows`
+// records no worse than its worst bound; sorted by that bound, the row groups
+// reach k records at some bound T, and a row group whose best bound is
+// strictly worse than T cannot hold one of the k best.  Ties are kept, as are
+// row groups without a zone map (they guarantee nothing) and, under NULLS
+// FIRST, those with a NULL (NULLS LAST: a NULL is worse than T's record, so
+// the strict test on the values decides).  Returns the row groups dropped.
+uint32_t topn_prune(const fls_table *t, const fls_order_key &key, uint32_t k, std::vector<uint32_t> &rgs) {
+    const uint8_t ty = t->meta.cols[key.col].type;
+    if (k == 0 || type_is_float(ty) || !topn_key_type(t->meta.cols[key.col])) return 0;
+    const uint8_t kind = type_is_signed(ty) ? FK_INT : FK_UINT;
+    struct Bound {
+        uint64_t best, worst;
+        bool valid, has_null;
+    };
+    std::vector<Bound> b(rgs.size());
+    std::vector<std::pair<uint64_t, uint64_t>> sure;  // (worst bound, rows) of the row groups without a NULL
+    for (size_t i = 0; i < rgs.size(); ++i) {
+        const RowGroupMeta &r = t->meta.rgs[rgs[i]];
+        b[i] = Bound{0, 0, false, false};
+        if (r.zones.empty() || !(r.zones[key.col].flags & ZM_VALID)) continue;
+        const ZoneMap &z = r.zones[key.col];
+        const uint64_t a = topn_key(z.min, kind, key.desc != 0), c = topn_key(z.max, kind, key.desc != 0);
+        b[i] = Bound{std::min(a, c), std::max(a, c), true, (z.flags & (ZM_HAS_NULL | ZM_ALL_NULL)) != 0};
+        if (!b[i].has_null) sure.emplace_back(b[i].worst, r.nrows);
+    }
+    std::sort(sure.begin(), sure.end());
+    uint64_t have = 0, T = 0;
+    bool reached = false;
+    for (size_t i = 0; i < sure.size() && !reached; ++i) {
+        have += sure[i].second;
+        T = sure[i].first;
+        reached = have >= k;
+    }
+    if (!reached) return 0;
+    std::vector<uint32_t> keep;
+    for (size_t i = 0; i < rgs.size(); ++i) {
+        const bool drop = b[i].valid && b[i].best > T && !(b[i].has_null && key.nulls_first);
+        if (!drop) keep.push_back(rgs[i]);
+    }
+    const uint32_t dropped = (uint32_t)(rgs.size() - keep.size());
+    rgs.swap(keep);
+    return dropped;
+}
+
+// The row groups of [rg0, rg1) a scan reads, in order, and how many it skips:
+// those the filter's zone maps / dictionaries rule out, and for a top-N scan
+// without a filter those topn_prune drops.
+uint32_t select_rowgroups(const fls_table *t, const std::vector<HostTerm> &terms, const fls_order_key *order, uint32_t k,
+                          uint32_t rg0, uint32_t rg1, std::vector<uint32_t> &rgs) {
+    uint32_t pruned = 0;
+    rgs.clear();
+    for (uint32_t r = rg0; r < rg1; ++r) {
+        if (terms.empty() || rowgroup_may_match(t, r, terms)) rgs.push_back(r);
+        else pruned++;
+    }
+    if (order && terms.empty()) pruned += topn_prune(t, *order, k, rgs);
+    return pruned;
+}
+
 // The file's resident image on GPU dev (made on first use), or none: a table
 // not read from a file, FLS_SCAN_RESIDENT_MB=0, or no room in the GPU's image
 // budget (FLS_SCAN_RESIDENT_MB, default 65,536 MB, over every cached file)
@@ -1606,7 +1687,8 @@ std::shared_ptr<DevImage> resident_image(fls_table *t, int dev, uint32_t g, uint
 
 int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uint8_t *col_mask, uint32_t rg0,
                uint32_t rg1, const std::vector<HostTerm> *filter, const std::vector<HostAgg> *aggs = nullptr,
-               const std::vector<uint32_t> *keys = nullptr) {
+               const std::vector<uint32_t> *keys = nullptr, const fls_order_key *order = nullptr,
+               uint32_t topk = 0, const std::vector<uint32_t> *only = nullptr) {
     ProfTimer prof(PROF_SETUP);
     t->profiled = t->profiled || ScanProf::on();
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
@@ -1663,12 +1745,19 @@ int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uin
             string_key = string_key || type_is_string(t->meta.cols[c].type);
         }
     }
-    // row-group pruning on zone maps / dictionaries
-    s.rgs.clear();
-    s.pruned = 0;
-    for (uint32_t r = rg0; r < rg1; ++r) {
-        if (s.terms.empty() || rowgroup_may_match(t, r, s.terms)) s.rgs.push_back(r);
-        else s.pruned++;
+    // a top-N scan delivers nothing either and decodes the filter's columns and its key column
+    s.tk = order ? topk : 0;
+    s.tkey = order ? *order : fls_order_key{};
+    if (s.tk) {
+        s.dict_codes = s.narrow = s.defer_records = false;
+        s.dmask[s.tkey.col] = 1;
+    }
+    // row-group pruning on zone maps / dictionaries (a top-N scan without a
+    // filter: by the k-th bound of the key's zone maps)
+    s.pruned = select_rowgroups(t, s.terms, s.tk ? &s.tkey : nullptr, s.tk, rg0, rg1, s.rgs);
+    if (only) {  // a scan of listed row groups (ascending, inside the range): fls_topn's late materialisation
+        s.rgs = *only;
+        s.pruned = 0;
     }
     s.cur = 0;
     s.held = -1;
@@ -1772,6 +1861,7 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
         if (a.fn == AGG_SUM_PRODUCT) need[a.col2] = 1;
     }
     for (uint32_t c : s.keys) need[c] = 1;
+    if (s.tk) need[s.tkey.col] = 1;
     for (uint32_t c = 0; c < ncols; ++c) {
         bool any = false;
         for (uint32_t r = sl.rg0; need[c] && r < sl.rg0 + sl.nrg; ++r)
@@ -1857,7 +1947,7 @@ int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
     HIP_TRY(sl.d_counts.alloc(d.dev, hb.nvec));
     HIP_TRY(launch_filter((const DevTerm *)sl.d_fdesc.p, (uint32_t)nt, (uint32_t)rows, sl.d_mask.p, sl.d_counts.p,
                           d.err.p, sl.stream));
-    if (!s.aggs.empty()) return 0;  // an aggregate scan reduces under the mask: nothing is compacted or delivered
+    if (!s.aggs.empty() || s.tk) return 0;  // an aggregate / top-N scan reduces under the mask: nothing is compacted or delivered
     HIP_TRY(hb.h_counts.alloc(hb.nvec));
     HIP_TRY(hb.h_sel.alloc(std::max<uint64_t>(rows, 1)));
     HIP_TRY(launch_compact((const DevOut *)(sl.d_fdesc.p + nt * sizeof(DevTerm)), (uint32_t)no, sl.d_mask.p,
@@ -2010,6 +2100,57 @@ int enqueue_group_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint
                                    (const uint32_t *)(sl.d_gdesc.p + kMaxKeys * sizeof(DevKey)), sl.nrg, rg_vecs,
                                    sl.d_gvec.p, sl.d_grg.p, d.err.p, sl.stream));
     HIP_TRY(hipMemcpyAsync(hb.h_grp.p, sl.d_grg.p, (size_t)sl.nrg * rg_stride, hipMemcpyDeviceToHost, sl.stream));
+    return 0;
+}
+
+// The top-N counterpart: stage 1 leaves every vector's best k candidates in
+// sl.d_tvec, stage 2 merges the vectors of each row group pairwise (between
+// sl.d_tvec and sl.d_ttmp) into sl.d_trg, and
+// the row groups' lists are the batch's only D2H.
+int enqueue_topn(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
+    HostBatch &hb = *sl.hb;
+    const bool filtered = !s.terms.empty();
+    if (!filtered)  // (enqueue_filter staged the filter's and the key's validity together)
+        if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
+    const uint32_t c = s.tkey.col;
+    const uint8_t ty = t->meta.cols[c].type;
+    hb.nvec = (uint32_t)((rows + 1023) / 1024);
+    HIP_TRY(sl.h_tdesc.alloc(2ull * sl.nrg));
+    HIP_TRY(sl.d_tdesc.alloc(d.dev, 2ull * sl.nrg));
+    uint64_t vecs = 0;
+    uint32_t rg_vecs = 1;
+    for (uint32_t r = 0; r < sl.nrg; ++r) {
+        const RowGroupMeta &rg = t->meta.rgs[sl.rg0 + r];
+        uint32_t *rv = sl.h_tdesc.p + 2 * r;
+        rv[0] = (uint32_t)((rg.first_row - t->meta.rgs[sl.rg0].first_row) / kVectorSize);
+        rv[1] = (uint32_t)((rg.nrows + kVectorSize - 1) / kVectorSize);
+        vecs = std::max<uint64_t>(vecs, (uint64_t)rv[0] + rv[1]);
+        rg_vecs = std::max(rg_vecs, rv[1]);
+    }
+    if (rows > (1ull << 30)) return fail(FLS_ERR_LIMIT, "fls_topn: a batch of more than 2^30 rows");
+    if (vecs > hb.nvec) return fail(FLS_ERR_STATE, "internal: row groups of a batch past its %u vectors", hb.nvec);
+    const size_t stride = topn_stride(s.tk);
+    HIP_TRY(sl.d_tvec.alloc(d.dev, (size_t)hb.nvec * stride));
+    HIP_TRY(sl.d_ttmp.alloc(d.dev, (size_t)hb.nvec * stride));
+    HIP_TRY(sl.d_trg.alloc(d.dev, (size_t)sl.nrg * stride));
+    HIP_TRY(hb.h_topn.alloc((size_t)sl.nrg * stride));
+    DevTopn p;
+    memset(&p, 0, sizeof(p));
+    p.col = sl.d_out[c].p;
+    p.valid = sl.valid_staged[c] ? sl.d_valid[c].p : nullptr;
+    p.mask = filtered ? sl.d_mask.p : nullptr;
+    p.nrows = (uint32_t)rows;
+    p.k = s.tk;
+    p.ob = (uint8_t)out_bytes_of(t, c);
+    p.kind = type_is_float(ty) ? FK_FLOAT : type_is_signed(ty) ? FK_INT : FK_UINT;
+    p.desc = s.tkey.desc ? 1 : 0;
+    p.nulls_first = s.tkey.nulls_first ? 1 : 0;
+    HIP_TRY(hipMemcpyAsync(sl.d_tdesc.p, sl.h_tdesc.p, 2ull * sl.nrg * sizeof(uint32_t), hipMemcpyHostToDevice,
+                           sl.stream));
+    HIP_TRY(launch_topn_vectors(p, sl.d_tvec.p, sl.stream));
+    HIP_TRY(launch_topn_rowgroups(sl.d_tdesc.p, sl.nrg, rg_vecs, hb.nvec, s.tk, sl.d_tvec.p, sl.d_ttmp.p, sl.d_trg.p,
+                                  sl.stream));
+    HIP_TRY(hipMemcpyAsync(hb.h_topn.p, sl.d_trg.p, (size_t)sl.nrg * stride, hipMemcpyDeviceToHost, sl.stream));
     return 0;
 }
 
@@ -2333,6 +2474,9 @@ int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
         if (int rc = s.keys.empty() ? enqueue_aggregate(t, s, d, sl, rows, lo)
                                     : enqueue_group_aggregate(t, s, d, sl, rows, lo))
             return rc;
+    // 3c. top-N scan: select under the mask; the row groups' candidate lists are the batch's only D2H
+    if (s.tk)
+        if (int rc = enqueue_topn(t, s, d, sl, rows, lo)) return rc;
     // 3. D2H into pinned host columns (and string heaps)
     if (hb.pt[1]) HIP_TRY(hipEventRecord(hb.pt[1], sl.stream));
     hb.prof_d2h = 0;
@@ -2577,7 +2721,7 @@ int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
     out->ncols = ncols;
     out->nrows_scanned = out->nrows;
     out->sel = nullptr;
-    if (!s.terms.empty() && s.aggs.empty()) {
+    if (!s.terms.empty() && s.aggs.empty() && !s.tk) {
         batch_selection(t, s, *hb);
         const uint32_t i = rg - hb->rg0;
         out->nrows = hb->sel_off[i + 1] - hb->sel_off[i];
@@ -3468,6 +3612,226 @@ const fls_aggregate_value *fls_group_result_values(const fls_group_result *r, ui
 }
 
 void fls_group_result_free(fls_group_result *r) { delete r; }
+
+}  // extern "C"
+
+// The winners of fls_topn in result order: their global rows and, per
+// delivered column, their values (the scan's physical layout), validity words
+// and the bytes of their long strings -- all copies.
+struct fls_topn_result {
+    uint32_t ncols = 0;
+    std::vector<uint64_t> rows;
+    std::vector<uint8_t> delivered;               // per column
+    std::vector<std::vector<uint8_t>> values;     // per column: rows x out_bytes
+    std::vector<std::vector<uint64_t>> validity;  // per column: (rows + 63) / 64 words
+    std::vector<uint8_t> has_null;                // per column: a returned row is NULL
+    std::vector<std::unique_ptr<uint8_t[]>> heap; // strings over 12 bytes, one allocation each
+    double phase_ms[2] = {0, 0};                  // host clock: the selection scan, the late materialisation
+};
+
+namespace {
+
+// fls_topn's argument checks (no device work); FLS_ERR_ARG messages start "order key:".
+int check_topn(const fls_table *t, const fls_order_key *key, uint32_t k, const uint8_t *col_mask, uint32_t rg_begin,
+               uint32_t rg_end) {
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    if (key->col >= ncols) return fail(FLS_ERR_ARG, "order key: column %u out of range", key->col);
+    const ColumnMeta &cm = t->meta.cols[key->col];
+    if (type_is_string(cm.type))
+        return fail(FLS_ERR_ARG, "order key: a VARCHAR / BLOB column (%u) cannot be an ORDER BY key", key->col);
+    if (!topn_key_type(cm))
+        return fail(FLS_ERR_ARG, "order key: DECIMAL(%u) column %u is wider than 64 bits", (unsigned)cm.width, key->col);
+    if (col_mask) {
+        bool any = false;
+        for (uint32_t c = 0; c < ncols; ++c) any = any || col_mask[c];
+        if (!any) return fail(FLS_ERR_ARG, "order key: col_mask names no column to deliver");
+    }
+    if (rg_end > t->meta.rgs.size() || rg_begin > rg_end)
+        return fail(FLS_ERR_ARG, "order key: row-group range [%u,%u) out of bounds", rg_begin, rg_end);
+    if (k > kMaxTopN)
+        return fail(FLS_ERR_LIMIT, "fls_topn: k = %u is above %u (kMaxTopN); scan the columns (fls_scan_begin) and sort "
+                    "the rows instead", k, kMaxTopN);
+    for (uint32_t r = rg_begin; r < rg_end; ++r)
+        if (t->meta.rgs[r].nrows > (1u << 30))
+            return fail(FLS_ERR_LIMIT, "fls_topn: row group %u has more than 2^30 rows", r);
+    return 0;
+}
+
+struct TopnCand {
+    uint32_t rank;
+    uint64_t key;
+    uint64_t row;   // global
+    uint32_t rg, rg_row;
+};
+inline bool cand_less(const TopnCand &a, const TopnCand &b) {
+    if (a.rank != b.rank) return a.rank < b.rank;
+    if (a.key != b.key) return a.key < b.key;
+    return a.row < b.row;
+}
+
+// Phase 2 of fls_topn: the winners' values of the masked columns, copied out
+// of their row groups (ascending), decoded on the context and by the path
+// fls_materialize uses.
+int topn_gather(fls_table *t, const std::vector<TopnCand> &win, const uint8_t *col_mask, fls_topn_result &res) {
+    const uint32_t ncols = res.ncols;
+    const size_t n = win.size();
+    std::vector<uint32_t> order(n);
+    for (size_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return win[a].row < win[b].row; });
+    for (uint32_t c = 0; c < ncols; ++c) {
+        if (!res.delivered[c]) continue;
+        res.values[c].assign(n * (size_t)out_bytes_of(t, c), 0);
+        res.validity[c].assign(std::max<size_t>(1, (n + 63) / 64), ~0ull);
+    }
+    // one delivering scan of the winners' row groups on the materialize context: no filter, every row
+    // delivered at full width, the batches pipelined and sharded as in any scan
+    std::vector<uint32_t> rgs;
+    for (size_t j = 0; j < n; ++j)
+        if (rgs.empty() || rgs.back() != win[order[j]].rg) rgs.push_back(win[order[j]].rg);
+    ScanCtx &s = t->mat;
+    int rc = scan_setup(t, s, t->devices, col_mask, rgs.front(), rgs.back() + 1, nullptr, nullptr, nullptr, nullptr, 0, &rgs);
+    if (!rc) rc = scan_start(t, s);
+    if (rc) return rc;
+    size_t i = 0;
+    while (i < n) {
+        const uint32_t rg = win[order[i]].rg;
+        fls_rowgroup out;
+        rc = scan_next(t, s, &out);
+        if (rc < 0) return rc;
+        if (rc == 0 || out.rowgroup != rg)
+            return fail(FLS_ERR_STATE, "internal: the winners' scan did not deliver row group %u", rg);
+        for (; i < n && win[order[i]].rg == rg; ++i) {
+            const uint32_t dst = order[i], row = win[dst].rg_row;
+            if (row >= out.nrows) return fail(FLS_ERR_STATE, "internal: winner row %u past row group %u", row, rg);
+            for (uint32_t c = 0; c < ncols; ++c) {
+                if (!res.delivered[c]) continue;
+                if (!out.columns[c]) return fail(FLS_ERR_STATE, "internal: column %u of row group %u not decoded", c, rg);
+                const size_t ob = (size_t)out_bytes_of(t, c);
+                uint8_t *d = res.values[c].data() + dst * ob;
+                const uint64_t *vw = out.validity[c];
+                if (vw && !((vw[row >> 6] >> (row & 63)) & 1)) {  // NULL: the placeholder stays behind
+                    res.validity[c][dst >> 6] &= ~(1ull << (dst & 63));
+                    res.has_null[c] = 1;
+                    continue;
+                }
+                memcpy(d, (const uint8_t *)out.columns[c] + row * ob, ob);
+                if (!type_is_string(t->meta.cols[c].type)) continue;
+                uint32_t len;
+                memcpy(&len, d, 4);
+                if (len <= 12) continue;  // inline
+                const uint8_t *src;
+                memcpy(&src, d + 8, 8);
+                res.heap.emplace_back(new uint8_t[len]);
+                memcpy(res.heap.back().get(), src, len);
+                const uint8_t *own = res.heap.back().get();
+                memcpy(d + 8, &own, 8);
+            }
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fls_topn(fls_table *t, const fls_order_key *key, uint32_t k, const uint8_t *col_mask, uint32_t rg_begin,
+             uint32_t rg_end, fls_topn_result **out) {
+    if (!t || !key || !out) return fail(FLS_ERR_ARG, "fls_topn: NULL argument");
+    *out = nullptr;
+    if (int rc = check_topn(t, key, k, col_mask, rg_begin, rg_end)) return rc;
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    auto res = std::make_unique<fls_topn_result>();
+    res->ncols = ncols;
+    res->delivered.assign(ncols, 1);
+    if (col_mask)
+        for (uint32_t c = 0; c < ncols; ++c) res->delivered[c] = col_mask[c] ? 1 : 0;
+    res->values.resize(ncols);
+    res->validity.resize(ncols);
+    res->has_null.assign(ncols, 0);
+    std::vector<TopnCand> best;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (k > 0) {
+        // phase 1: the row groups' candidate lists, merged in row-group order
+        const std::vector<uint8_t> none(std::max(1u, ncols), 0);  // nothing is delivered
+        ScanCtx &s = t->scan;
+        int rc = scan_setup(t, s, t->devices, none.data(), rg_begin, rg_end, &t->filter, nullptr, nullptr, key, k);
+        if (!rc) rc = scan_start(t, s);
+        if (rc) return rc;
+        const size_t stride = topn_stride(k);
+        std::vector<TopnCand> inc, merged;
+        fls_rowgroup rg;
+        while ((rc = scan_next(t, s, &rg)) == 1) {
+            const HostBatch *hb = held_batch(s, rg.rowgroup);
+            if (!hb) return fail(FLS_ERR_STATE, "internal: top-N batch of row group %u not found", rg.rowgroup);
+            const uint8_t *base = hb->h_topn.p + (size_t)(rg.rowgroup - hb->rg0) * stride;
+            TopnHdr hdr;
+            memcpy(&hdr, base, sizeof(hdr));
+            const uint32_t rg_rows = t->meta.rgs[rg.rowgroup].nrows;
+            // a record's row counts from the batch's first row
+            const uint64_t rg_off = t->meta.rgs[rg.rowgroup].first_row - t->meta.rgs[hb->rg0].first_row;
+            if (hdr.count > k || hdr.count > rg_rows)  // never indexed with
+                return fail(FLS_ERR_FORMAT, "top-N: row group %u reports %u candidates (k = %u, %u rows)", rg.rowgroup,
+                            hdr.count, k, rg_rows);
+            const TopnRec *recs = (const TopnRec *)(base + sizeof(TopnHdr));
+            inc.clear();
+            for (uint32_t i = 0; i < hdr.count; ++i) {
+                const TopnRec &r = recs[i];
+                if (r.row < rg_off || r.row - rg_off >= rg_rows || r.rank > 1)
+                    return fail(FLS_ERR_FORMAT, "top-N: candidate %u of row group %u names batch row %u (its rows: %llu "
+                                "to %llu; rank %u)", i, rg.rowgroup, r.row, (unsigned long long)rg_off,
+                                (unsigned long long)(rg_off + rg_rows), r.rank);
+                const uint32_t rg_row = (uint32_t)(r.row - rg_off);
+                inc.push_back(TopnCand{r.rank, r.key, rg.first_row + rg_row, rg.rowgroup, rg_row});
+            }
+            if (!std::is_sorted(inc.begin(), inc.end(), cand_less))
+                return fail(FLS_ERR_FORMAT, "top-N: the candidates of row group %u are not in order", rg.rowgroup);
+            merged.resize(best.size() + inc.size());
+            std::merge(best.begin(), best.end(), inc.begin(), inc.end(), merged.begin(), cand_less);
+            if (merged.size() > k) merged.resize(k);
+            best.swap(merged);
+        }
+        if (rc < 0) return rc;
+    }
+    res->rows.reserve(best.size());
+    for (const TopnCand &c : best) res->rows.push_back(c.row);
+    const auto t1 = std::chrono::steady_clock::now();
+    // phase 2: late materialisation of the winners
+    if (!best.empty())
+        if (int rc = topn_gather(t, best, col_mask, *res)) return rc;
+    res->phase_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    res->phase_ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    *out = res.release();
+    return 0;
+}
+
+int fls_topn_pruned(const fls_table *t, const fls_order_key *key, uint32_t k, uint32_t rg_begin, uint32_t rg_end) {
+    if (!t || !key) return fail(FLS_ERR_ARG, "fls_topn_pruned: NULL argument");
+    if (int rc = check_topn(t, key, k, nullptr, rg_begin, rg_end)) return rc;
+    std::vector<uint32_t> rgs;
+    return (int)select_rowgroups(t, t->filter, key, k, rg_begin, rg_end, rgs);
+}
+
+uint64_t fls_topn_result_nrows(const fls_topn_result *r) { return r ? r->rows.size() : 0; }
+
+const uint64_t *fls_topn_result_rows(const fls_topn_result *r) { return r ? r->rows.data() : nullptr; }
+
+int fls_topn_result_column(const fls_topn_result *r, uint32_t col, const void **values, const uint64_t **validity) {
+    if (!r || col >= r->ncols || !r->delivered[col])
+        return fail(FLS_ERR_ARG, "fls_topn_result_column: column %u was not delivered", col);
+    if (values) *values = r->values[col].data();
+    if (validity) *validity = r->has_null[col] ? r->validity[col].data() : nullptr;
+    return 0;
+}
+
+int fls_topn_result_times(const fls_topn_result *r, double *phase1_ms, double *phase2_ms) {
+    if (!r) return fail(FLS_ERR_ARG, "fls_topn_result_times: NULL result");
+    if (phase1_ms) *phase1_ms = r->phase_ms[0];
+    if (phase2_ms) *phase2_ms = r->phase_ms[1];
+    return 0;
+}
+
+void fls_topn_result_free(fls_topn_result *r) { delete r; }
 
 int fls_scan_pruned(const fls_table *t) {
     if (!t) return fail(FLS_ERR_ARG, "fls_scan_pruned: NULL table");

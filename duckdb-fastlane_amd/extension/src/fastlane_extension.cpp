@@ -5,7 +5,8 @@
 // `fastlane_version()` (:32-42, used at examples/basic_usage.sql:8), the typed
 // GPU scan (here `read_fastlanes`, VARCHAR and LIST(VARCHAR)), the
 // .fls/.fastlane replacement scan, the COPY TO (FORMAT fls | fastlane)
-// writer, and `fastlanes_aggregate` (ungrouped aggregates reduced on the GPU).
+// writer, `fastlanes_aggregate` (aggregates reduced on the GPU) and
+// `fastlanes_topn` (ORDER BY one column LIMIT k selected on the GPU).
 #define DUCKDB_EXTENSION_MAIN
 
 #include "fastlane_extension.hpp"
@@ -14,6 +15,7 @@
 #include "gpu_devices.hpp"
 #include "scan_fastlanes.hpp"
 #include "table_function/fastlanes_aggregate.hpp"
+#include "table_function/fastlanes_topn.hpp"
 #include "table_function/read_fastlanes.hpp"
 #include "writer/copy_fastlanes.hpp"
 
@@ -45,6 +47,7 @@ void FastlaneExtension::Load(DuckDB &db) {
     ScanFastLanes::Register(*db.instance);
     ext_fastlane::RegisterReadFastlanes(*db.instance);
     ext_fastlane::RegisterFastlanesAggregate(*db.instance);
+    ext_fastlane::RegisterFastlanesTopn(*db.instance);
     ext_fastlane::RegisterFastlaneCopyFunction(*db.instance);
 }
 

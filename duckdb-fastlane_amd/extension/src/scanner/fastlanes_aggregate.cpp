@@ -52,12 +52,15 @@
 #include "duckdb/common/string_util.hpp"
 #include "duckdb/main/extension_util.hpp"
 #include "table_function/fastlanes_aggregate.hpp"
+#include "table_function/filter_text.hpp"
 #include "type_mapping.hpp"
 
 namespace duckdb {
 namespace ext_fastlane {
 
 namespace {
+
+using namespace filter_text;  // the schema, lexer, literal and filter parsers shared with fastlanes_topn
 
 struct AggTable {
     fls_table *table = nullptr;
@@ -88,39 +91,6 @@ struct AggGlobalState : public GlobalTableFunctionState {
     }
 };
 
-string Trim(const string &s) {
-    size_t a = 0, b = s.size();
-    while (a < b && isspace((unsigned char)s[a])) ++a;
-    while (b > a && isspace((unsigned char)s[b - 1])) --b;
-    return s.substr(a, b - a);
-}
-
-bool IsIdent(const string &s) {
-    if (s.empty() || !(isalpha((unsigned char)s[0]) || s[0] == '_')) return false;
-    for (char c : s)
-        if (!(isalnum((unsigned char)c) || c == '_')) return false;
-    return true;
-}
-
-struct Schema {
-    std::vector<fls_column_info> cols;
-    vector<string> names;
-    vector<LogicalType> types;
-    // exact name first, then case-insensitively (DuckDB's identifier matching)
-    int Find(string name) const {
-        if (name.size() >= 2 && name.front() == '"' && name.back() == '"') name = name.substr(1, name.size() - 2);
-        for (size_t c = 0; c < names.size(); ++c)
-            if (names[c] == name) return (int)c;
-        const string low = StringUtil::Lower(name);
-        for (size_t c = 0; c < names.size(); ++c)
-            if (StringUtil::Lower(names[c]) == low) return (int)c;
-        return -1;
-    }
-};
-
-bool IsString(uint8_t t) { return t == FLS_VARCHAR || t == FLS_BLOB; }
-bool IsFloat(uint8_t t) { return t == FLS_FLOAT || t == FLS_DOUBLE; }
-
 int ColumnOf(const Schema &sch, const string &name, const string &item) {
     const string n = Trim(name);
     if (!(IsIdent(n) || (n.size() >= 2 && n.front() == '"' && n.back() == '"')))
@@ -128,181 +98,6 @@ int ColumnOf(const Schema &sch, const string &name, const string &item) {
     const int c = sch.Find(n);
     if (c < 0) throw BinderException("fastlanes_aggregate: column \"" + n + "\" of aggregate \"" + item + "\" not found");
     return c;
-}
-
-// ---- the filter text ------------------------------------------------------
-struct Token {
-    enum Kind { END, WORD, NUMBER, STRING, OP } kind = END;
-    string text;   // WORD as written, NUMBER digits, STRING unescaped contents, OP the operator
-};
-
-struct Lexer {
-    const string &s;
-    size_t pos = 0;
-    explicit Lexer(const string &text) : s(text) {}
-    Token Next() {
-        while (pos < s.size() && isspace((unsigned char)s[pos])) ++pos;
-        Token t;
-        if (pos >= s.size()) return t;
-        const char c = s[pos];
-        if (isalpha((unsigned char)c) || c == '_') {
-            const size_t a = pos;
-            while (pos < s.size() && (isalnum((unsigned char)s[pos]) || s[pos] == '_')) ++pos;
-            t.kind = Token::WORD;
-            t.text = s.substr(a, pos - a);
-            return t;
-        }
-        if (c == '"') {
-            const size_t e = s.find('"', pos + 1);
-            if (e == string::npos) throw BinderException("fastlanes_aggregate: unterminated identifier in filter \"" + s + "\"");
-            t.kind = Token::WORD;
-            t.text = s.substr(pos, e + 1 - pos);
-            pos = e + 1;
-            return t;
-        }
-        if (c == '\'') {
-            t.kind = Token::STRING;
-            for (++pos;; ++pos) {
-                if (pos >= s.size()) throw BinderException("fastlanes_aggregate: unterminated string in filter \"" + s + "\"");
-                if (s[pos] == '\'') {
-                    if (pos + 1 < s.size() && s[pos + 1] == '\'') {
-                        t.text += '\'';
-                        ++pos;
-                        continue;
-                    }
-                    ++pos;
-                    return t;
-                }
-                t.text += s[pos];
-            }
-        }
-        if (isdigit((unsigned char)c) || c == '.' || ((c == '-' || c == '+') && pos + 1 < s.size() &&
-                                                      (isdigit((unsigned char)s[pos + 1]) || s[pos + 1] == '.'))) {
-            const size_t a = pos++;
-            while (pos < s.size() && (isalnum((unsigned char)s[pos]) || s[pos] == '.' ||
-                                      ((s[pos] == '-' || s[pos] == '+') && (s[pos - 1] == 'e' || s[pos - 1] == 'E'))))
-                ++pos;
-            t.kind = Token::NUMBER;
-            t.text = s.substr(a, pos - a);
-            return t;
-        }
-        for (const char *op : {"<>", "!=", "<=", ">=", "=", "<", ">"})
-            if (s.compare(pos, strlen(op), op) == 0) {
-                t.kind = Token::OP;
-                t.text = op;
-                pos += strlen(op);
-                return t;
-            }
-        throw BinderException("fastlanes_aggregate: cannot parse \"" + s.substr(pos, 1) + "\" in filter \"" + s + "\"");
-    }
-};
-
-int64_t DaysFromCivil(int64_t y, unsigned m, unsigned d) {
-    y -= m <= 2;
-    const int64_t era = (y >= 0 ? y : y - 399) / 400;
-    const unsigned yoe = (unsigned)(y - era * 400);
-    const unsigned doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1;
-    const unsigned doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
-    return era * 146097 + (int64_t)doe - 719468;
-}
-
-bool AllDigits(const string &s) {
-    if (s.empty()) return false;
-    for (char c : s)
-        if (!isdigit((unsigned char)c)) return false;
-    return true;
-}
-
-// the literal of a comparison in the column's physical type (fls_predicate.value / str)
-void SetLiteral(const Schema &sch, int col, Lexer &lex, Token lit, const string &filter, fls_predicate &p,
-                std::deque<string> &strs, const char *where = "filter") {
-    const fls_column_info &ci = sch.cols[col];
-    const string cname = sch.names[col];
-    bool date_kw = false;
-    if (lit.kind == Token::WORD && StringUtil::Lower(lit.text) == "date") {
-        date_kw = true;
-        lit = lex.Next();
-        if (lit.kind != Token::STRING)
-            throw BinderException(string("fastlanes_aggregate: DATE needs a 'YYYY-MM-DD' string in ") + where + " \"" + filter + "\"");
-    }
-    auto bad = [&](const char *want) {
-        return BinderException("fastlanes_aggregate: \"" + (lit.kind == Token::STRING ? "'" + lit.text + "'" : lit.text) +
-                               "\" is not " + want + " for " + sch.types[col].ToString() + " column \"" + cname +
-                               "\" in " + where + " \"" + filter + "\"");
-    };
-    if (lit.kind == Token::END || lit.kind == Token::OP)
-        throw BinderException("fastlanes_aggregate: a literal is missing after column \"" + cname + "\" in " + where + " \"" +
-                              filter + "\"");
-    if (date_kw != (ci.type == FLS_DATE)) throw bad(ci.type == FLS_DATE ? "a DATE 'YYYY-MM-DD' literal" : "a literal");
-    switch (ci.type) {
-    case FLS_DATE: {
-        int y = 0, n = 0;
-        unsigned m = 0, d = 0;
-        if (sscanf(lit.text.c_str(), "%d-%u-%u%n", &y, &m, &d, &n) != 3 || (size_t)n != lit.text.size() || m < 1 ||
-            m > 12 || d < 1 || d > 31)
-            throw bad("a DATE 'YYYY-MM-DD' literal");
-        p.value = (uint64_t)DaysFromCivil(y, m, d);
-        return;
-    }
-    case FLS_VARCHAR: case FLS_BLOB:
-        if (lit.kind != Token::STRING) throw bad("a quoted string");
-        strs.push_back(lit.text);
-        p.str = strs.back().data();
-        p.str_len = strs.back().size();
-        return;
-    case FLS_FLOAT: case FLS_DOUBLE: {
-        if (lit.kind == Token::STRING) throw bad("a number");
-        char *end = nullptr;
-        const double d = std::strtod(lit.text.c_str(), &end);
-        if (end == lit.text.c_str() || *end) throw bad("a number");
-        if (ci.type == FLS_FLOAT) {
-            const float f = (float)d;
-            uint32_t b;
-            memcpy(&b, &f, 4);
-            p.value = b;
-        } else {
-            memcpy(&p.value, &d, 8);
-        }
-        return;
-    }
-    case FLS_BOOLEAN:
-        if (lit.kind == Token::WORD && (StringUtil::Lower(lit.text) == "true" || StringUtil::Lower(lit.text) == "false")) {
-            p.value = StringUtil::Lower(lit.text) == "true";
-            return;
-        }
-        if (lit.kind != Token::NUMBER || (lit.text != "0" && lit.text != "1")) throw bad("true, false, 0 or 1");
-        p.value = lit.text == "1";
-        return;
-    default: break;
-    }
-    // integers and DECIMAL: exact decimal text -> (scaled) integer
-    if (lit.kind != Token::NUMBER) throw bad("a number");
-    string t = lit.text;
-    const bool neg = t[0] == '-';
-    if (t[0] == '-' || t[0] == '+') t = t.substr(1);
-    const size_t dot = t.find('.');
-    string ip = dot == string::npos ? t : t.substr(0, dot), fp = dot == string::npos ? "" : t.substr(dot + 1);
-    if ((!ip.empty() && !AllDigits(ip)) || (!fp.empty() && !AllDigits(fp)) || (ip.empty() && fp.empty()))
-        throw bad("a number");
-    while (!fp.empty() && fp.back() == '0') fp.pop_back();
-    const unsigned scale = ci.type == FLS_DECIMAL ? ci.scale : 0;
-    if (fp.size() > scale)
-        throw bad(ci.type == FLS_DECIMAL ? "exactly representable (too many fractional digits)" : "an integer");
-    fp.resize(scale, '0');
-    const string digits = ip + fp;
-    const bool is_unsigned = ci.type >= FLS_UINT8 && ci.type <= FLS_UINT64;
-    unsigned __int128 v = 0;
-    for (char c : digits) {
-        v = v * 10 + (unsigned)(c - '0');
-        if (v > ((unsigned __int128)1 << 64)) throw bad("in range");
-    }
-    if (is_unsigned) {
-        if ((neg && v != 0) || v > UINT64_MAX) throw bad("in range");
-        p.value = (uint64_t)v;
-    } else {
-        if (v > ((unsigned __int128)1 << 63) - (neg ? 0 : 1)) throw bad("in range");
-        p.value = neg ? (uint64_t)0 - (uint64_t)v : (uint64_t)v;
-    }
 }
 
 // ---- the aggregate list ---------------------------------------------------
@@ -460,55 +255,6 @@ void ParseAggregate(const Schema &sch, const string &item, fls_aggregate_spec &s
     }
 }
 
-void ParseFilter(const Schema &sch, const string &filter, std::vector<fls_predicate> &preds, std::deque<string> &strs) {
-    if (Trim(filter).empty()) return;
-    Lexer lex(filter);
-    uint32_t clause = 0;
-    for (;;) {
-        Token col = lex.Next();
-        if (col.kind != Token::WORD)
-            throw BinderException("fastlanes_aggregate: a column name is expected at \"" + col.text + "\" in filter \"" +
-                                  filter + "\"");
-        const int c = sch.Find(col.text);
-        if (c < 0)
-            throw BinderException("fastlanes_aggregate: column \"" + col.text + "\" of filter \"" + filter + "\" not found");
-        fls_predicate p;
-        memset(&p, 0, sizeof(p));
-        p.col = (uint32_t)c;
-        p.clause = clause++;
-        Token op = lex.Next();
-        if (op.kind == Token::WORD && StringUtil::Lower(op.text) == "is") {
-            Token t = lex.Next();
-            bool is_not = false;
-            if (t.kind == Token::WORD && StringUtil::Lower(t.text) == "not") {
-                is_not = true;
-                t = lex.Next();
-            }
-            if (t.kind != Token::WORD || StringUtil::Lower(t.text) != "null")
-                throw BinderException("fastlanes_aggregate: IS [NOT] NULL is expected after \"" + col.text +
-                                      "\" in filter \"" + filter + "\"");
-            p.op = is_not ? FLS_CMP_IS_NOT_NULL : FLS_CMP_IS_NULL;
-        } else if (op.kind == Token::OP) {
-            p.op = op.text == "="                        ? FLS_CMP_EQ
-                   : (op.text == "!=" || op.text == "<>") ? FLS_CMP_NE
-                   : op.text == "<"                      ? FLS_CMP_LT
-                   : op.text == "<="                     ? FLS_CMP_LE
-                   : op.text == ">"                      ? FLS_CMP_GT
-                                                         : FLS_CMP_GE;
-            SetLiteral(sch, c, lex, lex.Next(), filter, p, strs);
-        } else {
-            throw BinderException("fastlanes_aggregate: a comparison or IS [NOT] NULL is expected after \"" + col.text +
-                                  "\" in filter \"" + filter + "\"");
-        }
-        preds.push_back(p);
-        Token next = lex.Next();
-        if (next.kind == Token::END) return;
-        if (next.kind != Token::WORD || StringUtil::Lower(next.text) != "and")
-            throw BinderException("fastlanes_aggregate: only AND joins filter terms, found \"" + next.text +
-                                  "\" in filter \"" + filter + "\"");
-    }
-}
-
 // the group_by text: 1 to 4 column names separated by commas
 void ParseGroupBy(const Schema &sch, const string &list, std::vector<uint32_t> &keys, vector<string> &names,
                   vector<LogicalType> &types) {
@@ -551,13 +297,7 @@ unique_ptr<FunctionData> AggBind(ClientContext &, TableFunctionBindInput &input,
     if (!conn || fls_read_fls(conn, bind->file.c_str(), &bind->table->table) != 0)
         throw BinderException("Failed to open FastLanes file: " + bind->file);
     Schema sch;
-    const uint32_t n = fls_table_ncols(bind->table->table);
-    sch.cols.resize(n);
-    for (uint32_t c = 0; c < n; ++c) {
-        fls_table_column(bind->table->table, c, &sch.cols[c]);
-        sch.types.push_back(TypeMapping::FastLanesToDuckDB(sch.cols[c].type, sch.cols[c].width, sch.cols[c].scale));
-        sch.names.emplace_back(sch.cols[c].name);
-    }
+    sch.Load(bind->table->table);
     // the aggregate list: items separated by commas outside parentheses
     const string list = input.inputs[1].GetValue<string>();
     vector<string> items;

@@ -51,7 +51,7 @@ typedef enum fls_status {
     FLS_ERR_STATE = -5,     /* call out of order (e.g. decode before upload) */
     FLS_ERR_NOMEM = -6,
     FLS_ERR_CONFIG = -7,    /* an FLS_* tuning variable names a kernel this build does not hold */
-    FLS_ERR_LIMIT = -8      /* a documented capacity was exceeded (fls_aggregate_grouped) */
+    FLS_ERR_LIMIT = -8      /* a documented capacity was exceeded (fls_aggregate_grouped, fls_topn) */
 } fls_status;
 
 typedef struct fls_connection fls_connection;
@@ -314,6 +314,64 @@ int fls_group_result_key(const fls_group_result *r, uint64_t group, uint32_t key
 /* the group's n values in the aggregates' order; NULL out of range */
 const fls_aggregate_value *fls_group_result_values(const fls_group_result *r, uint64_t group);
 void fls_group_result_free(fls_group_result *r);
+/* ORDER BY key [DESC] LIMIT k selected on the GPU: the k best rows of row
+ * groups [rg_begin, rg_end) under the filter set by fls_scan_filter, ordered
+ * by one key column; their global row indices and the values of the columns
+ * col_mask names (NULL = every column; the key column only if masked in).
+ * Phase 1 decodes the filter's columns and the key column into HBM, keeps the
+ * best k candidates of every 1024-row vector and merges them per row group
+ * (csrc/fls_topn.hip); one list of at most k 16-byte records per row group
+ * crosses PCIe, and the call merges the row groups' lists.  Phase 2 decodes
+ * the masked columns of the at most k row groups that hold a winner, as
+ * fls_materialize does, and copies the winners' values out; the call is
+ * synchronous.  Key column: INT*, UINT*, BOOLEAN, DATE, DECIMAL of at most 64
+ * bits, FLOAT or DOUBLE in any encoding.  Integers order by value, floats in
+ * the filter's order (every NaN above +inf, -0 equal to +0); desc inverts the
+ * order.  NULL keys come after every value in both directions (DuckDB's
+ * default, NULLS LAST) or, with nulls_first, before every value; the
+ * placeholder stored at a NULL is never read.  Equal keys (-0 / +0 and NaN /
+ * NaN included) are ordered by ascending global row index, so the result is
+ * unique, and identical whatever the batch size, slot count or number of
+ * GPUs.  A row takes part when the filter selects it.  Fewer than k such rows
+ * give that many; none at all (an empty table or range, every row group
+ * pruned, k = 0) give an empty result with no device work.  k <= 1024 (one
+ * vector's worth): a larger k is FLS_ERR_LIMIT before any device work; scan
+ * and sort instead.  Without a filter and with an integer-like key, row
+ * groups whose zone map puts every value strictly behind the k-th bound the
+ * other row groups' zone maps guarantee are not read (ties and row groups
+ * without a zone map are; a row group with a NULL is kept under nulls_first);
+ * they count in fls_scan_pruned.  FLOAT / DOUBLE keys and filtered calls are
+ * not pruned this way (a filter prunes as in fls_scan_begin).
+ * FLS_ERR_ARG before any device work, the message starting "order key:": a
+ * key column out of range, a VARCHAR / BLOB key, a DECIMAL wider than 64
+ * bits, a col_mask that names no column, rg_begin / rg_end out of bounds.
+ * The call replaces a scan in progress on the table, as fls_aggregate does,
+ * and the table stays usable after any error.  Not in the reference.
+ * *out is owned by the caller (fls_topn_result_free) and stays valid after
+ * the table is closed: values, validity and strings are copies. */
+typedef struct fls_order_key { uint32_t col; uint8_t desc; uint8_t nulls_first; uint8_t pad[2]; } fls_order_key;
+typedef struct fls_topn_result fls_topn_result;
+int fls_topn(fls_table *t, const fls_order_key *key, uint32_t k, const uint8_t *col_mask,
+             uint32_t rg_begin, uint32_t rg_end, fls_topn_result **out);
+uint64_t fls_topn_result_nrows(const fls_topn_result *r);
+/* global row indices, in result order */
+const uint64_t *fls_topn_result_rows(const fls_topn_result *r);
+/* nrows values of a delivered column in the scan's physical layout
+ * (fls_column_info.out_bytes per row; VARCHAR / BLOB as 16-byte string_t
+ * records whose long strings point into bytes the result owns) and their
+ * validity in DuckDB's layout, or NULL when every returned row is valid.
+ * FLS_ERR_ARG for a column that was not delivered. */
+int fls_topn_result_column(const fls_topn_result *r, uint32_t col, const void **values,
+                           const uint64_t **validity);
+/* Host-clock milliseconds the call spent in phase 1 (the selection scan and
+ * the merge) and in phase 2 (the late materialisation); either may be NULL. */
+int fls_topn_result_times(const fls_topn_result *r, double *phase1_ms, double *phase2_ms);
+void fls_topn_result_free(fls_topn_result *r);
+/* Host only, of the fls_rowgroup_may_match family: the number of row groups of
+ * [rg_begin, rg_end) an fls_topn call with this key and k would not read
+ * under the filter currently set (what fls_scan_pruned reports after it);
+ * fls_topn's argument checks apply. */
+int fls_topn_pruned(const fls_table *t, const fls_order_key *key, uint32_t k, uint32_t rg_begin, uint32_t rg_end);
 /* Zone map of column col in row group rg: 1 and *min / *max (int64, uint64
  * or double bits by column type, see fls_predicate.value; FLOAT widened to
  * double) and *flags (1 valid, 2 / 4 has / all NaN, 8 / 16 has / all NULL;
