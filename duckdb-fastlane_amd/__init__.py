@@ -70,7 +70,19 @@ class Predicate(C.Structure):
 # fls_cmp (include/flsgpu.h)
 EQ, NE, LT, LE, GT, GE, IS_NULL, IS_NOT_NULL = range(8)
 OPS = {"=": EQ, "==": EQ, "!=": NE, "<>": NE, "<": LT, "<=": LE, ">": GT, ">=": GE,
-       "is_null": IS_NULL, "is_not_null": IS_NOT_NULL, "false": 8}
+       "is_null": IS_NULL, "is_not_null": IS_NOT_NULL, "false": 8,
+       "in_set": 9, "not_in_set": 10}
+IN_SET, NOT_IN_SET = 9, 10
+# fls_keyset_form
+KEYSET_AUTO, KEYSET_BITMAP, KEYSET_HASH = 0, 1, 2
+MAX_KEYSET_KEYS = 1 << 28          # kMaxKeysetKeys
+KEYSET_HASH_MUL = 0x9E3779B97F4A7C15
+
+
+class KeySetInfo(C.Structure):     # fls_keyset_info_t
+    _fields_ = [("count", C.c_uint64), ("form", C.c_uint32), ("kind", C.c_uint32), ("device_bytes", C.c_uint64),
+                ("capacity", C.c_uint64), ("max_probe", C.c_uint32), ("pad", C.c_uint32), ("min", C.c_uint64),
+                ("max", C.c_uint64), ("empty", C.c_uint64)]
 
 
 # fls_agg_fn / fls_aggregate_spec / fls_aggregate_value (include/flsgpu.h)
@@ -164,6 +176,10 @@ _sig("fls_scan_acquire", C.c_int, _P, C.POINTER(RowGroup))
 _sig("fls_scan_release", C.c_int, _P, C.c_uint32)
 _sig("fls_scan_filter", C.c_int, _P, C.POINTER(Predicate), C.c_uint32)
 _sig("fls_scan_pruned", C.c_int, _P)
+_sig("fls_keyset_create", C.c_int, _P, _P, C.c_uint64, C.c_int, C.c_int, C.POINTER(_P))
+_sig("fls_keyset_free", None, _P)
+_sig("fls_keyset_info", C.c_int, _P, C.POINTER(KeySetInfo))
+_sig("fls_keyset_contains", C.c_int, _P, C.c_uint64)
 _sig("fls_aggregate", C.c_int, _P, C.POINTER(AggregateSpec), C.c_uint32, C.c_uint32, C.c_uint32,
      C.POINTER(AggregateValue))
 _sig("fls_aggregate_exprs", C.c_int, _P, C.POINTER(AggExpr), C.c_uint32)
@@ -537,10 +553,68 @@ class Connection:
         _check(_lib.fls_read_fls_image(self.h, buf, len(buf), 1, C.byref(h)))
         return Table(h.value, self)
 
+    def keyset(self, values, signed: bool = True, form: int = KEYSET_AUTO) -> "KeySet":
+        """A key set for (col, "in_set" / "not_in_set", keyset) filter terms
+        (fls_keyset_create): values are integers of the probed column's
+        physical type (DATE days, DECIMAL scaled), signed its order (False for
+        UINT* and BOOLEAN columns), form 0 auto / 1 bitmap / 2 hash table.
+        Built on the host; no GPU is needed.  TypeError for anything but
+        integers (a float is never truncated into a key)."""
+        # (a list goes value by value: numpy would turn Python integers of mixed sign past 2^63 into floats)
+        a = values if isinstance(values, np.ndarray) else np.asarray(list(values), dtype=object)
+        if a.size == 0:
+            a = np.zeros(0, np.uint64)
+        elif a.dtype == object:
+            vals = list(a.ravel())
+            for v in vals:
+                if not isinstance(v, (int, np.integer, np.bool_)):
+                    raise TypeError(f"keyset: {v!r} is not an integer")
+            a = np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in vals], dtype=np.uint64)
+        elif a.dtype.kind not in "iub":
+            raise TypeError(f"keyset: values of dtype {a.dtype} are not integers")
+        elif a.dtype.kind == "i":
+            a = a.astype(np.int64).view(np.uint64)    # sign-extended patterns
+        else:
+            a = a.astype(np.uint64)
+        a = np.ascontiguousarray(a.ravel())
+        h = _P()
+        _check(_lib.fls_keyset_create(self.h, a.ctypes.data if a.size else None, a.size, 0 if signed else 1, form,
+                                      C.byref(h)))
+        return KeySet(h.value, self)
+
     def close(self):
         if self.h:
             _lib.fls_disconnect(self.h)
             self.h = None
+
+
+class KeySet:
+    """fls_keyset: the build side of a semi-join.  The handle is a token the
+    library looks up; a closed set in a filter is refused, never dereferenced."""
+
+    def __init__(self, h, conn):
+        self.h, self.conn = h, conn
+
+    @property
+    def info(self) -> KeySetInfo:
+        out = KeySetInfo()
+        _check(_lib.fls_keyset_info(self.h, C.byref(out)))
+        return out
+
+    def contains(self, key: int) -> bool:
+        """Host probe of the image a scan uploads."""
+        return _check(_lib.fls_keyset_contains(self.h, int(key) & 0xFFFFFFFFFFFFFFFF)) == 1
+
+    def close(self):
+        if self.h:
+            _lib.fls_keyset_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _mask(t: "Table", cols) -> C.Array | None:
@@ -748,7 +822,8 @@ class Table:
     def _preds(self, filt):
         """filt: list of (col, op, value[, clause]); op a fls_cmp or one of OPS;
         value int (integers, DATE days, DECIMAL scaled), float (FLOAT/DOUBLE) or
-        str/bytes (VARCHAR).  Terms without a clause get their own clause."""
+        str/bytes (VARCHAR), or a KeySet for "in_set" / "not_in_set" (a clause
+        of its own).  Terms without a clause get their own clause."""
         sch = self.schema()
         arr = (Predicate * max(1, len(filt)))()
         keep = []
@@ -759,7 +834,10 @@ class Table:
             p.clause = term[3] if len(term) > 3 else 1000000 + i
             p.op = OPS[op] if isinstance(op, str) else op
             ty = sch[col][1] if 0 <= col < len(sch) else None
-            if val is None or ty is None:
+            if p.op in (IN_SET, NOT_IN_SET):
+                p.value = (val.h or 0) if isinstance(val, KeySet) else int(val)   # the set's handle
+                keep.append(val)
+            elif val is None or ty is None:
                 pass
             elif ty in STRING_TYPES:
                 b = val.encode() if isinstance(val, str) else bytes(val)
@@ -819,6 +897,21 @@ class Table:
                 yield out.rowgroup, out.first_row, sel, self._rg_arrays(out)
         finally:
             _check(_lib.fls_scan_filter(self.h, None, 0))
+
+    def keyset(self, col: int, filt=None, form: int = KEYSET_AUTO) -> "KeySet":
+        """The build side of a semi-join: the key set of the non-NULL values
+        of one integer-like column (INT*, UINT*, BOOLEAN, DATE, DECIMAL of at
+        most 64 bits) over the rows filt selects (a filtered scan of that
+        column).  Use it as (col, "in_set", keyset) on this or another table
+        of the same connection."""
+        ci = self.column(col)
+        if ci.type in STRING_TYPES or ci.type in (FLOAT, DOUBLE) or ci.out_bytes > 8:
+            raise ValueError(f"keyset: column {col} ({TYPE_NAMES.get(ci.type, ci.type)}) is not integer-like")
+        terms = list(filt or []) + [(col, "is_not_null", None)]
+        parts = [arrs[col].view(NP_DTYPE[ci.type]) for _, _, _, arrs in self.scan_filtered(terms, cols=[col])]
+        vals = np.concatenate(parts) if parts else np.zeros(0, NP_DTYPE[ci.type])
+        signed = ci.type in (INT8, INT16, INT32, INT64, DATE, DECIMAL)
+        return self.conn.keyset(np.unique(vals), signed=signed, form=form)
 
     # -- aggregates reduced on the GPU
     def set_aggregate_exprs(self, exprs):

@@ -16,6 +16,10 @@
 // number and -0 == 0, strings compared bytewise (memcmp order, a proper
 // prefix sorts first).  NULL rows (the chunks' validity bitmaps) satisfy
 // IS NULL and no comparison, as in DuckDB; IS NOT NULL holds for the rest.
+// A term may also test membership in a key set (`column IN set` / `NOT IN
+// set`, fls_keyset.hpp): such a term is a clause of its own, pruned against
+// the zone maps by the set's sorted keys and evaluated by a kernel of its own
+// (fls_keyset.hip) that narrows the mask the filter kernel wrote.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,7 +35,10 @@ enum FilterKind : uint8_t {
 };
 enum FilterOp : uint8_t {
     OP_EQ = 0, OP_NE = 1, OP_LT = 2, OP_LE = 3, OP_GT = 4, OP_GE = 5, OP_IS_NULL = 6, OP_IS_NOT_NULL = 7,
-    OP_FALSE = 8  // no row (col <op> NULL)
+    OP_FALSE = 8,  // no row (col <op> NULL)
+    // key-set membership (fls_keyset.hpp): a clause of its own, evaluated by
+    // keyset_kernel after filter_kernel, never by eval_term
+    OP_IN_SET = 9, OP_NOT_IN_SET = 10
 };
 
 __host__ __device__ inline bool op_holds(uint8_t op, int c) {
@@ -118,6 +125,31 @@ hipError_t launch_filter(const DevTerm *d_terms, uint32_t nterms, uint32_t nrows
 // their row group of rg_rows rows, into sel) in row order.
 hipError_t launch_compact(const DevOut *d_outs, uint32_t nouts, const uint64_t *d_mask, const uint32_t *d_counts,
                           uint32_t nrows, uint32_t rg_rows, uint32_t *sel, hipStream_t stream);
+
+// One key-set term (OP_IN_SET / OP_NOT_IN_SET) as keyset_kernel sees it,
+// rebuilt per scan batch; the set's image (fls_keyset.hpp) lives in HBM with
+// the set.  A row stays selected when its value is valid and in the set
+// (negate: valid and not in it).
+struct DevSetTerm {           // 64 B
+    const uint8_t *col;       // decoded column of the batch in HBM (row 0 of the batch)
+    const uint64_t *valid;    // as DevTerm::valid
+    const uint64_t *table;    // bitmap words or hash slots
+    uint64_t min, span;       // bitmap: bit (value - min) for value - min <= span
+    uint64_t empty;           // hash: the empty slot's sentinel
+    uint32_t cap_log2;        // hash: log2 of the capacity
+    uint32_t max_probe;       // hash: slots a lookup examines at most
+    uint8_t form;             // KS_BITMAP / KS_HASH
+    uint8_t ob, sign;         // bytes per decoded value; values sign-extend to 64 bits
+    uint8_t negate;           // NOT IN
+    uint8_t pad[4];
+};
+static_assert(sizeof(DevSetTerm) == 64, "DevSetTerm is 64 B");
+// a key-set descriptor no sound set produces (the probe loop itself is bounded)
+enum : uint32_t { KERR_KEYSET = 512 };
+// Narrows the mask and recomputes the counts launch_filter wrote for the same
+// nrows rows (fls_keyset.hip).
+hipError_t launch_keyset(const DevSetTerm *d_terms, uint32_t nterms, uint32_t nrows, uint64_t *d_mask,
+                         uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
 
 // Narrowed delivery (fls_scan_narrow): an integer column of a batch whose
 // values, per row group, lie in [base, base + 2^(8 nw)) crosses PCIe as the

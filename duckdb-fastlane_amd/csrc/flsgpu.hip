@@ -38,6 +38,7 @@
 #include "fls_filter.hpp"
 #include "fls_format.hpp"
 #include "fls_groupagg.hpp"
+#include "fls_keyset.hpp"
 #include "fls_pinned.hpp"
 #include "fls_reader.hpp"
 #include "fls_resident.hpp"
@@ -421,6 +422,8 @@ struct Slot {                       // one batch of row groups in flight
     DevBuf<uint32_t> d_counts;      // selected rows per vector
     PinBuf<uint8_t> h_fdesc;        // DevTerm[] + DevOut[] + constant strings
     DevBuf<uint8_t> d_fdesc;
+    PinBuf<DevSetTerm> h_sdesc;     // the filter's key-set terms
+    DevBuf<DevSetTerm> d_sdesc;
     std::vector<DevBuf<uint64_t>> d_valid;  // per filtered / aggregated column with a NULL: batch validity words
     std::vector<uint8_t> valid_staged;      // per column: d_valid[c] holds this batch's words (stage_validity)
     std::vector<DevBuf<uint8_t>> d_narrow;  // per narrowed column: its narrowed copy
@@ -488,13 +491,64 @@ struct ScanDev {
     }
 };
 
+// A key set (fls_keyset_create): the host image and its copies in HBM, one
+// per GPU, made by the first scan that probes the set there.  Filters hold a
+// reference, so the handle may be freed while a filter or a scan uses the set;
+// the copies go with the last reference.  They are not resident images and do
+// not count against FLS_SCAN_RESIDENT_MB.
+struct KeySet {
+    KeysetImage img;
+    const fls_connection *conn = nullptr;
+    std::mutex mu;
+    std::vector<std::unique_ptr<DevBuf<uint64_t>>> copies;
+    // the image on GPU dev (the current device), uploaded on first use
+    hipError_t device_image(int dev, const uint64_t **out) {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto &c : copies)
+            if (c->dev == dev) {
+                *out = c->p;
+                return hipSuccess;
+            }
+        auto b = std::make_unique<DevBuf<uint64_t>>();
+        hipError_t e = b->alloc(dev, img.words.size());
+        // a synchronous copy: complete before any kernel enqueued after this call
+        if (e == hipSuccess && !img.words.empty())
+            e = hipMemcpy(b->p, img.words.data(), img.bytes(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return e;
+        *out = b->p;
+        copies.push_back(std::move(b));
+        return hipSuccess;
+    }
+};
+
+// Live key sets by handle.  A handle is a counter value, never an address:
+// a stale or foreign fls_predicate.value is looked up here and refused
+// without being dereferenced.
+struct KeySetRegistry {
+    std::mutex mu;
+    uint64_t next = 1;
+    std::unordered_map<uint64_t, std::shared_ptr<KeySet>> live;
+    static uint64_t handle_of(uint64_t id) { return (id << 4) | 0x5; }
+    std::shared_ptr<KeySet> find(uint64_t handle) {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = live.find(handle);
+        return it == live.end() ? nullptr : it->second;
+    }
+};
+KeySetRegistry &keyset_registry() {
+    static auto *r = new KeySetRegistry();
+    return *r;
+}
+
 // One term of a pushed-down filter (fls_scan_filter), host side.
 struct HostTerm {
     uint32_t col = 0, clause = 0;
     uint8_t op = 0, kind = 0;
     uint64_t value = 0;             // comparison domain: int64 / uint64 / double bits
     std::string str;
+    std::shared_ptr<KeySet> set;    // OP_IN_SET / OP_NOT_IN_SET
 };
+inline bool is_set_op(uint8_t op) { return op == OP_IN_SET || op == OP_NOT_IN_SET; }
 
 // One aggregate of fls_aggregate, host side.
 struct HostAgg {
@@ -1498,6 +1552,13 @@ bool term_may_match(const fls_table *t, uint32_t rg, const HostTerm &h) {
     if (h.op == OP_IS_NULL) return chunk_has_validity(ch.hdr);
     if (h.op == OP_IS_NOT_NULL) return !all_null;
     if (all_null) return false;  // no valid row to compare
+    if (h.op == OP_NOT_IN_SET) return true;
+    if (h.op == OP_IN_SET) {
+        // a key inside the zone map's range (exact on a sorted column); the empty set matches nowhere
+        if (h.set->img.keys.empty()) return false;
+        if (r.zones.empty() || !(r.zones[h.col].flags & ZM_VALID)) return true;
+        return keyset_any_in_range(h.set->img, r.zones[h.col].min, r.zones[h.col].max);
+    }
     if (h.kind == FK_STR) {
         if (ch.hdr.enc != ENC_DICT) return true;  // FSST: no statistics
         const uint8_t *aux = t->img + ch.off + ch.hdr.aux_off;
@@ -1719,7 +1780,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uin
     s.defer_records = filter != nullptr && t->defer_records;
     s.dmask = s.mask;
     for (auto &h : s.terms)
-        if (h.op < OP_IS_NULL) s.dmask[h.col] = 1;
+        if (h.op < OP_IS_NULL || is_set_op(h.op)) s.dmask[h.col] = 1;
     s.aggs.clear();
     if (aggs) {
         // an aggregate scan delivers nothing and decodes the filter's columns
@@ -1901,17 +1962,43 @@ int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
     }
     if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
     const std::vector<uint8_t> &need = sl.valid_staged;
-    const size_t nt = s.terms.size(), no = outs.size();
+    // key-set terms (each a clause of its own) go to keyset_kernel, the rest
+    // to filter_kernel, which with no term left writes the row < nrows mask
+    std::vector<const HostTerm *> ord, sets;
+    for (auto &h : s.terms) (is_set_op(h.op) ? sets : ord).push_back(&h);
+    const size_t nt = ord.size(), no = outs.size(), ns = sets.size();
     size_t str_bytes = 0;
-    for (auto &h : s.terms) str_bytes += (h.str.size() + 15) & ~size_t(15);
+    for (auto *h : ord) str_bytes += (h->str.size() + 15) & ~size_t(15);
     const size_t bytes = nt * sizeof(DevTerm) + no * sizeof(DevOut) + str_bytes;
     HIP_TRY(sl.h_fdesc.alloc(bytes));
     HIP_TRY(sl.d_fdesc.alloc(d.dev, bytes));
     uint8_t *fd = sl.h_fdesc.p;
     DevTerm *terms = (DevTerm *)fd;
     size_t so = nt * sizeof(DevTerm) + no * sizeof(DevOut);
+    if (ns) {
+        HIP_TRY(sl.h_sdesc.alloc(ns));
+        HIP_TRY(sl.d_sdesc.alloc(d.dev, ns));
+    }
+    for (size_t i = 0; i < ns; ++i) {
+        const HostTerm &h = *sets[i];
+        const KeysetImage &ki = h.set->img;
+        DevSetTerm &ds = sl.h_sdesc.p[i];
+        memset(&ds, 0, sizeof(ds));
+        ds.col = sl.d_out[h.col].p;
+        ds.valid = need[h.col] ? sl.d_valid[h.col].p : nullptr;
+        HIP_TRY(h.set->device_image(d.dev, &ds.table));
+        ds.min = ki.min;
+        ds.span = ki.span;
+        ds.empty = ki.empty;
+        ds.cap_log2 = ki.cap_log2;
+        ds.max_probe = ki.max_probe;
+        ds.form = (uint8_t)ki.form;
+        ds.ob = (uint8_t)out_bytes_of(t, h.col);
+        ds.sign = ki.is_signed ? 1 : 0;
+        ds.negate = h.op == OP_NOT_IN_SET ? 1 : 0;
+    }
     for (size_t i = 0; i < nt; ++i) {
-        const HostTerm &h = s.terms[i];
+        const HostTerm &h = *ord[i];
         DevTerm &dt = terms[i];
         memset(&dt, 0, sizeof(dt));
         dt.col = sl.d_out[h.col].p;
@@ -1919,7 +2006,7 @@ int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
         dt.kind = h.kind;
         dt.op = h.op;
         dt.ob = (uint8_t)out_bytes_of(t, h.col);
-        dt.end_clause = (i + 1 == nt || s.terms[i + 1].clause != h.clause) ? 1 : 0;
+        dt.end_clause = (i + 1 == nt || ord[i + 1]->clause != h.clause) ? 1 : 0;
         dt.valid = need[h.col] ? sl.d_valid[h.col].p : nullptr;
         if (h.kind == FK_STR) {
             memcpy(fd + so, h.str.data(), h.str.size());
@@ -1947,6 +2034,11 @@ int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
     HIP_TRY(sl.d_counts.alloc(d.dev, hb.nvec));
     HIP_TRY(launch_filter((const DevTerm *)sl.d_fdesc.p, (uint32_t)nt, (uint32_t)rows, sl.d_mask.p, sl.d_counts.p,
                           d.err.p, sl.stream));
+    if (ns) {
+        HIP_TRY(hipMemcpyAsync(sl.d_sdesc.p, sl.h_sdesc.p, ns * sizeof(DevSetTerm), hipMemcpyHostToDevice, sl.stream));
+        HIP_TRY(launch_keyset(sl.d_sdesc.p, (uint32_t)ns, (uint32_t)rows, sl.d_mask.p, sl.d_counts.p, d.err.p,
+                              sl.stream));
+    }
     if (!s.aggs.empty() || s.tk) return 0;  // an aggregate / top-N scan reduces under the mask: nothing is compacted or delivered
     HIP_TRY(hb.h_counts.alloc(hb.nvec));
     HIP_TRY(hb.h_sel.alloc(std::max<uint64_t>(rows, 1)));
@@ -2688,6 +2780,7 @@ int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
         }
         const uint32_t err = *(volatile const uint32_t *)hb->h_err.p;
         if (err & KERR_FILTER_STR) return fail(FLS_ERR_FORMAT, "filter: string outside its batch heap (flags 0x%x)", err);
+        if (err & KERR_KEYSET) return fail(FLS_ERR_FORMAT, "filter: damaged key-set descriptor (flags 0x%x)", err);
         if (err & KERR_NARROW)
             return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a narrowed column (flags 0x%x)", err);
         if (err & KERR_LDS_BASE) return fail(FLS_ERR_DEVICE, "FSST kernel: dynamic LDS not at address 0 (flags 0x%x)", err);
@@ -2849,13 +2942,34 @@ int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std::vector
     if (n && !p) return fail(FLS_ERR_ARG, "fls_scan_filter: NULL predicates");
     for (uint32_t i = 0; i < n; ++i) {
         if (p[i].col >= t->meta.cols.size()) return fail(FLS_ERR_ARG, "filter column %u out of range", p[i].col);
-        if (p[i].op > FLS_CMP_FALSE) return fail(FLS_ERR_ARG, "filter operator %u unknown", p[i].op);
+        if (p[i].op > FLS_CMP_NOT_IN_SET) return fail(FLS_ERR_ARG, "filter operator %u unknown", p[i].op);
         HostTerm h;
         h.col = p[i].col;
         h.clause = p[i].clause;
         h.op = p[i].op;
         const uint8_t ty = t->meta.cols[h.col].type;
-        if (type_is_string(ty)) {
+        if (is_set_op(h.op)) {
+            const ColumnMeta &cm = t->meta.cols[h.col];
+            if (type_is_string(ty) || type_is_float(ty) || !type_valid(ty))
+                return fail(FLS_ERR_ARG, "filter term %u: a key set cannot be probed with a VARCHAR / BLOB / FLOAT / "
+                            "DOUBLE column (%u)", i, h.col);
+            if (ty == TY_DECIMAL && cm.width > 18)
+                return fail(FLS_ERR_ARG, "filter term %u: a key set cannot be probed with a DECIMAL wider than 64 bits "
+                            "(column %u)", i, h.col);
+            h.set = keyset_registry().find(p[i].value);
+            if (!h.set)
+                return fail(FLS_ERR_ARG, "filter term %u: value 0x%llx is not a live key set", i,
+                            (unsigned long long)p[i].value);
+            if (h.set->img.is_signed != type_is_signed(ty))
+                return fail(FLS_ERR_ARG, "filter term %u: the key set's kind is %s, column %u is %s", i,
+                            h.set->img.is_signed ? "signed" : "unsigned", h.col,
+                            type_is_signed(ty) ? "signed" : "unsigned");
+            for (uint32_t j = 0; j < n; ++j)
+                if (j != i && p[j].clause == p[i].clause)
+                    return fail(FLS_ERR_ARG, "filter term %u: a key-set term shares clause %u with term %u (a set "
+                                "term is a clause of its own)", i, p[i].clause, j);
+            h.kind = type_is_signed(ty) ? FK_INT : FK_UINT;
+        } else if (type_is_string(ty)) {
             h.kind = FK_STR;
             if (p[i].str_len && !p[i].str) return fail(FLS_ERR_ARG, "filter on column %u: NULL string", h.col);
             if (p[i].str_len > 0xFFFFFFFFull) return fail(FLS_ERR_ARG, "filter string too long");
@@ -2968,7 +3082,83 @@ int fls_connect(const int *devices, int ndevices, fls_connection **out) {
     return 0;
 }
 
-void fls_disconnect(fls_connection *conn) { delete conn; }
+void fls_disconnect(fls_connection *conn) {
+    if (conn) {  // the connection's key sets go with it (a filter or scan still using one keeps it alive)
+        KeySetRegistry &R = keyset_registry();
+        std::vector<std::shared_ptr<KeySet>> dead;  // released outside the lock
+        std::lock_guard<std::mutex> lk(R.mu);
+        for (auto it = R.live.begin(); it != R.live.end();) {
+            if (it->second->conn == conn) {
+                dead.push_back(std::move(it->second));
+                it = R.live.erase(it);
+            } else {
+                ++it;
+            }
+        }
+    }
+    delete conn;
+}
+
+int fls_keyset_create(fls_connection *conn, const uint64_t *keys, uint64_t n, int kind, int form, fls_keyset **out) {
+    if (!conn || !out) return fail(FLS_ERR_ARG, "fls_keyset_create: NULL argument");
+    if (kind != FLS_KEYSET_SIGNED && kind != FLS_KEYSET_UNSIGNED)
+        return fail(FLS_ERR_ARG, "fls_keyset_create: kind %d (0 signed, 1 unsigned)", kind);
+    if (form < 0 || form > 2) return fail(FLS_ERR_ARG, "fls_keyset_create: form %d (0 auto, 1 bitmap, 2 hash)", form);
+    if (n > kMaxKeysetKeys)  // before keys is read
+        return fail(FLS_ERR_LIMIT, "fls_keyset_create: %llu keys (at most %llu, kMaxKeysetKeys)", (unsigned long long)n,
+                    (unsigned long long)kMaxKeysetKeys);
+    if (n && !keys) return fail(FLS_ERR_ARG, "fls_keyset_create: NULL keys");
+    auto ks = std::make_shared<KeySet>();
+    ks->conn = conn;
+    int rc;
+    try {
+        rc = keyset_build(keys, n, kind == FLS_KEYSET_SIGNED, (uint32_t)form, ks->img);
+    } catch (const std::bad_alloc &) {
+        return fail(FLS_ERR_NOMEM, "fls_keyset_create: out of memory");
+    }
+    if (rc == KS_TOO_WIDE)
+        return fail(FLS_ERR_LIMIT, "fls_keyset_create: a bitmap over [min, max] would cover more than 2^32 values");
+    if (rc != KS_OK) return fail(FLS_ERR_ARG, "fls_keyset_create: cannot build the set (%d)", rc);
+    KeySetRegistry &R = keyset_registry();
+    std::lock_guard<std::mutex> lk(R.mu);
+    const uint64_t h = KeySetRegistry::handle_of(R.next++);
+    R.live[h] = std::move(ks);
+    *out = (fls_keyset *)(uintptr_t)h;
+    return 0;
+}
+
+void fls_keyset_free(fls_keyset *set) {
+    KeySetRegistry &R = keyset_registry();
+    std::shared_ptr<KeySet> dead;  // released outside the lock
+    std::lock_guard<std::mutex> lk(R.mu);
+    auto it = R.live.find((uint64_t)(uintptr_t)set);
+    if (it == R.live.end()) return;
+    dead = std::move(it->second);
+    R.live.erase(it);
+}
+
+int fls_keyset_info(const fls_keyset *set, fls_keyset_info_t *info) {
+    auto ks = keyset_registry().find((uint64_t)(uintptr_t)set);
+    if (!ks || !info) return fail(FLS_ERR_ARG, "fls_keyset_info: not a live key set");
+    const KeysetImage &k = ks->img;
+    memset(info, 0, sizeof(*info));
+    info->count = k.keys.size();
+    info->form = k.form;
+    info->kind = k.is_signed ? FLS_KEYSET_SIGNED : FLS_KEYSET_UNSIGNED;
+    info->device_bytes = k.bytes();
+    info->capacity = k.capacity();
+    info->max_probe = k.max_probe;
+    info->min = k.min;
+    info->max = k.max;
+    info->empty = k.empty;
+    return 0;
+}
+
+int fls_keyset_contains(const fls_keyset *set, uint64_t key) {
+    auto ks = keyset_registry().find((uint64_t)(uintptr_t)set);
+    if (!ks) return fail(FLS_ERR_ARG, "fls_keyset_contains: not a live key set");
+    return keyset_contains(ks->img, key) ? 1 : 0;
+}
 
 int fls_release_device_memory(int device, uint64_t *freed_bytes) {
     const uint64_t b = release_idle_images(device < 0 ? -1 : device);

@@ -10,7 +10,12 @@
 //           `column IS [NOT] NULL`.  Literals by column type: integers,
 //           decimal numbers the column's scale represents exactly,
 //           DATE 'YYYY-MM-DD', floats, single-quoted strings ('' escapes a
-//           quote).  No OR, no parentheses.
+//           quote).  `column [NOT] IN (literal, ...)` is a term too: on an
+//           integer-like column the list becomes one key-set term
+//           (fls_keyset_create, FLS_CMP_IN_SET / FLS_CMP_NOT_IN_SET), on
+//           VARCHAR / FLOAT / DOUBLE EQ terms of one clause (NOT IN: NE terms,
+//           a clause each); NULL in the list follows SQL.  No OR, no other
+//           parentheses.
 //
 // Everything unparsable, unknown or ill-typed is a BinderException that starts
 // with the calling function's name (`who`) and quotes the offending text.
@@ -79,8 +84,8 @@ inline bool IsString(uint8_t t) { return t == FLS_VARCHAR || t == FLS_BLOB; }
 inline bool IsFloat(uint8_t t) { return t == FLS_FLOAT || t == FLS_DOUBLE; }
 
 struct Token {
-    enum Kind { END, WORD, NUMBER, STRING, OP } kind = END;
-    string text;   // WORD as written, NUMBER digits, STRING unescaped contents, OP the operator
+    enum Kind { END, WORD, NUMBER, STRING, OP, PUNCT } kind = END;
+    string text;   // WORD as written, NUMBER digits, STRING unescaped contents, OP the operator, PUNCT ( ) or ,
 };
 
 struct Lexer {
@@ -134,6 +139,12 @@ struct Lexer {
             t.text = s.substr(a, pos - a);
             return t;
         }
+        if (c == '(' || c == ')' || c == ',') {  // the brackets and commas of an IN list
+            t.kind = Token::PUNCT;
+            t.text = string(1, c);
+            ++pos;
+            return t;
+        }
         for (const char *op : {"<>", "!=", "<=", ">=", "=", "<", ">"})
             if (s.compare(pos, strlen(op), op) == 0) {
                 t.kind = Token::OP;
@@ -179,7 +190,7 @@ inline void SetLiteral(const Schema &sch, int col, Lexer &lex, Token lit, const 
                                "\" is not " + want + " for " + sch.types[col].ToString() + " column \"" + cname +
                                "\" in " + where + " \"" + filter + "\"");
     };
-    if (lit.kind == Token::END || lit.kind == Token::OP)
+    if (lit.kind == Token::END || lit.kind == Token::OP || lit.kind == Token::PUNCT)
         throw BinderException(who + ": a literal is missing after column \"" + cname + "\" in " + where + " \"" +
                               filter + "\"");
     if (date_kw != (ci.type == FLS_DATE)) throw bad(ci.type == FLS_DATE ? "a DATE 'YYYY-MM-DD' literal" : "a literal");
@@ -254,8 +265,99 @@ inline void SetLiteral(const Schema &sch, int col, Lexer &lex, Token lit, const 
     }
 }
 
+// The key sets a filter's IN lists became (fls_keyset_create): freed with the
+// bind data that owns the predicates.
+struct KeySets {
+    std::vector<fls_keyset *> sets;
+    KeySets() = default;
+    KeySets(const KeySets &) = delete;
+    KeySets &operator=(const KeySets &) = delete;
+    ~KeySets() {
+        for (fls_keyset *s : sets) fls_keyset_free(s);
+    }
+};
+
+// `column [NOT] IN (literal, ...)`, the lexer past IN.  On an integer-like
+// column (everything but VARCHAR / BLOB / FLOAT / DOUBLE) the list becomes one
+// key-set term; on the others IN becomes EQ terms of one clause and NOT IN NE
+// terms of a clause each.  SQL's NULL rules: a NULL in an IN list is ignored
+// (a list of nothing else matches no row), a NULL in a NOT IN list leaves no
+// row (FLS_CMP_FALSE).
+inline void ParseInList(const Schema &sch, int c, bool negate, Lexer &lex, const string &filter, uint32_t &clause,
+                        std::vector<fls_predicate> &preds, std::deque<string> &strs, fls_connection *conn,
+                        KeySets *sets) {
+    const string &who = lex.who;
+    const string what = negate ? "NOT IN" : "IN";
+    Token t = lex.Next();
+    if (t.kind != Token::PUNCT || t.text != "(")
+        throw BinderException(who + ": \"(\" is expected after " + what + " in filter \"" + filter + "\"");
+    std::vector<fls_predicate> lits;
+    bool has_null = false;
+    t = lex.Next();
+    if (t.kind == Token::PUNCT && t.text == ")")
+        throw BinderException(who + ": the " + what + " list of column \"" + sch.names[c] + "\" is empty in filter \"" +
+                              filter + "\"");
+    for (;;) {
+        if (t.kind == Token::END)
+            throw BinderException(who + ": \")\" is missing after the " + what + " list of column \"" + sch.names[c] +
+                                  "\" in filter \"" + filter + "\"");
+        if (t.kind == Token::WORD && StringUtil::Lower(t.text) == "null") {
+            has_null = true;
+        } else {
+            fls_predicate p;
+            memset(&p, 0, sizeof(p));
+            p.col = (uint32_t)c;
+            SetLiteral(sch, c, lex, t, filter, p, strs);
+            lits.push_back(p);
+        }
+        t = lex.Next();
+        if (t.kind == Token::PUNCT && t.text == ")") break;
+        if (t.kind == Token::END)
+            throw BinderException(who + ": \")\" is missing after the " + what + " list of column \"" + sch.names[c] +
+                                  "\" in filter \"" + filter + "\"");
+        if (t.kind != Token::PUNCT || t.text != ",")
+            throw BinderException(who + ": \",\" or \")\" is expected at \"" + t.text + "\" in the " + what +
+                                  " list of filter \"" + filter + "\"");
+        t = lex.Next();
+    }
+    fls_predicate p;
+    memset(&p, 0, sizeof(p));
+    p.col = (uint32_t)c;
+    if ((negate && has_null) || lits.empty()) {
+        p.clause = clause++;
+        p.op = FLS_CMP_FALSE;
+        preds.push_back(p);
+        return;
+    }
+    const uint8_t ty = sch.cols[c].type;
+    if (IsString(ty) || IsFloat(ty)) {
+        for (fls_predicate &l : lits) {
+            l.op = negate ? FLS_CMP_NE : FLS_CMP_EQ;
+            l.clause = negate ? clause++ : clause;
+            preds.push_back(l);
+        }
+        if (!negate) ++clause;
+        return;
+    }
+    std::vector<uint64_t> keys;
+    for (const fls_predicate &l : lits) keys.push_back(l.value);
+    const bool is_unsigned = (ty >= FLS_UINT8 && ty <= FLS_UINT64) || ty == FLS_BOOLEAN;
+    fls_keyset *set = nullptr;
+    if (!conn || !sets ||
+        fls_keyset_create(conn, keys.data(), keys.size(), is_unsigned ? FLS_KEYSET_UNSIGNED : FLS_KEYSET_SIGNED,
+                          FLS_KEYSET_AUTO, &set) != 0)
+        throw BinderException(who + ": cannot build the key set of the " + what + " list in filter \"" + filter +
+                              "\": " + (conn && sets ? fls_last_error() : "no connection"));
+    sets->sets.push_back(set);
+    p.clause = clause++;
+    p.op = negate ? FLS_CMP_NOT_IN_SET : FLS_CMP_IN_SET;
+    p.value = (uint64_t)(uintptr_t)set;
+    preds.push_back(p);
+}
+
 inline void ParseFilter(const Schema &sch, const string &filter, std::vector<fls_predicate> &preds,
-                        std::deque<string> &strs, const string &who = "fastlanes_aggregate") {
+                        std::deque<string> &strs, const string &who = "fastlanes_aggregate",
+                        fls_connection *conn = nullptr, KeySets *sets = nullptr) {
     if (Trim(filter).empty()) return;
     Lexer lex(filter, who);
     uint32_t clause = 0;
@@ -268,8 +370,24 @@ inline void ParseFilter(const Schema &sch, const string &filter, std::vector<fls
         fls_predicate p;
         memset(&p, 0, sizeof(p));
         p.col = (uint32_t)c;
-        p.clause = clause++;
         Token op = lex.Next();
+        bool in_list = op.kind == Token::WORD && StringUtil::Lower(op.text) == "in", negate = false;
+        if (op.kind == Token::WORD && StringUtil::Lower(op.text) == "not") {
+            Token t = lex.Next();
+            if (t.kind != Token::WORD || StringUtil::Lower(t.text) != "in")
+                throw BinderException(who + ": NOT IN is expected after \"" + col.text + "\" in filter \"" + filter + "\"");
+            in_list = negate = true;
+        }
+        if (in_list) {
+            ParseInList(sch, c, negate, lex, filter, clause, preds, strs, conn, sets);
+            Token next = lex.Next();
+            if (next.kind == Token::END) return;
+            if (next.kind != Token::WORD || StringUtil::Lower(next.text) != "and")
+                throw BinderException(who + ": only AND joins filter terms, found \"" + next.text + "\" in filter \"" +
+                                      filter + "\"");
+            continue;
+        }
+        p.clause = clause++;
         if (op.kind == Token::WORD && StringUtil::Lower(op.text) == "is") {
             Token t = lex.Next();
             bool is_not = false;

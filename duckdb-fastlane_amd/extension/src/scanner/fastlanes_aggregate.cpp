@@ -77,6 +77,7 @@ struct AggBindData : public TableFunctionData {
     vector<string> names;                // the items' trimmed text
     std::vector<fls_predicate> preds;
     std::deque<string> pred_strs;        // VARCHAR constants the predicates point at
+    std::shared_ptr<KeySets> pred_sets = std::make_shared<KeySets>();  // the key sets of the filter's IN lists
     std::shared_ptr<AggTable> table;     // opened at bind (footer only)
     std::vector<uint32_t> keys;          // the group_by columns (empty: ungrouped, one row)
 };
@@ -324,7 +325,9 @@ unique_ptr<FunctionData> AggBind(ClientContext &, TableFunctionBindInput &input,
     if (bind->specs.size() > 32)
         throw BinderException("fastlanes_aggregate: at most 32 aggregates per call, \"" + list + "\" holds " +
                               std::to_string(bind->specs.size()));
-    if (input.inputs.size() >= 3) ParseFilter(sch, input.inputs[2].GetValue<string>(), bind->preds, bind->pred_strs);
+    if (input.inputs.size() >= 3)
+        ParseFilter(sch, input.inputs[2].GetValue<string>(), bind->preds, bind->pred_strs, "fastlanes_aggregate", conn,
+                    bind->pred_sets.get());
     return_types = bind->types;
     if (input.inputs.size() == 4) {
         // the key columns come first, named and typed as the table's columns

@@ -58,6 +58,7 @@ struct TopnBindData : public TableFunctionData {
     std::vector<uint8_t> mask;           // fls_topn's col_mask
     std::vector<fls_predicate> preds;
     std::deque<string> pred_strs;        // VARCHAR constants the predicates point at
+    std::shared_ptr<KeySets> pred_sets = std::make_shared<KeySets>();  // the key sets of the filter's IN lists
     std::shared_ptr<TopnTable> table;    // opened at bind (footer only)
 };
 
@@ -167,7 +168,8 @@ unique_ptr<FunctionData> TopnBind(ClientContext &, TableFunctionBindInput &input
     sch.Load(bind->table->table);
     ParseOrderBy(sch, input.inputs[1].GetValue<string>(), bind->key);
     if (input.inputs.size() >= 4)
-        ParseFilter(sch, input.inputs[3].GetValue<string>(), bind->preds, bind->pred_strs, kWho);
+        ParseFilter(sch, input.inputs[3].GetValue<string>(), bind->preds, bind->pred_strs, kWho, conn,
+                    bind->pred_sets.get());
     ParseColumns(sch, input.inputs.size() == 5 ? input.inputs[4].GetValue<string>() : string(), bind->out_cols);
     bind->mask.assign(sch.cols.size(), 0);
     for (uint32_t c : bind->out_cols) {

@@ -45,6 +45,7 @@
 #include "duckdb/planner/table_filter.hpp"
 #include "duckdb/planner/table_filter_state.hpp"
 #include "duckdb/storage/table/column_segment.hpp"
+#include "table_function/filter_text.hpp"
 #include "table_function/read_fastlanes.hpp"
 #include "type_mapping.hpp"
 
@@ -123,6 +124,7 @@ struct ReadGlobalState : public GlobalTableFunctionState {
     std::vector<fls_predicate> preds;    // pushed-down filter (empty: none)
     bool narrow = false;                 // narrowed delivery of integer columns (fls_scan_narrow)
     std::deque<string> pred_strs;        // VARCHAR constants the predicates point at
+    filter_text::KeySets pred_sets;      // key sets of the long IN lists (live as long as this state)
     // pushed-down filters the engine cannot evaluate (e.g. EXPRESSION_FILTER):
     // applied on the host to every delivered chunk the way DuckDB's own scans
     // apply them (ColumnSegment::FilterSelection), so the query never fails
@@ -323,18 +325,80 @@ bool AddOrTerms(const TableFilter &f, uint32_t col, uint32_t clause, const Logic
     return true;
 }
 
+// An IN list of more than kInSetMinValues values on an integer-like column,
+// as a clause of its own (not under an OR), becomes one key-set term
+// (fls_keyset_create / FLS_CMP_IN_SET): filter_kernel walks every EQ term for
+// every row, a set is probed once.  Shorter lists, other types and an InFilter
+// under a ConjunctionOrFilter stay EQ terms of one clause.
+constexpr size_t kInSetMinValues = 16;
+
+bool IsKeySetType(const LogicalType &type) {
+    switch (type.id()) {
+    case LogicalTypeId::TINYINT: case LogicalTypeId::SMALLINT: case LogicalTypeId::INTEGER: case LogicalTypeId::BIGINT:
+    case LogicalTypeId::UTINYINT: case LogicalTypeId::USMALLINT: case LogicalTypeId::UINTEGER:
+    case LogicalTypeId::UBIGINT: case LogicalTypeId::BOOLEAN: case LogicalTypeId::DATE:
+        return true;
+    case LogicalTypeId::DECIMAL: return type.Width() <= 18;
+    default: return false;
+    }
+}
+
+// the set lives in `sets`, as long as the scan's global state
+bool AddSetTerm(const vector<Value> &values, uint32_t col, uint32_t clause, const LogicalType &type,
+                std::vector<fls_predicate> &out, std::deque<string> &strs, filter_text::KeySets &sets) {
+    std::vector<uint64_t> keys;
+    fls_predicate p;
+    for (auto &v : values) {
+        if (v.IsNull()) continue;  // x IN (..., NULL) is never true through the NULL
+        if (!MakeTerm(col, clause, FLS_CMP_EQ, v, type, strs, p)) return false;
+        keys.push_back(p.value);
+    }
+    memset(&p, 0, sizeof(p));
+    p.col = col;
+    p.clause = clause;
+    if (keys.empty()) {
+        p.op = FLS_CMP_FALSE;
+        out.push_back(p);
+        return true;
+    }
+    bool is_unsigned = false;
+    switch (type.id()) {
+    case LogicalTypeId::UTINYINT: case LogicalTypeId::USMALLINT: case LogicalTypeId::UINTEGER:
+    case LogicalTypeId::UBIGINT: case LogicalTypeId::BOOLEAN:
+        is_unsigned = true;
+        break;
+    default: break;
+    }
+    fls_connection *conn = SharedConnection();
+    fls_keyset *set = nullptr;
+    if (!conn || fls_keyset_create(conn, keys.data(), keys.size(), is_unsigned ? FLS_KEYSET_UNSIGNED : FLS_KEYSET_SIGNED,
+                                   FLS_KEYSET_AUTO, &set) != 0)
+        return false;  // the filter stays on the host
+    sets.sets.push_back(set);
+    p.op = FLS_CMP_IN_SET;
+    p.value = (uint64_t)(uintptr_t)set;
+    out.push_back(p);
+    return true;
+}
+
 // TableFilter on one column -> clauses (AND of ORs); false: some part the
 // engine cannot evaluate (the caller keeps the whole filter on the host)
 bool AddFilter(const TableFilter &f, uint32_t col, const LogicalType &type, uint32_t &clause,
-               std::vector<fls_predicate> &out, std::deque<string> &strs) {
+               std::vector<fls_predicate> &out, std::deque<string> &strs, filter_text::KeySets &sets) {
     switch (f.filter_type) {
     case TableFilterType::CONJUNCTION_AND:
         for (auto &ch : f.Cast<ConjunctionAndFilter>().child_filters)
-            if (!AddFilter(*ch, col, type, clause, out, strs)) return false;
+            if (!AddFilter(*ch, col, type, clause, out, strs, sets)) return false;
         return true;
     case TableFilterType::OPTIONAL_FILTER:  // optional by definition: DuckDB re-checks it above the scan
         return true;
-    case TableFilterType::CONSTANT_COMPARISON: case TableFilterType::IN_FILTER: case TableFilterType::IS_NULL:
+    case TableFilterType::IN_FILTER: {
+        auto &values = f.Cast<InFilter>().values;
+        if (values.size() > kInSetMinValues && IsKeySetType(type))
+            return AddSetTerm(values, col, clause++, type, out, strs, sets);
+        return AddOrTerms(f, col, clause++, type, out, strs);
+    }
+    case TableFilterType::CONSTANT_COMPARISON: case TableFilterType::IS_NULL:
     case TableFilterType::IS_NOT_NULL: case TableFilterType::CONJUNCTION_OR:
         return AddOrTerms(f, col, clause++, type, out, strs);
     default: return false;  // EXPRESSION_FILTER, STRUCT_EXTRACT, DYNAMIC_FILTER, ...
@@ -371,7 +435,8 @@ unique_ptr<GlobalTableFunctionState> ReadInitGlobal(ClientContext &context, Tabl
             // the engine takes the column's filter whole or not at all
             const size_t n0 = state->preds.size();
             const uint32_t c0 = clause;
-            if (!AddFilter(*entry.second, (uint32_t)id, bind.types[id], clause, state->preds, state->pred_strs)) {
+            if (!AddFilter(*entry.second, (uint32_t)id, bind.types[id], clause, state->preds, state->pred_strs,
+                           state->pred_sets)) {
                 state->preds.resize(n0);
                 clause = c0;
                 state->residual.push_back({id, entry.second.get()});

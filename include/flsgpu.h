@@ -51,7 +51,7 @@ typedef enum fls_status {
     FLS_ERR_STATE = -5,     /* call out of order (e.g. decode before upload) */
     FLS_ERR_NOMEM = -6,
     FLS_ERR_CONFIG = -7,    /* an FLS_* tuning variable names a kernel this build does not hold */
-    FLS_ERR_LIMIT = -8      /* a documented capacity was exceeded (fls_aggregate_grouped, fls_topn) */
+    FLS_ERR_LIMIT = -8      /* a documented capacity was exceeded (fls_aggregate_grouped, fls_topn, fls_keyset_create) */
 } fls_status;
 
 typedef struct fls_connection fls_connection;
@@ -102,11 +102,19 @@ typedef struct fls_rowgroup {
 /* Pushed-down filter term: `column <op> constant` (DuckDB TableFilterSet:
  * ConstantFilter / IsNullFilter / IsNotNullFilter; ConjunctionOr and InFilter
  * become several terms of one clause, ConjunctionAnd several clauses).
- * Terms with equal `clause` are OR-ed, clauses are AND-ed. */
+ * Terms with equal `clause` are OR-ed, clauses are AND-ed.
+ * FLS_CMP_IN_SET / FLS_CMP_NOT_IN_SET test membership in a key set
+ * (fls_keyset_create below): `value` carries the set's handle.  IN_SET holds
+ * for a row whose column is valid and whose decoded value, sign- or
+ * zero-extended to 64 bits, is in the set; NOT_IN_SET for a valid row whose
+ * value is not; a NULL row satisfies neither.  A set term is a clause of its
+ * own, AND-ed with the rest (the semi-join / anti-join restriction of a fact
+ * table by a filtered dimension's keys). */
 typedef enum fls_cmp {
     FLS_CMP_EQ = 0, FLS_CMP_NE = 1, FLS_CMP_LT = 2, FLS_CMP_LE = 3, FLS_CMP_GT = 4, FLS_CMP_GE = 5,
     FLS_CMP_IS_NULL = 6, FLS_CMP_IS_NOT_NULL = 7,
-    FLS_CMP_FALSE = 8             /* holds for no row (a comparison with a NULL constant) */
+    FLS_CMP_FALSE = 8,            /* holds for no row (a comparison with a NULL constant) */
+    FLS_CMP_IN_SET = 9, FLS_CMP_NOT_IN_SET = 10
 } fls_cmp;
 typedef struct fls_predicate {
     uint32_t col;                 /* table column */
@@ -116,7 +124,8 @@ typedef struct fls_predicate {
     uint64_t value;               /* constant in the column's physical type:
                                      signed ints / DATE days / DECIMAL scaled as
                                      int64, unsigned as uint64, FLOAT as IEEE
-                                     binary32 bits (low 32), DOUBLE binary64 bits */
+                                     binary32 bits (low 32), DOUBLE binary64 bits;
+                                     IN_SET / NOT_IN_SET: the fls_keyset handle */
     const char *str;              /* VARCHAR constant (copied) */
     uint64_t str_len;
 } fls_predicate;
@@ -178,6 +187,70 @@ int fls_connection_trim(fls_connection *conn, uint64_t keep_bytes, uint64_t *idl
  * fls_resident_info: the images' bytes and count on device (-1: every GPU). */
 int fls_release_device_memory(int device, uint64_t *freed_bytes);
 int fls_resident_info(int device, uint64_t *bytes, uint32_t *images);
+
+/* Key sets: the build side of a semi-join pushed into the scan filter
+ * (FLS_CMP_IN_SET / FLS_CMP_NOT_IN_SET).  fls_keyset_create builds the set of
+ * keys[0, n) on the host -- no GPU is needed to create a set, query it or
+ * prune with it.  keys are 64-bit patterns as fls_predicate.value carries a
+ * constant of the column's physical type; kind is the order of the column the
+ * set will be probed with (signed: INT*, DATE, DECIMAL; unsigned: UINT*,
+ * BOOLEAN) and orders min / max and the pruning.  Duplicates are removed;
+ * n = 0 is a valid empty set; sets hold no NULL.
+ * form: 0 auto, 1 bitmap, 2 hash table.
+ *   bitmap: one bit per value of [min, max] (max - min < 2^32).
+ *   hash:   open addressing, linear probing, 8-byte slots, capacity the next
+ *           power of two >= 2 * count (1 for the empty set); the home slot of
+ *           key k is (k * 0x9E3779B97F4A7C15 mod 2^64) >> (64 - log2(capacity))
+ *           (slot 0 when the capacity is 1); keys are inserted in ascending
+ *           order of the set's kind, so the table is a pure function of the
+ *           set.  An empty slot holds a sentinel: the largest 64-bit pattern
+ *           that is not a key (~0, else ~0 - 1, ...), so every 64-bit key is
+ *           representable.  max_probe is the largest number of slots examined
+ *           to find a key of the set; every lookup, on the host and on the
+ *           GPU, stops at a match, an empty slot or after max_probe slots.
+ *   auto:   the bitmap when max - min < 2^32 and it is no larger than the hash
+ *           table would be, or at most 1 MiB; else the hash table.
+ * FLS_ERR_LIMIT: n above 2^28 (kMaxKeysetKeys; returned before keys is
+ * read), a forced bitmap spanning more than 2^32 values.
+ * The handle is an opaque token, never dereferenced: every call looks it up
+ * among the live sets, and a stale or foreign value is FLS_ERR_ARG.
+ * fls_scan_filter takes a reference on the set, so freeing the handle while a
+ * filter or a running scan uses it is safe.  The set's image is uploaded to a
+ * GPU by the first scan that probes it there and cached per device inside the
+ * set until the set (and every filter holding it) or its connection is gone.
+ * It does not count against FLS_SCAN_RESIDENT_MB, and fls_connection_trim and
+ * fls_release_device_memory do not free it: free the set.  The upload is
+ * synchronous (fls_keyset_info.device_bytes per GPU, up to 4 GiB at 2^28
+ * keys) and is paid by the first batch on each device.  One set may serve
+ * any number of tables.
+ * fls_scan_filter / fls_rowgroup_may_match refuse with FLS_ERR_ARG before any
+ * device work, the message naming the term ("filter term i: ..."): a set term
+ * on a VARCHAR / BLOB / FLOAT / DOUBLE column or a DECIMAL wider than 64 bits,
+ * a set whose kind differs from the column's, a handle that is not live, and
+ * a set term that shares its clause with another term.
+ * Pruning: under IN_SET a row group with a zone map is read only if a key
+ * lies in [min, max] of its zone map (the empty set prunes every row group,
+ * so the call does no device work); an all-NULL chunk matches neither
+ * operator; NOT_IN_SET prunes nothing else.  Not in the reference. */
+typedef struct fls_keyset fls_keyset;
+typedef enum fls_keyset_kind { FLS_KEYSET_SIGNED = 0, FLS_KEYSET_UNSIGNED = 1 } fls_keyset_kind;
+typedef enum fls_keyset_form { FLS_KEYSET_AUTO = 0, FLS_KEYSET_BITMAP = 1, FLS_KEYSET_HASH = 2 } fls_keyset_form;
+typedef struct fls_keyset_info_t {
+    uint64_t count;         /* distinct keys */
+    uint32_t form;          /* the form chosen: FLS_KEYSET_BITMAP or FLS_KEYSET_HASH */
+    uint32_t kind;          /* fls_keyset_kind */
+    uint64_t device_bytes;  /* bytes of the image, per GPU that probes the set */
+    uint64_t capacity;      /* hash: slots (0 for a bitmap) */
+    uint32_t max_probe;     /* hash: longest probe sequence (0 for a bitmap or an empty set) */
+    uint32_t pad;
+    uint64_t min, max;      /* patterns, in the set's order (0 for the empty set) */
+    uint64_t empty;         /* hash: the empty slot's sentinel */
+} fls_keyset_info_t;
+int fls_keyset_create(fls_connection *conn, const uint64_t *keys, uint64_t n, int kind, int form, fls_keyset **out);
+void fls_keyset_free(fls_keyset *set);
+int fls_keyset_info(const fls_keyset *set, fls_keyset_info_t *info);
+/* Host probe of the very image a scan uploads: 1 in the set, 0 not. */
+int fls_keyset_contains(const fls_keyset *set, uint64_t key);
 
 /* Connection::read_fls(): parse footer + schema (no GPU work). */
 int fls_read_fls(fls_connection *conn, const char *path, fls_table **out);
