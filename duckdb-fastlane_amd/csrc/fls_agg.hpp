@@ -5,7 +5,7 @@
 //
 // One launch per batch evaluates every requested aggregate and writes one
 // fixed-size partial record per (1024-row vector, aggregate); the host folds
-// the records in row order (flsgpu.hip).  A row contributes when it is
+// the records in row order (fls_scan_agg.hip).  A row contributes when it is
 // selected (mask bit, or row < nrows without a mask) and its operand column(s)
 // are valid there: values at NULL rows are placeholders and are never loaded.
 // The reduction order inside a vector is fixed (lane: its four rows in order;

@@ -33,6 +33,7 @@ inline constexpr Knob kKnobs[] = {
     {"FLS_OPEN_CACHE", 16},           // opened files kept mapped with their metadata (0: off)
     {"FLS_COPY_THREADS", 4},          // staging copy threads per connection
     {"FLS_PIN_ARENA_MB", 0},          // registered pinned arena cap (fls_pinned.hpp; 0: hipHostMalloc only)
+    // device-resident table (fls_device_table.hip)
     {"FLS_PLACEMENT_DECODE", 6},      // output-buffer sets rated by decode launches per resident part (0/1: write probe)
     {"FLS_PLACEMENT_HEAPS", 1},       // candidate sets include new FSST heaps
     {"FLS_PLACEMENT_IMAGE", 1},       // candidate sets include a new copy of the compressed image

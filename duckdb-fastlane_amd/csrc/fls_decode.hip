@@ -66,7 +66,7 @@ namespace {
 //   queue != NULL: whole chunks, the first static, then from the work queue;
 //   neither: whole chunks, grid-stride.
 // RATING: the same kernel under another name, for the upload's placement
-// rating launches (rating_launch(), flsgpu.hip decode_rating), so a profile
+// rating launches (rating_launch(), fls_device_table.hip decode_rating), so a profile
 // tells them from the decode's own launches
 template <bool RATING>
 __global__ __launch_bounds__(256, FLS_WAVES_PER_SIMD) void decode_kernel(const DevChunk *__restrict__ chunks, uint32_t nchunks,

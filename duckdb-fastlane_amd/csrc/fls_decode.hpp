@@ -219,7 +219,7 @@ int decode_grid_size(uint32_t shmem_per_block);
 int device_cus();
 int occupancy(const void *kernel, int block, size_t shmem);
 
-// Placement rating (flsgpu.hip decode_rating): decode launches made by this
+// Placement rating (fls_device_table.hip decode_rating): decode launches made by this
 // thread while it is set use the kernels' RATING instantiations -- the same
 // code under another name (decode_kernel<true>, fused_kernel<.., .., true>),
 // so profiles and step spans tell the upload's rating launches from the

@@ -1,0 +1,567 @@
+// fls_device_table.hip -- device-resident mode (fls_device_*): a table's row
+// groups uploaded verbatim to HBM, one part per GPU, and decoded there by one
+// launch per pass (launch_all, flsgpu.hip); the decoded columns stay on the
+// device.  The benchmark's kernel roofline runs on this path.  Also the plain
+// device-memory helpers of the C ABI (fls_device_count / alloc / free / memcpy).
+#include "fls_engine.hpp"
+
+using namespace fls;
+using namespace fls::engine;
+
+extern "C" {
+
+int fls_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+int fls_device_alloc(int device, uint64_t bytes, void **ptr) {
+    if (!ptr) return fail(FLS_ERR_ARG, "fls_device_alloc: NULL out");
+    *ptr = nullptr;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMalloc(ptr, std::max<uint64_t>(bytes, 1)));
+    return 0;
+}
+
+int fls_device_free(int device, void *ptr) {
+    if (!ptr) return 0;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipFree(ptr));
+    return 0;
+}
+
+int fls_device_memcpy(int device, void *dst, const void *src, uint64_t bytes, int kind) {
+    if (!dst || !src) return fail(FLS_ERR_ARG, "fls_device_memcpy: NULL pointer");
+    const hipMemcpyKind k = kind == 0 ? hipMemcpyHostToDevice : kind == 1 ? hipMemcpyDeviceToHost
+                                                                           : hipMemcpyDeviceToDevice;
+    if (kind < 0 || kind > 2) return fail(FLS_ERR_ARG, "fls_device_memcpy: kind %d", kind);
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMemcpy(dst, src, bytes, k));
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- HBM placement of the resident output columns --------------
+// The decode's write stream runs at a speed set by where the driver placed
+// the output buffers (the same decode at the same virtual addresses: 2.63-3.13
+// ms on lineitem_full SF12.5 from one allocation to the next,
+// profiles/r6/placement_*.txt).  A candidate set of output columns is rated by
+// probe_placement: the decode's chunk-order write stream against a linear fill
+// of the same buffers (the fill runs at the same speed on every placement, so
+// the ratio q rates the placement on this box).  Up to FLS_PLACEMENT_TRIES
+// sets (default 8) are tried, the best kept, the search ending early once
+// q >= FLS_PLACEMENT_GOOD / 1000 (default 990: at 0.93-0.97 some placements
+// still decoded slowly, profiles/r6/placement_q_sf25_r6q.txt).
+int placement_tries() { return (int)std::max<int64_t>(1, knob_value("FLS_PLACEMENT_TRIES")); }
+
+struct PlacementRating {
+    float chunk_ms = 0, fill_ms = 0;
+    double q = 0;
+};
+
+int rate_outputs(const fls_table *t, const Resident &r, const std::vector<DevBuf<uint8_t>> &outs,
+                 PlacementRating &pr) {
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    std::vector<ProbeRegion> reg;
+    for (uint32_t c = 0; c < ncols; ++c)
+        for (uint32_t g = r.rg0; g < r.rg1; ++g) {
+            const uint64_t ob = out_bytes_of(t, c);
+            const uint64_t bytes = (t->meta.rgs[g].nrows * ob) & ~1023ull;
+            if (bytes) reg.push_back({outs[c].p + (t->meta.rgs[g].first_row - r.first_row) * ob, bytes});
+        }
+    // the decode's queue order: largest output first
+    std::stable_sort(reg.begin(), reg.end(), [](const ProbeRegion &a, const ProbeRegion &b) { return a.bytes > b.bytes; });
+    DevBuf<ProbeRegion> d;
+    HIP_TRY(d.alloc(r.dev, reg.size()));
+    HIP_TRY(hipMemcpy(d.p, reg.data(), reg.size() * sizeof(ProbeRegion), hipMemcpyHostToDevice));
+    std::vector<uint8_t *> bufs(ncols);
+    std::vector<uint64_t> sizes(ncols);
+    for (uint32_t c = 0; c < ncols; ++c) {
+        bufs[c] = outs[c].p;
+        sizes[c] = (r.rows * out_bytes_of(t, c)) & ~4095ull;
+    }
+    HIP_TRY(probe_placement(d.p, (uint32_t)reg.size(), bufs.data(), sizes.data(), ncols, 2, r.stream, &pr.chunk_ms,
+                            &pr.fill_ms));
+    pr.q = pr.chunk_ms > 0 ? pr.fill_ms / pr.chunk_ms : 0;
+    return 0;
+}
+
+int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask);
+
+// A candidate set rated by one real decode launch of every column (the
+// launch after a warm-up one, HIP events): at SF100 the write probe rated every
+// set >= 0.99 while the main columns still decoded up to 5 % slower on some
+// sets (profiles/r6/placement_sels_sf100_r6w.txt), and four sets rated by
+// their decode differed by 3-4 % within one upload, the kept one decoding
+// within 0.3 % of its rating afterwards (placement_dec_sf100_r6x.txt).  The
+// launch's errors are not the upload's: a failure (ms < 0) falls back to the
+// write probe.
+float decode_rating(fls_table *t, Resident &r) {
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    const std::vector<uint8_t> mask(ncols, 1);
+    r.invalidate();  // descriptors point at the current outputs
+    const uint32_t ev0 = r.ev_used;
+    struct RatingScope {
+        RatingScope() { rating_launch() = true; }
+        ~RatingScope() { rating_launch() = false; }
+    } scope;
+    // two warm-up launches (a fresh set decodes ~4 % slower at first), then
+    // the fastest of three
+    constexpr int kWarm = 2, kTimed = 3;
+    bool ok = true;
+    for (int i = 0; i < kWarm + kTimed && ok; ++i) ok = decode_part(t, r, mask) == 0;
+    ok = ok && hipStreamSynchronize(r.stream) == hipSuccess;
+    float ms = -1;
+    for (int i = kWarm; i < kWarm + kTimed && ok; ++i) {
+        float x = 0;
+        ok = hipEventElapsedTime(&x, r.ev_pool[ev0 + 2 * i], r.ev_pool[ev0 + 2 * i + 1]) == hipSuccess;
+        if (ok && (ms < 0 || x < ms)) ms = x;
+    }
+    uint32_t e = 0;
+    ok = ok && hipMemcpy(&e, r.err.p, sizeof(e), hipMemcpyDeviceToHost) == hipSuccess && e == 0;
+    (void)hipGetLastError();
+    (void)hipMemset(r.err.p, 0, sizeof(uint32_t));
+    r.ev_used = ev0;
+    r.invalidate();
+    return ok ? ms : -1.0f;
+}
+
+// A candidate placement: a new set of output columns, new FSST heaps
+// (FLS_PLACEMENT_HEAPS, default 1) and a new copy of the compressed image
+// (FLS_PLACEMENT_IMAGE, default 1): with all three re-drawn the decode-rated
+// SF100 step ran 20.65-20.75 ms against 20.91-21.05 for outputs alone, four
+// interleaved bench runs each (profiles/r6/ab_placement_candidates_r6af.txt).
+// swap_into exchanges it with the part's current buffers.
+struct Candidate {
+    std::vector<DevBuf<uint8_t>> out, heap;
+    DevBuf<uint8_t> img;
+    void clear() {
+        out.clear();
+        heap.clear();
+        img.release();
+    }
+    void swap_into(Resident &r) {
+        std::swap(r.d_out, out);
+        if (!heap.empty()) std::swap(r.d_heap, heap);
+        if (img.p) {
+            std::swap(r.img.p, img.p);
+            std::swap(r.img.n, img.n);
+            std::swap(r.img.dev, img.dev);
+        }
+    }
+};
+bool placement_flag(const char *name) { return knob_value(name) != 0; }
+
+// a new candidate (plain hipMalloc: a speculative set must not evict cached
+// images), or false when it does not fit
+bool alloc_candidate(const fls_table *t, const Resident &r, uint64_t set_bytes, Candidate &cand) {
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    const bool heaps = placement_flag("FLS_PLACEMENT_HEAPS"), image = placement_flag("FLS_PLACEMENT_IMAGE");
+    uint64_t extra = image ? r.img.n : 0;
+    for (uint32_t c = 0; heaps && c < ncols; ++c) extra += r.d_heap[c].p ? r.d_heap[c].n : 0;
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < set_bytes + extra + (set_bytes + extra) / 8 + (1ull << 30)) {
+        (void)hipGetLastError();
+        return false;  // no room for a second set
+    }
+    cand.clear();
+    auto make = [&](DevBuf<uint8_t> &b, size_t n) {
+        if (hipMalloc((void **)&b.p, std::max<size_t>(1, n)) != hipSuccess) {
+            (void)hipGetLastError();
+            b.p = nullptr;
+            return false;
+        }
+        b.n = n;
+        b.dev = r.dev;
+        return true;
+    };
+    cand.out.resize(ncols);
+    bool ok = true;
+    for (uint32_t c = 0; c < ncols && ok; ++c) ok = make(cand.out[c], r.rows * out_bytes_of(t, c));
+    if (ok && heaps) {
+        cand.heap.resize(ncols);
+        for (uint32_t c = 0; c < ncols && ok; ++c)
+            if (r.d_heap[c].p) ok = make(cand.heap[c], r.d_heap[c].n);
+    }
+    if (ok && image) ok = make(cand.img, r.img.n) && hipMemcpy(cand.img.p, r.img.p, r.img.n, hipMemcpyDeviceToDevice) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        cand.clear();  // frees the ones made
+    }
+    return ok;
+}
+
+int choose_placement(fls_table *t, Resident &r) {
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    uint64_t set_bytes = 0;
+    for (uint32_t c = 0; c < ncols; ++c) set_bytes += r.rows * out_bytes_of(t, c);
+    if (set_bytes < (256ull << 20)) return 0;  // small outputs: nothing to gain
+    const bool dbg = getenv("FLS_DEBUG") != nullptr;
+    // 1. by decode time: FLS_PLACEMENT_DECODE sets (default 6), the fastest kept
+    const int ndec = (int)std::max<int64_t>(0, knob_value("FLS_PLACEMENT_DECODE"));
+    float best_ms = ndec > 1 ? decode_rating(t, r) : -1.0f;
+    if (best_ms > 0) {
+        if (dbg) fprintf(stderr, "DEBUG: placement dev %d set 0: decode %.3f ms\n", r.dev, best_ms);
+        int kept = 0;
+        Candidate cand;
+        for (int k = 1; k < ndec && alloc_candidate(t, r, set_bytes, cand); ++k) {
+            cand.swap_into(r);  // the candidate decodes in place of the current set
+            const float ms = decode_rating(t, r);
+            if (dbg) fprintf(stderr, "DEBUG: placement dev %d set %d: decode %.3f ms\n", r.dev, k, ms);
+            if (ms > 0 && ms < best_ms) {
+                best_ms = ms;  // keep it: the previous set is freed with cand
+                kept = k;
+            } else {
+                cand.swap_into(r);  // back to the current set; the candidate goes
+            }
+            cand.clear();
+        }
+        r.placement_ms = best_ms;
+        if (dbg) fprintf(stderr, "DEBUG: placement dev %d kept set %d (decode %.3f ms)\n", r.dev, kept, best_ms);
+        return 0;
+    }
+    // 2. by the write probe: up to FLS_PLACEMENT_TRIES sets, stop at q >= good
+    const int tries = placement_tries();
+    if (tries <= 1) return 0;
+    const double good = knob_value("FLS_PLACEMENT_GOOD") / 1000.0;  // per mille
+    PlacementRating best;
+    if (const int rc = rate_outputs(t, r, r.d_out, best)) return rc;
+    if (dbg)
+        fprintf(stderr, "DEBUG: placement dev %d set 0: chunk order %.3f ms, fill %.3f ms, q %.3f\n", r.dev,
+                best.chunk_ms, best.fill_ms, best.q);
+    int kept = 0;
+    Candidate cand;
+    for (int k = 1; k < tries && best.q < good && alloc_candidate(t, r, set_bytes, cand); ++k) {
+        PlacementRating pr;
+        if (const int rc = rate_outputs(t, r, cand.out, pr)) return rc;
+        if (dbg)
+            fprintf(stderr, "DEBUG: placement dev %d set %d: chunk order %.3f ms, fill %.3f ms, q %.3f\n", r.dev, k,
+                    pr.chunk_ms, pr.fill_ms, pr.q);
+        if (pr.q > best.q) {
+            cand.swap_into(r);  // the previous set is freed with cand
+            best = pr;
+            kept = k;
+        }
+        cand.clear();
+    }
+    r.placement_q = best.q;
+    if (dbg) fprintf(stderr, "DEBUG: placement dev %d kept set %d (q %.3f)\n", r.dev, kept, best.q);
+    return 0;
+}
+
+// Upload one GPU's part: row groups [rg0, rg1) verbatim, their string_t
+// tables, HBM output columns and FSST heaps.
+int upload_part(fls_table *t, Resident &r) {
+    HIP_TRY(hipSetDevice(r.dev));
+    if (!r.stream) HIP_TRY(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));
+    uint64_t lo, hi;
+    rg_byte_range(t->meta, r.rg0, r.rg1, lo, hi);
+    r.base = lo;
+    HIP_TRY(r.img.alloc(r.dev, hi - lo + kImagePad));
+    HIP_TRY(hipMemcpy(r.img.p, t->img + lo, hi - lo, hipMemcpyHostToDevice));
+    std::vector<StrT> host;  // (the resident part keeps only the device tables)
+    int rc = build_strtabs(t, r.dev, r.rg0, r.rg1, r.strtab, r.strtab_off, host);
+    if (rc) return rc;
+    HIP_TRY(r.err.alloc(r.dev, 1));
+    HIP_TRY(hipMemset(r.err.p, 0, sizeof(uint32_t)));
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    r.first_row = t->meta.rgs[r.rg0].first_row;
+    r.rows = t->meta.rgs[r.rg1 - 1].first_row + t->meta.rgs[r.rg1 - 1].nrows - r.first_row;
+    r.d_out.resize(ncols);
+    for (uint32_t c = 0; c < ncols; ++c) HIP_TRY(r.d_out[c].alloc(r.dev, r.rows * out_bytes_of(t, c)));
+    // FSST heaps: chunk heaps back to back per column, host copy for string_t
+    r.heap_off.assign((size_t)(r.rg1 - r.rg0) * ncols, 0);
+    r.d_heap.resize(ncols);
+    r.h_heap.resize(ncols);
+    for (uint32_t c = 0; c < ncols; ++c) {
+        uint64_t tot = 0;
+        for (uint32_t g = r.rg0; g < r.rg1; ++g) {
+            r.heap_off[(size_t)(g - r.rg0) * ncols + c] = tot;
+            if (is_fsst(t, g, c)) tot += t->meta.rgs[g].chunks[c].hdr.reserved1;
+        }
+        if (tot) {
+            HIP_TRY(r.d_heap[c].alloc(r.dev, tot));
+            HIP_TRY(r.h_heap[c].alloc(tot));
+        } else {
+            r.d_heap[c].release();
+            r.h_heap[c].release();
+        }
+    }
+    r.invalidate();
+    r.mask.clear();
+    if (const int prc = choose_placement(t, r)) return prc;
+    if (getenv("FLS_DEBUG")) {  // buffer placement (decode speed by buffer address)
+        fprintf(stderr, "DEBUG: part dev %d rg [%u, %u) image %p %llu B\n", r.dev, r.rg0, r.rg1, (void *)r.img.p,
+                (unsigned long long)(hi - lo));
+        for (uint32_t c = 0; c < ncols; ++c)
+            fprintf(stderr, "DEBUG:   col %u out %p %llu B heap %p\n", c, (void *)r.d_out[c].p,
+                    (unsigned long long)(r.rows * out_bytes_of(t, c)), (void *)r.d_heap[c].p);
+    }
+    return 0;
+}
+
+// Enqueue one decode launch of the selected columns on part r (asynchronous).
+int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask) {
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    HIP_TRY(hipSetDevice(r.dev));
+    const int64_t policy = decode_policy();
+    if (mask != r.mask || !r.list_built || policy != r.policy) {
+        // (re)build the launch descriptor list: column-major task order, so
+        // concurrent waves stream one column's consecutive row groups
+        std::vector<DevChunk> chunks;
+        ByteCount bc;
+        for (uint32_t c = 0; c < ncols; ++c) {
+            if (!mask[c]) continue;
+            for (uint32_t g = r.rg0; g < r.rg1; ++g) {
+                const ChunkRef &ch = t->meta.rgs[g].chunks[c];
+                const uint64_t so = r.strtab_off[(size_t)(g - r.rg0) * ncols + c];
+                const uint8_t *dict = so == UINT64_MAX ? nullptr : (const uint8_t *)(r.strtab.p + so);
+                uint8_t *out = r.d_out[c].p + (t->meta.rgs[g].first_row - r.first_row) * out_bytes_of(t, c);
+                const uint64_t ho = r.heap_off[(size_t)(g - r.rg0) * ncols + c];
+                chunks.push_back(make_devchunk(t, g, c, r.img.p + (ch.off - r.base), dict, out, &bc,
+                                               r.d_heap[c].p ? r.d_heap[c].p + ho : nullptr,
+                                               r.h_heap[c].p ? r.h_heap[c].p + ho : nullptr));
+            }
+        }
+        const int64_t lpol = launch_policy(policy, chunks, bc.geom);
+        std::vector<DevChunk> dictwg;
+        r.nmain = order_for_launch(chunks, &r.fsst, lpol, &dictwg);
+        // one DictVec per vector of the chunks the dictionary-string grid takes,
+        // from the host image's VecMeta arrays (validated when the file was read)
+        std::vector<DictVec> dvecs;
+        for (const DevChunk &d : dictwg) {
+            const uint8_t *meta = t->img + r.base + (d.chunk - r.img.p) + d.meta_off;
+            for (uint32_t v = 0; v < d.nvec; ++v) {
+                VecMeta vm;
+                memcpy(&vm, meta + 32ull * v, 32);
+                dvecs.push_back(DictVec{d.chunk + d.packed_off + vm.packed_off, d.dict,
+                                        d.out + (size_t)v * kVectorSize * 16, (uint32_t)vm.for_base,
+                                        (uint32_t)vm.nvals | (uint32_t)vm.bw << 11 | d.dict_count << 17});
+            }
+        }
+        if (getenv("FLS_DEBUG")) {
+            size_t kept = 0;
+            for (size_t i = 0; i < r.nmain; ++i) kept += chunks[i].enc == ENC_DICT && chunks[i].ob == 16;
+            fprintf(stderr, "DEBUG: dictstr_decode_kernel takes %zu chunks (%zu vectors), %zu DICT VARCHAR chunks stay "
+                            "on the main decode\n", dictwg.size(), dvecs.size(), kept);
+        }
+        r.policy = policy;
+        r.lpolicy = lpol;
+        const size_t k = chunks.size();
+        r.split = append_split(chunks, r.nmain, bc.geom, lpol);
+        HIP_TRY(hipStreamSynchronize(r.stream));
+        HIP_TRY(r.d_chunks.alloc(r.dev, chunks.size()));
+        HIP_TRY(hipMemcpy(r.d_chunks.p, chunks.data(), chunks.size() * sizeof(DevChunk), hipMemcpyHostToDevice));
+        HIP_TRY(r.d_dictvecs.alloc(r.dev, dvecs.size()));
+        if (!dvecs.empty())
+            HIP_TRY(hipMemcpy(r.d_dictvecs.p, dvecs.data(), dvecs.size() * sizeof(DictVec), hipMemcpyHostToDevice));
+        r.ndictvecs = (uint32_t)dvecs.size();
+        r.list_built = true;
+        chunks.resize(k);
+        r.h_chunks.swap(chunks);
+        r.mask = mask;
+        r.bytes = bc;
+    }
+    if (r.ev_used + 2 > r.ev_pool.size()) {
+        for (int i = 0; i < 2; ++i) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreate(&e));
+            r.ev_pool.push_back(e);
+        }
+    }
+    // queue counters and the side stream exist before the timed region
+    HIP_TRY(r.queue.alloc(r.dev, kQueueWords));
+    if (!r.side.stream) {
+        HIP_TRY(hipStreamCreateWithFlags(&r.side.stream, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&r.side.fork, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&r.side.join, hipEventDisableTiming));
+    }
+    if (r.fsst.total_vecs() > 0)
+        if (const int rc = fsst_config_check(r.lpolicy)) return rc;
+    hipEvent_t e0 = r.ev_pool[r.ev_used], e1 = r.ev_pool[r.ev_used + 1];
+    r.ev_used += 2;
+    HIP_TRY(hipEventRecord(e0, r.stream));
+    HIP_TRY(launch_all(r.d_chunks.p, r.nmain, (uint32_t)r.h_chunks.size(), r.fsst, r.err.p, r.bytes.geom, r.stream,
+                       r.queue.p, r.lpolicy, r.split, &r.side, r.d_dictvecs.p, r.ndictvecs));
+    HIP_TRY(hipEventRecord(e1, r.stream));
+    return 0;
+}
+
+uint64_t resident_rows(const fls_table *t) {
+    uint64_t n = 0;
+    for (auto &r : t->resident) n += r->rows;
+    return n;
+}
+
+const Resident *part_of(const fls_table *t, uint32_t part) {
+    return t && part < t->resident.size() ? t->resident[part].get() : nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fls_device_upload(fls_table *t, uint32_t rg_begin, uint32_t rg_end) {
+    if (!t) return fail(FLS_ERR_ARG, "fls_device_upload: NULL table");
+    if (rg_end > t->meta.rgs.size() || rg_begin >= rg_end)
+        return fail(FLS_ERR_ARG, "row-group range [%u,%u) out of bounds", rg_begin, rg_end);
+    // contiguous shards over the connection's GPUs, as a scan splits them
+    const uint32_t G = (uint32_t)t->devices.size(), n = rg_end - rg_begin;
+    t->resident.clear();
+    t->launches = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        const uint32_t a = rg_begin + (uint32_t)((uint64_t)n * g / G), b = rg_begin + (uint32_t)((uint64_t)n * (g + 1) / G);
+        if (a == b) continue;
+        auto r = std::make_unique<Resident>();
+        r->dev = t->devices[g];
+        r->rg0 = a;
+        r->rg1 = b;
+        int rc = upload_part(t, *r);
+        t->resident.push_back(std::move(r));
+        if (rc) {
+            t->resident.clear();
+            return rc;
+        }
+    }
+    return 0;
+}
+
+int fls_device_decode(fls_table *t, const uint8_t *col_mask) {
+    if (!t) return fail(FLS_ERR_ARG, "fls_device_decode: NULL table");
+    if (t->resident.empty()) return fail(FLS_ERR_STATE, "fls_device_decode before fls_device_upload");
+    const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    std::vector<uint8_t> mask(ncols, 1);
+    if (col_mask)
+        for (uint32_t c = 0; c < ncols; ++c) mask[c] = col_mask[c] ? 1 : 0;
+    for (auto &r : t->resident) {  // every GPU's launch is queued before any waits
+        int rc = decode_part(t, *r, mask);
+        if (rc) return rc;
+    }
+    t->launches++;
+    return 0;
+}
+
+int fls_device_sync(fls_table *t, fls_decode_stats *stats) {
+    if (!t) return fail(FLS_ERR_ARG, "fls_device_sync: NULL table");
+    if (t->resident.empty()) return fail(FLS_ERR_STATE, "nothing uploaded");
+    uint32_t err = 0;
+    for (auto &r : t->resident) {
+        HIP_TRY(hipSetDevice(r->dev));
+        HIP_TRY(hipStreamSynchronize(r->stream));
+        uint32_t e = 0;
+        HIP_TRY(hipMemcpy(&e, r->err.p, sizeof(e), hipMemcpyDeviceToHost));
+        err |= e;
+    }
+    if (stats) {
+        // per launch the slowest GPU's time (the parts run concurrently)
+        memset(stats, 0, sizeof(*stats));
+        const uint32_t nl = t->resident[0]->ev_used / 2;
+        double total = 0, last = 0;
+        for (uint32_t i = 0; i < nl; ++i) {
+            double span = 0;
+            for (auto &r : t->resident) {
+                if (2 * i + 1 >= r->ev_used) continue;
+                float ms = 0;
+                HIP_TRY(hipSetDevice(r->dev));
+                HIP_TRY(hipEventElapsedTime(&ms, r->ev_pool[2 * i], r->ev_pool[2 * i + 1]));
+                span = std::max(span, (double)ms);
+            }
+            total += span;
+            last = span;
+        }
+        stats->kernel_ms = last;
+        stats->kernel_ms_total = total;
+        stats->timed_launches = nl;
+        for (auto &r : t->resident) {
+            stats->values += r->bytes.values;
+            stats->packed_bytes += r->bytes.packed;
+            stats->meta_bytes += r->bytes.meta;
+            stats->out_bytes += r->bytes.out;
+        }
+        stats->launches = t->launches;
+    }
+    for (auto &r : t->resident) r->ev_used = 0;
+    if (err & KERR_LDS_BASE) return fail(FLS_ERR_DEVICE, "FSST kernel: dynamic LDS not at address 0 (flags 0x%x)", err);
+    if (err) return fail(FLS_ERR_FORMAT, "corrupt chunk detected while decoding (flags 0x%x)", err);
+    return 0;
+}
+
+int fls_device_parts(const fls_table *t) { return t ? (int)t->resident.size() : 0; }
+
+int fls_device_part(const fls_table *t, uint32_t part, fls_device_part_info *out) {
+    const Resident *r = part_of(t, part);
+    if (!r || !out) return fail(FLS_ERR_ARG, "resident part %u out of range", part);
+    out->device = r->dev;
+    out->rg_begin = r->rg0;
+    out->rg_end = r->rg1;
+    out->first_row = r->first_row;
+    out->nrows = r->rows;
+    return 0;
+}
+
+int fls_device_part_column(fls_table *t, uint32_t part, uint32_t col, void **dev_ptr, uint64_t *nbytes) {
+    const Resident *r = part_of(t, part);
+    if (!r || col >= r->d_out.size() || !r->d_out[col].p)
+        return fail(FLS_ERR_ARG, "column %u of part %u not resident", col, part);
+    if (dev_ptr) *dev_ptr = r->d_out[col].p;
+    if (nbytes) *nbytes = r->rows * out_bytes_of(t, col);
+    return 0;
+}
+
+int fls_device_part_heap(fls_table *t, uint32_t part, uint32_t col, void **dev_ptr, const void **host_ptr,
+                         uint64_t *nbytes) {
+    const Resident *r = part_of(t, part);
+    if (!r || col >= r->d_out.size() || !r->d_out[col].p)
+        return fail(FLS_ERR_ARG, "column %u of part %u not resident", col, part);
+    const bool has = col < r->d_heap.size() && r->d_heap[col].p;
+    if (dev_ptr) *dev_ptr = has ? r->d_heap[col].p : nullptr;
+    if (host_ptr) *host_ptr = has ? r->h_heap[col].p : nullptr;
+    if (nbytes) *nbytes = has ? r->d_heap[col].n : 0;
+    return has ? 1 : 0;
+}
+
+// single-GPU accessors: the table's only part (a table split over several
+// GPUs is addressed per part)
+int fls_device_column(fls_table *t, uint32_t col, void **dev_ptr, uint64_t *nbytes) {
+    if (t && t->resident.size() > 1)
+        return fail(FLS_ERR_STATE, "table is resident on %zu GPUs: use fls_device_part_column", t->resident.size());
+    return fls_device_part_column(t, 0, col, dev_ptr, nbytes);
+}
+
+int fls_device_heap(fls_table *t, uint32_t col, void **dev_ptr, const void **host_ptr, uint64_t *nbytes) {
+    if (t && t->resident.size() > 1)
+        return fail(FLS_ERR_STATE, "table is resident on %zu GPUs: use fls_device_part_heap", t->resident.size());
+    return fls_device_part_heap(t, 0, col, dev_ptr, host_ptr, nbytes);
+}
+
+int fls_device_copy_out(fls_table *t, uint32_t col, uint64_t row, uint64_t n, void *host_dst) {
+    if (!t || t->resident.empty() || col >= t->meta.cols.size() || !host_dst)
+        return fail(FLS_ERR_ARG, "column %u not resident", col);
+    const uint64_t total = resident_rows(t);
+    if (row > total || n > total - row) return fail(FLS_ERR_ARG, "rows out of range");
+    const int ob = out_bytes_of(t, col);
+    uint64_t at = 0;  // first resident row of the part, counted over the parts
+    for (auto &rp : t->resident) {
+        Resident &r = *rp;
+        const uint64_t a = std::max(row, at), b = std::min(row + n, at + r.rows);
+        if (a < b) {
+            HIP_TRY(hipSetDevice(r.dev));
+            HIP_TRY(hipStreamSynchronize(r.stream));
+            HIP_TRY(hipMemcpy((uint8_t *)host_dst + (a - row) * ob, r.d_out[col].p + (a - at) * ob, (b - a) * ob,
+                              hipMemcpyDeviceToHost));
+            // FSST: string_t pointers target the host copy of the part's heap
+            if (col < r.d_heap.size() && r.d_heap[col].p)
+                HIP_TRY(hipMemcpy(r.h_heap[col].p, r.d_heap[col].p, r.d_heap[col].n, hipMemcpyDeviceToHost));
+        }
+        at += r.rows;
+    }
+    return 0;
+}
+
+uint64_t fls_device_rows(const fls_table *t) { return t ? resident_rows(t) : 0; }
+
+}  // extern "C"

@@ -1,0 +1,733 @@
+// fls_engine.hpp -- the host engine's internal types and the functions its
+// units call across files.  Not part of the C ABI (include/flsgpu.h).
+//
+//   flsgpu.hip            connections, files, the launch policy and the scan
+//                         pipeline (scan_setup, fill_batch, scan_acquire ...)
+//   fls_scan_agg.hip      fls_aggregate / fls_aggregate_grouped: checks,
+//                         per-batch enqueue, the host fold
+//   fls_scan_topn.hip     fls_topn: checks, per-batch enqueue, the host merge
+//                         and the late materialisation
+//   fls_scan_keyset.hip   the key-set registry and fls_keyset_*
+//   fls_device_table.hip  the device-resident table (fls_device_*)
+//
+// The pushdown and device-table units depend on flsgpu.hip's scan pipeline and
+// launch helpers; flsgpu.hip depends on them only through the three enqueue_*
+// functions fill_batch switches over and keyset_registry().  Every function
+// and registry declared here is defined in exactly one unit.
+//
+// All of it lives in fls::engine, which is hidden: nothing here reaches
+// libflsgpu.so's dynamic symbol table.  A namespace's visibility attribute
+// covers one block only, so every block is opened with FLS_ENGINE_BEGIN.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <condition_variable>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <memory>
+#include <string>
+#include <chrono>
+#include <cmath>
+#include <thread>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/flsgpu.h"
+#include "fls_agg.hpp"
+#include "fls_common.hpp"
+#include "fls_config.hpp"
+#include "fls_decode.hpp"
+#include "fls_filter.hpp"
+#include "fls_format.hpp"
+#include "fls_groupagg.hpp"
+#include "fls_keyset.hpp"
+#include "fls_pinned.hpp"
+#include "fls_reader.hpp"
+#include "fls_resident.hpp"
+#include "fls_topn.hpp"
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess)                                                                      \
+            return fail(FLS_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
+                        __LINE__);                                                                 \
+    } while (0)
+
+#define FLS_ENGINE_BEGIN namespace fls { namespace engine __attribute__((visibility("hidden"))) {
+#define FLS_ENGINE_END } }
+
+struct DevImage;    // a file's compressed image resident in HBM (flsgpu.hip)
+struct MappedFile;  // a mapped, validated file shared by the tables that read it (flsgpu.hip)
+struct fls_table;
+
+FLS_ENGINE_BEGIN
+
+struct ConnRes;  // what a connection keeps between scans (flsgpu.hip)
+
+// DuckDB v1.3.2 string_t (16 B): len <= 12 inlined, else 4-byte prefix + pointer
+struct StrT {
+    uint32_t len;
+    char data[12];
+};
+static_assert(sizeof(StrT) == 16, "string_t is 16 B");
+
+// Scan set-up profile (FLS_SCAN_PROFILE=1): process-wide time and bytes per
+// phase, printed to stderr when a table that scanned closes -- where a cold
+// query's first milliseconds go (pinned and device allocations, string_t
+// tables, the resident image, staging copies, the consumers' waits), and
+// per batch on the GPU (HIP events on the slot's stream: the decode kernels,
+// then the D2H of its columns; batches of different slots overlap, so these
+// are summed stream time, not wall time).
+enum ProfPhase {
+    PROF_PIN_ALLOC, PROF_DEV_ALLOC, PROF_SETUP, PROF_STRTABS, PROF_IMAGE, PROF_STAGE_COPY, PROF_FILL, PROF_FILL_DESC,
+    PROF_FILL_LIST, PROF_REFILL_LAT, PROF_WAIT, PROF_GPU_DECODE, PROF_D2H, PROF_N
+};
+struct ScanProf {
+    std::atomic<uint64_t> ns[PROF_N] = {}, bytes[PROF_N] = {}, calls[PROF_N] = {};
+    static bool on() {
+        static const bool e = getenv("FLS_SCAN_PROFILE") && atoi(getenv("FLS_SCAN_PROFILE")) != 0;
+        return e;
+    }
+    void print() {
+        static const char *names[PROF_N] = {"pinned host alloc", "device alloc", "scan_setup", "string_t tables",
+                                            "resident image", "staging copy", "fill_batch (all)",
+                                            "fill: descriptors", "fill: chunk list", "batch seen -> refill",
+                                            "consumer wait",
+                                            "GPU decode (events)", "D2H (events)"};
+        fprintf(stderr, "FLS_SCAN_PROFILE (process, since the last report):\n");
+        for (int i = 0; i < PROF_N; ++i)
+            fprintf(stderr, "  %-20s %9.3f ms  %8llu calls  %10.1f MB\n", names[i], ns[i].exchange(0) / 1e6,
+                    (unsigned long long)calls[i].exchange(0), bytes[i].exchange(0) / 1e6);
+    }
+};
+ScanProf &scan_prof();  // (flsgpu.hip)
+struct ProfTimer {
+    int ph;
+    uint64_t b;
+    std::chrono::steady_clock::time_point t0;
+    explicit ProfTimer(int phase, uint64_t bytes = 0) : ph(ScanProf::on() ? phase : -1), b(bytes) {
+        if (ph >= 0) t0 = std::chrono::steady_clock::now();
+    }
+    void stop() {  // record now (once)
+        if (ph < 0) return;
+        ScanProf &p = scan_prof();
+        p.ns[ph] += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        p.bytes[ph] += b;
+        p.calls[ph] += 1;
+        ph = -1;
+    }
+    void cancel() { ph = -1; }
+    ~ProfTimer() { stop(); }
+};
+
+// Frees every HBM-resident image no running scan uses on GPU dev (defined
+// with the image registry); a device allocation that runs out of memory calls
+// it once and retries, so the image cache never fails a scan's own buffers.
+uint64_t release_idle_images(int dev);
+
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    int dev = -1;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n), dev(o.dev) { o.p = nullptr; o.n = 0; }
+    void release() {
+        if (p) {
+            int cur;
+            hipGetDevice(&cur);
+            hipSetDevice(dev);
+            hipFree(p);
+            hipSetDevice(cur);
+        }
+        p = nullptr;
+        n = 0;
+    }
+    hipError_t alloc(int d, size_t count) {
+        if (count <= n && p && d == dev) return hipSuccess;
+        release();
+        dev = d;
+        n = count;
+        ProfTimer pt(PROF_DEV_ALLOC, count * sizeof(T));
+        hipError_t e = hipMalloc((void **)&p, std::max<size_t>(1, count * sizeof(T)));
+        if (e == hipErrorOutOfMemory && release_idle_images(d) > 0) {
+            (void)hipGetLastError();
+            e = hipMalloc((void **)&p, std::max<size_t>(1, count * sizeof(T)));
+        }
+        if (e != hipSuccess) {
+            p = nullptr;
+            n = 0;
+        }
+        return e;
+    }
+    ~DevBuf() { release(); }
+};
+
+template <typename T>
+struct PinBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    PinBuf(PinBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    void release() {
+        if (p) pinned_free(p);
+        p = nullptr;
+        n = 0;
+    }
+    hipError_t alloc(size_t count) {
+        if (count <= n && p) return hipSuccess;
+        release();
+        n = count;
+        ProfTimer pt(PROF_PIN_ALLOC, count * sizeof(T));
+        const hipError_t e = pinned_alloc((void **)&p, std::max<size_t>(1, count * sizeof(T)));
+        if (e != hipSuccess) {
+            p = nullptr;
+            n = 0;
+        }
+        return e;
+    }
+    ~PinBuf() { release(); }
+};
+
+// Device images are allocated this much past their last chunk: kernels read
+// whole 16 B blocks of a stream whose last block may end inside it.
+constexpr uint64_t kImagePad = 256;
+
+// FSST chunks of a launch, one kernel group after another (order_for_launch):
+// 0 = segment tables and every string <= 255 bytes, 1 = segment tables,
+// 2 = strings <= 255 bytes, 3 = the rest (DevChunk.vbits: bit 0 = small
+// strings, bit 1 = segment tables); each group numbers its vectors through
+// DevChunk.vec_base.
+constexpr int kFsstGroups = 4;
+inline int fsst_group(uint8_t vbits) { return vbits == 3 ? 0 : vbits == 2 ? 1 : vbits == 1 ? 2 : 3; }
+struct FsstCounts {
+    uint32_t n[kFsstGroups] = {}, vecs[kFsstGroups] = {};
+    uint32_t first(int g) const {
+        uint32_t f = 0;
+        for (int k = 0; k < g; ++k) f += n[k];
+        return f;
+    }
+    uint64_t total_vecs() const {
+        uint64_t t = 0;
+        for (int k = 0; k < kFsstGroups; ++k) t += vecs[k];
+        return t;
+    }
+};
+
+// Per-chunk algorithmic byte accounting (roofline numerator).
+struct ByteCount {
+    uint64_t values = 0, packed = 0, meta = 0, out = 0;
+    DecodeGeom geom;   // max LDS need over the counted chunks
+};
+
+// Byte range of the file covering row groups [rg0, rg1).
+void rg_byte_range(const FileMeta &m, uint32_t rg0, uint32_t rg1, uint64_t &lo, uint64_t &hi);
+
+// Pinned host side of one decoded batch: what consumers read.  It belongs to
+// the batch's row groups, not to the device slot that produced it: once every
+// row group of the batch has been handed out (fls_scan_acquire) the slot is
+// refilled with a fresh HostBatch from the pool, and this one goes back to the
+// pool when the last of its row groups is released.  So a consumer that keeps
+// a row group (DuckDB vectors that reference the pinned columns) never holds
+// up the GPU pipeline, and no consumer waits for another one's release.
+struct HostBatch {
+    uint32_t rg0 = 0, nrg = 0;
+    uint32_t handed = 0, released = 0;    // row groups handed out / handed back
+    std::vector<PinBuf<uint8_t>> h_out;   // per delivered column (pinned)
+    std::vector<PinBuf<uint8_t>> h_heap;  // per FSST column: pinned copy string_t points into
+    std::vector<const void *> col_ptrs;   // per (rg - rg0) * ncols + col: pinned host column start
+    PinBuf<uint32_t> h_counts;            // filtered: selected rows per vector
+    PinBuf<uint32_t> h_sel;               // filtered: selected row indices within their row group
+    uint32_t nvec = 0;                    // vectors of the batch
+    bool sel_ready = false;               // sel_off computed from h_counts
+    std::vector<uint32_t> sel_off;        // per row group of the batch (+1): first selected row
+    // per (rg - rg0) * ncols + col: the delivered rows' validity words (NULL:
+    // all valid) -- the file image's bitmaps, or, filtered, gathered into vbits
+    std::vector<const uint64_t *> valid_ptrs;
+    std::vector<std::vector<uint64_t>> vbits;
+    // dictionary-coded delivery (fls_scan_dict_codes): per column the bytes
+    // delivered per row (string_t 16, or a code width 1 / 2), per (rg - rg0) *
+    // ncols + col the host string_t dictionary and its size (NULL: not coded)
+    std::vector<uint8_t> ob;
+    std::vector<const void *> dict_ptrs;
+    std::vector<uint32_t> dict_sizes;
+    // narrowed delivery (fls_scan_narrow): per column 1 when it crosses PCIe
+    // as value - base in ob bytes, per (rg - rg0) * ncols + col that base
+    std::vector<uint8_t> narrowed;
+    std::vector<uint64_t> nbase;
+    // FSST columns delivered as string lengths (fls_scan_narrow, unfiltered
+    // scans): per column the length width (0: string_t records cross PCIe);
+    // per (rg - rg0) * ncols + col the row group's heap offset in h_heap; the
+    // string_t records rebuilt on the consumer's thread (scan_acquire) into
+    // h_rec; narrow_out = narrowed with these columns cleared (the consumer
+    // sees string_t)
+    std::vector<uint8_t> strlen_w, narrow_out, ob_out;
+    std::vector<uint64_t> heap_off;
+    std::vector<std::unique_ptr<uint8_t[]>> h_rec;
+    std::vector<uint64_t> h_rec_cap;      // rows h_rec[c] holds
+    // completion of the batch's device work, per batch rather than per slot:
+    // the slot takes its next batch as soon as this one's D2H is complete (its
+    // first acquire), while consumers still take this one's row groups
+    hipEvent_t done = nullptr;            // recorded after the D2H (fill_batch)
+    hipEvent_t pt[3] = {};                // FLS_SCAN_PROFILE: decode start, D2H start, end (timing events)
+    uint64_t prof_d2h = 0;                // ... and the batch's D2H bytes
+    std::atomic<bool> prof_pending{false};  // the batch's times not yet counted (its first acquire does)
+    std::atomic<bool> upload_resident{false};  // the batch uploads into the resident image (marked present once done)
+    PinBuf<uint32_t> h_err;               // the device error flags, copied after the batch's kernels
+    PinBuf<AggRec> h_agg;                 // aggregate scan: nvec x naggs partial records (vector-major)
+    // grouped aggregate scan: per row group of the batch its table of groups
+    // (fls_groupagg.hpp, group_rg_stride(naggs, g_nfsum, g_rg_vecs) bytes each)
+    PinBuf<uint8_t> h_grp;
+    uint32_t g_nfsum = 0, g_rg_vecs = 0;
+    // top-N scan: per row group of the batch its list of candidates
+    // (fls_topn.hpp, topn_stride(k) bytes each)
+    PinBuf<uint8_t> h_topn;
+    HostBatch() = default;
+    HostBatch(const HostBatch &) = delete;
+    HostBatch &operator=(const HostBatch &) = delete;
+    ~HostBatch() {
+        if (done) hipEventDestroy(done);
+        for (hipEvent_t e : pt)
+            if (e) hipEventDestroy(e);
+    }
+};
+
+struct Slot {                       // one batch of row groups in flight
+    uint32_t rg0 = 0, nrg = 0;      // absolute row groups (consecutive, all surviving pruning)
+    bool busy = false;              // a batch is enqueued and its D2H not yet seen complete by an acquire
+    bool filling = false;           // claimed, its work being enqueued (fill_batch, outside s.mu)
+    bool starved = false;           // refill deferred: the host-batch pool is at its cap
+    HostBatch *hb = nullptr;        // host side of the batch in flight
+    std::vector<DevBuf<uint8_t>> d_out;   // per decoded column
+    std::vector<DevBuf<uint8_t>> d_heap;  // per FSST column: decoded string bytes
+    std::vector<uint64_t> heap_bytes;     // per column: heap bytes of this batch
+    PinBuf<DevChunk> h_chunks;
+    DevBuf<DevChunk> d_chunks;
+    DevBuf<uint8_t> d_in;           // streamed compressed bytes of the batch (no resident image)
+    const uint8_t *in_dev = nullptr;  // device address of the batch's first compressed byte
+    PinBuf<uint8_t> h_stage;        // pinned bounce buffer when the image cannot be pinned
+    DevBuf<uint32_t> queue;         // decode work-queue counter
+    uint64_t in_base = 0;
+    hipStream_t stream = nullptr;   // one stream per slot: slot b's H2D+decode overlap slot a's D2H
+    // filtered batches (fls_scan_filter)
+    DevBuf<uint64_t> d_mask;        // selection bits, 16 words per 1024-row vector
+    DevBuf<uint32_t> d_counts;      // selected rows per vector
+    PinBuf<uint8_t> h_fdesc;        // DevTerm[] + DevOut[] + constant strings
+    DevBuf<uint8_t> d_fdesc;
+    PinBuf<DevSetTerm> h_sdesc;     // the filter's key-set terms
+    DevBuf<DevSetTerm> d_sdesc;
+    std::vector<DevBuf<uint64_t>> d_valid;  // per filtered / aggregated column with a NULL: batch validity words
+    std::vector<uint8_t> valid_staged;      // per column: d_valid[c] holds this batch's words (stage_validity)
+    std::vector<DevBuf<uint8_t>> d_narrow;  // per narrowed column: its narrowed copy
+    PinBuf<uint8_t> h_ndesc;                // DevNarrow[] + per-row-group bases
+    DevBuf<uint8_t> d_ndesc;
+    // aggregate batches (fls_aggregate)
+    PinBuf<DevAgg> h_adesc;
+    DevBuf<DevAgg> d_adesc;
+    DevBuf<AggRec> d_agg;           // partial records of the batch
+    // grouped aggregate batches (fls_aggregate_grouped)
+    PinBuf<uint8_t> h_gdesc;        // DevKey[kMaxKeys] + per row group its first vector and vector count
+    DevBuf<uint8_t> d_gdesc;
+    DevBuf<uint8_t> d_gvec;         // stage 1: the vectors' groups
+    DevBuf<uint8_t> d_grg;          // stage 2: the row groups' groups
+    // top-N batches (fls_topn)
+    PinBuf<uint32_t> h_tdesc;       // per row group its first vector and vector count
+    DevBuf<uint32_t> d_tdesc;
+    DevBuf<uint8_t> d_tvec;         // stage 1: the vectors' candidate lists
+    DevBuf<uint8_t> d_ttmp;         // stage 2: the other side of the merge tree's ping-pong
+    DevBuf<uint8_t> d_trg;          // stage 2: the row groups' candidate lists
+};
+
+// One GPU's scan pipeline: streams, the two device slots and the pinned
+// host-batch pool.  A scan borrows one per GPU from its connection
+// (ConnRes::take) and the table gives it back when it closes, so the next
+// table -- a new DuckDB query -- starts without stream creation, hipMalloc or
+// hipHostMalloc.
+constexpr size_t kIdent16 = 256;  // ScanDev::ident: where the u16 identity table starts
+
+struct ScanDev {
+    int dev = -1;
+    hipStream_t stream = nullptr;
+    uint32_t rg0 = 0, rg1 = 0;      // span of row groups this GPU owns within the scan
+    uint32_t p0 = 0, p1 = 0;        // ... as positions in ScanCtx::rgs
+    uint32_t next_p = 0;            // next position to enqueue
+    // device slots: batches in flight at once (ScanCtx::nslots of them used)
+    static constexpr int kMaxSlots = 4;
+    Slot slots[kMaxSlots];
+    std::shared_ptr<DevImage> dimg;  // the scanned file's resident image on this GPU (none: per-slot uploads)
+    std::vector<std::unique_ptr<HostBatch>> batches;  // host-batch pool of this GPU
+    std::vector<HostBatch *> free_batches;
+    DevBuf<StrT> strtab;
+    std::vector<uint64_t> strtab_off;
+    std::vector<StrT> h_strtab;     // host copy of strtab (the dictionaries coded columns reference)
+    // identity "dictionaries" a coded column gathers its codes from: u8 0..255
+    // at byte 0, u16 0..65535 at byte kIdent16
+    DevBuf<uint8_t> ident;
+    DevBuf<uint32_t> err;
+    int grid = 0;
+    ScanDev() = default;
+    ScanDev(const ScanDev &) = delete;
+    ScanDev &operator=(const ScanDev &) = delete;
+    void sync() {
+        if (dev < 0) return;
+        hipSetDevice(dev);
+        if (stream) hipStreamSynchronize(stream);
+        for (auto &sl : slots)
+            if (sl.stream) hipStreamSynchronize(sl.stream);
+    }
+    ~ScanDev() {
+        sync();
+        for (auto &sl : slots)
+            if (sl.stream) hipStreamDestroy(sl.stream);
+        if (stream) hipStreamDestroy(stream);
+    }
+};
+
+// A key set (fls_keyset_create): the host image and its copies in HBM, one
+// per GPU, made by the first scan that probes the set there.  Filters hold a
+// reference, so the handle may be freed while a filter or a scan uses the set;
+// the copies go with the last reference.  They are not resident images and do
+// not count against FLS_SCAN_RESIDENT_MB.
+struct KeySet {
+    KeysetImage img;
+    const fls_connection *conn = nullptr;
+    std::mutex mu;
+    std::vector<std::unique_ptr<DevBuf<uint64_t>>> copies;
+    // the image on GPU dev (the current device), uploaded on first use
+    hipError_t device_image(int dev, const uint64_t **out) {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto &c : copies)
+            if (c->dev == dev) {
+                *out = c->p;
+                return hipSuccess;
+            }
+        auto b = std::make_unique<DevBuf<uint64_t>>();
+        hipError_t e = b->alloc(dev, img.words.size());
+        // a synchronous copy: complete before any kernel enqueued after this call
+        if (e == hipSuccess && !img.words.empty())
+            e = hipMemcpy(b->p, img.words.data(), img.bytes(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return e;
+        *out = b->p;
+        copies.push_back(std::move(b));
+        return hipSuccess;
+    }
+};
+
+// Live key sets by handle.  A handle is a counter value, never an address:
+// a stale or foreign fls_predicate.value is looked up here and refused
+// without being dereferenced.
+struct KeySetRegistry {
+    std::mutex mu;
+    uint64_t next = 1;
+    std::unordered_map<uint64_t, std::shared_ptr<KeySet>> live;
+    static uint64_t handle_of(uint64_t id) { return (id << 4) | 0x5; }
+    std::shared_ptr<KeySet> find(uint64_t handle) {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = live.find(handle);
+        return it == live.end() ? nullptr : it->second;
+    }
+};
+KeySetRegistry &keyset_registry();  // (fls_scan_keyset.hip)
+
+// One term of a pushed-down filter (fls_scan_filter), host side.
+struct HostTerm {
+    uint32_t col = 0, clause = 0;
+    uint8_t op = 0, kind = 0;
+    uint64_t value = 0;             // comparison domain: int64 / uint64 / double bits
+    std::string str;
+    std::shared_ptr<KeySet> set;    // OP_IN_SET / OP_NOT_IN_SET
+};
+inline bool is_set_op(uint8_t op) { return op == OP_IN_SET || op == OP_NOT_IN_SET; }
+
+// One aggregate of fls_aggregate, host side.
+struct HostAgg {
+    uint8_t fn = 0;                 // AggFn
+    uint32_t col = 0, col2 = 0;
+    // SUM_EXPR: the product of the factors fk + (fneg ? -1 : +1) * column fcol
+    uint32_t nf = 0;
+    uint32_t fcol[kMaxFactors] = {};
+    uint8_t fneg[kMaxFactors] = {};
+    int64_t fk[kMaxFactors] = {};
+};
+
+// What a scan does with a batch's decoded rows instead of delivering them.
+// scan_setup sets it from the plan; everything after reads it here.
+enum class Reduce {
+    None,            // a delivering scan: the (filtered) columns go to the consumer
+    Aggregate,       // fls_aggregate: per-vector partial records (enqueue_aggregate)
+    GroupAggregate,  // fls_aggregate_grouped: per-row-group tables of groups (enqueue_group_aggregate)
+    TopN,            // fls_topn: per-row-group candidate lists (enqueue_topn)
+};
+
+// What a scan is asked to do (scan_setup).  The pointers are borrowed for the
+// call; what the scan needs later is copied into its ScanCtx.
+struct ScanPlan {
+    std::vector<int> devices;                       // the GPUs the row groups shard over
+    const uint8_t *col_mask = nullptr;              // per column: delivered (NULL: every column)
+    uint32_t rg0 = 0, rg1 = 0;                      // row groups [rg0, rg1)
+    const std::vector<HostTerm> *filter = nullptr;  // pushed-down filter (NULL: none)
+    // a consumer's scan (fls_scan_begin), which honours the table's delivery
+    // options (dictionary codes, narrowing, deferred records); fls_materialize
+    // and the scans the engine runs for itself deliver at full width
+    bool delivering_scan = false;
+    const std::vector<HostAgg> *aggs = nullptr;     // Reduce::Aggregate / GroupAggregate
+    const std::vector<uint32_t> *keys = nullptr;    // Reduce::GroupAggregate: the GROUP BY columns
+    const fls_order_key *order = nullptr;           // Reduce::TopN: the key and
+    uint32_t k = 0;                                 // ... how many rows
+    // exactly these row groups (ascending, inside the range) instead of
+    // pruning the range: fls_topn's late materialisation
+    const std::vector<uint32_t> *only = nullptr;
+};
+
+struct ScanCtx {
+    bool active = false;
+    Reduce reduce = Reduce::None;
+    std::vector<uint8_t> mask;      // delivered columns
+    std::vector<uint8_t> dmask;     // decoded columns (delivered + filter columns)
+    std::vector<HostTerm> terms;    // filter of this scan, sorted by clause (empty: none)
+    // aggregate scan (Reduce::Aggregate / GroupAggregate): no column is
+    // delivered, each batch's partial records ride in its HostBatch
+    std::vector<HostAgg> aggs;
+    // GROUP BY columns of a grouped aggregate scan (Reduce::GroupAggregate):
+    // decoded like operands, VARCHAR keys as dictionary codes
+    std::vector<uint32_t> keys;
+    // top-N scan (Reduce::TopN): no column is delivered, each batch's
+    // candidate lists ride in its HostBatch
+    fls_order_key tkey = {};
+    uint32_t tk = 0;
+    bool aggregating() const { return reduce == Reduce::Aggregate || reduce == Reduce::GroupAggregate; }
+    bool dict_codes = false;        // deliver DICT string chunks as codes + dictionary
+    bool narrow = false;            // deliver integer columns narrowed to their row groups' ranges
+    bool defer_records = false;     // FSST-as-lengths records built by fls_scan_build_records, not scan_acquire
+    std::vector<uint32_t> rgs;      // row groups to scan, in order (pruned ones left out)
+    uint32_t cur = 0;               // next position in rgs to hand out
+    uint32_t pruned = 0;
+    uint32_t batch = 8;
+    std::vector<std::unique_ptr<ScanDev>> devs;  // borrowed from the connection (ConnRes)
+    int64_t held = -1;              // row group fls_scan_next handed out last (released on the next call)
+    std::vector<std::pair<uint32_t, HostBatch *>> out;  // row groups handed out and not yet released
+    // batches whose D2H an acquire saw complete and whose slot took its next
+    // batch: (device index, batch) until their last row group is handed out
+    std::vector<std::pair<int, HostBatch *>> ready;
+    bool early_refill = true;       // FLS_SCAN_EARLY_REFILL
+    bool spin_wait = false;         // FLS_SCAN_SPIN_WAIT (A/B): acquires poll the batch event
+    uint32_t max_batches = 64;      // host-batch pool cap per GPU (FLS_SCAN_HOST_BATCHES)
+    int nslots = 2;                 // device slots per GPU (FLS_SCAN_SLOTS, 1..ScanDev::kMaxSlots)
+    // sticky error of a failed batch refill (scan_release): consumers waiting
+    // for a row group of that batch, and every later acquire, return it
+    // instead of waiting for a batch that will never be enqueued
+    int err_rc = 0;
+    std::string err_msg;
+    // fls_scan_acquire/release may be called from several consumer threads:
+    // claiming a row group, releasing one and refilling a slot happen under mu;
+    // waiting for a batch's decode does not.
+    std::mutex mu;
+    std::condition_variable cv;
+};
+
+FLS_ENGINE_END
+
+// Second stream a table decode overlaps its FSST kernels on (launch_all).
+struct SideStream {
+    hipStream_t stream = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    // CU-partitioned overlap (FLS_OVERLAP_CU_SPLIT = m): two streams whose
+    // kernels may only use disjoint CU sets -- set A (CU index mod 32 < m) for
+    // the main decode, set B for FSST -- made on first use for that m
+    int cu_m = 0;
+    hipStream_t cu_a = nullptr, cu_b = nullptr;
+    hipEvent_t join_a = nullptr, join_b = nullptr;
+    void release_cu() {
+        for (hipStream_t *st : {&cu_a, &cu_b})
+            if (*st) {
+                hipStreamSynchronize(*st);
+                hipStreamDestroy(*st);
+                *st = nullptr;
+            }
+        for (hipEvent_t *e : {&join_a, &join_b})
+            if (*e) {
+                hipEventDestroy(*e);
+                *e = nullptr;
+            }
+        cu_m = 0;
+    }
+};
+
+FLS_ENGINE_BEGIN
+
+// One GPU's part of a device-resident table (fls_device_*): a contiguous
+// range of row groups uploaded verbatim to its HBM with their string_t
+// tables, the decoded columns, the launch descriptor list and the streams and
+// events of its decode launches.  A table is split over the connection's GPUs
+// like a scan (no data crosses GPUs: row groups are independent).
+struct Resident {
+    int dev = -1;
+    uint32_t rg0 = 0, rg1 = 0;
+    uint64_t base = 0;                 // file offset of img[0]
+    uint64_t first_row = 0, rows = 0;  // resident rows, relative to the file's first row
+    DevBuf<uint8_t> img;               // compressed bytes of [rg0, rg1)
+    DevBuf<StrT> strtab;               // string_t tables of VARCHAR chunks
+    std::vector<uint64_t> strtab_off;  // per (rg - rg0) * ncols + col: index into strtab
+    DevBuf<uint32_t> err;
+    DevBuf<uint32_t> queue;                // decode work-queue counters
+    std::vector<DevBuf<uint8_t>> d_heap;   // per FSST column: decoded string bytes
+    std::vector<PinBuf<uint8_t>> h_heap;   // per FSST column: host copy string_t points into
+    std::vector<uint64_t> heap_off;        // per (rg - rg0) * ncols + col: chunk heap offset
+    std::vector<DevBuf<uint8_t>> d_out;    // per column, rows of [rg0, rg1)
+    double placement_q = 0;                // write-probe rating of d_out's placement (choose_placement; 0: not rated)
+    float placement_ms = 0;                // decode-time rating of d_out's placement (0: not rated)
+    DevBuf<DevChunk> d_chunks;
+    std::vector<DevChunk> h_chunks;
+    std::vector<uint8_t> mask;         // column mask h_chunks was built for
+    uint32_t nmain = 0;                // h_chunks[0, nmain) main kernel, the rest FSST
+    DevBuf<DictVec> d_dictvecs;        // the dictionary-string grid's vectors (launch_dictstr), built with h_chunks
+    uint32_t ndictvecs = 0;            // ... and how many (their chunks are not in h_chunks)
+    bool list_built = false;           // h_chunks / d_dictvecs describe the current mask, policy and outputs
+    void invalidate() {                // a new mask, policy or set of outputs: rebuild both at the next decode
+        h_chunks.clear();
+        ndictvecs = 0;
+        list_built = false;
+    }
+    int64_t policy = -1;               // decode_policy() h_chunks was ordered for
+    int64_t lpolicy = 0;                // ... and the launch policy it resolved to (launch_policy)
+    FsstCounts fsst;                   // FSST chunks of h_chunks
+    SplitPlan split;                   // balanced split after h_chunks on the device (waves 0: none)
+    ByteCount bytes;                   // algorithmic bytes of one launch
+    hipStream_t stream = nullptr;
+    SideStream side;                   // FSST kernels overlapping the main decode kernel
+    std::vector<hipEvent_t> ev_pool;   // per-launch (start, stop) pairs since last sync
+    uint32_t ev_used = 0;
+    Resident() = default;
+    Resident(const Resident &) = delete;
+    Resident &operator=(const Resident &) = delete;
+    ~Resident() {
+        if (dev < 0) return;
+        hipSetDevice(dev);
+        if (stream) hipStreamSynchronize(stream);
+        if (side.stream) hipStreamSynchronize(side.stream);
+        if (stream) hipStreamDestroy(stream);
+        if (side.stream) hipStreamDestroy(side.stream);
+        if (side.fork) hipEventDestroy(side.fork);
+        if (side.join) hipEventDestroy(side.join);
+        side.release_cu();
+        for (auto e : ev_pool) hipEventDestroy(e);
+    }
+};
+
+FLS_ENGINE_END
+
+struct fls_table {
+    std::vector<int> devices;          // the connection's GPUs (row groups shard over them)
+    std::shared_ptr<MappedFile> mapped;  // fls_read_fls: the file and its validated metadata (shared)
+    std::shared_ptr<fls::engine::ConnRes> res;  // the connection's scan resources (outlive a disconnect)
+    std::vector<uint8_t> owned;
+    const uint8_t *img = nullptr;
+    uint64_t len = 0;
+    fls::FileMeta meta;
+    std::vector<std::string> names;
+    bool registered = false;        // img pinned with hipHostRegister (FLS_SCAN_PIN=1)
+    bool pin_tried = false;
+    void *map = nullptr;            // fls_read_fls: the file, mapped read-only
+    size_t map_len = 0;
+
+    // device-resident mode: one part per GPU (fls_device_upload)
+    std::vector<std::unique_ptr<fls::engine::Resident>> resident;
+    uint32_t launches = 0;
+
+    fls::engine::ScanCtx scan, mat;
+    std::vector<fls::engine::HostTerm> filter;  // fls_scan_filter: applies to the next fls_scan_begin / fls_aggregate
+    std::vector<fls_agg_expr> exprs;  // fls_aggregate_exprs: what FLS_AGG_SUM_EXPR's spec.col indexes
+    bool dict_codes = false;        // fls_scan_dict_codes: applies to the next fls_scan_begin
+    bool narrow = false;            // fls_scan_narrow: applies to the next fls_scan_begin
+    bool defer_records = false;     // fls_scan_defer_records: applies to the next fls_scan_begin
+    bool profiled = false;          // scanned with FLS_SCAN_PROFILE=1 (prints the totals at close)
+    ~fls_table();
+};
+
+FLS_ENGINE_BEGIN
+
+// ---- columns and chunks (flsgpu.hip) ----------------------------------------
+
+int out_bytes_of(const fls_table *t, uint32_t c);
+// FK_FLOAT / FK_INT / FK_UINT of (non-string) column c, as the filter, aggregate and top-N kernels compare it
+uint8_t col_kind(const fls_table *t, uint32_t c);
+bool is_fsst(const fls_table *t, uint32_t rg, uint32_t c);
+// [rg0, rg1) inside the table, or FLS_ERR_ARG "<prefix>row-group range [rg0,rg1) out of bounds"
+int check_rowgroup_range(const fls_table *t, uint32_t rg0, uint32_t rg1, const char *prefix);
+int build_strtabs(const fls_table *t, int dev, uint32_t rg0, uint32_t rg1, DevBuf<StrT> &tab,
+                  std::vector<uint64_t> &offs, std::vector<StrT> &host);
+DevChunk make_devchunk(const fls_table *t, uint32_t rg, uint32_t col, const uint8_t *d_chunk, const uint8_t *d_dict,
+                       uint8_t *d_out, ByteCount *bc, uint8_t *d_heap = nullptr, const uint8_t *h_heap = nullptr,
+                       uint32_t code_w = 0, const uint8_t *d_ident = nullptr);
+
+// ---- launch policy and launches (flsgpu.hip) ---------------------------------
+
+constexpr uint32_t kQueueWords = 1 + kFsstGroups;  // launch_all's d_queue
+int64_t decode_policy();
+int64_t launch_policy(int64_t policy, const std::vector<DevChunk> &v, DecodeGeom &geom);
+uint32_t order_for_launch(std::vector<DevChunk> &v, FsstCounts *fc, int64_t policy,
+                          std::vector<DevChunk> *dictwg = nullptr);
+SplitPlan append_split(std::vector<DevChunk> &list, uint32_t nmain, const DecodeGeom &geom, int64_t policy);
+int fsst_config_check(int64_t policy);
+hipError_t launch_all(const DevChunk *d_chunks, uint32_t nmain, uint32_t ntotal, const FsstCounts &fc,
+                      uint32_t *d_err, const DecodeGeom &geom, hipStream_t stream, uint32_t *d_queue, int64_t policy,
+                      SplitPlan plan, const SideStream *side = nullptr, const DictVec *d_dictvecs = nullptr,
+                      uint32_t ndictvecs = 0);
+
+// ---- the scan pipeline (flsgpu.hip) -------------------------------------------
+
+bool rowgroup_may_match(const fls_table *t, uint32_t rg, const std::vector<HostTerm> &terms);
+bool topn_key_type(const ColumnMeta &c);
+uint32_t select_rowgroups(const fls_table *t, const std::vector<HostTerm> &terms, const fls_order_key *order, uint32_t k,
+                          uint32_t rg0, uint32_t rg1, std::vector<uint32_t> &rgs);
+int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &plan);
+int scan_start(fls_table *t, ScanCtx &s);
+int scan_next(fls_table *t, ScanCtx &s, fls_rowgroup *out);
+// The host batch that holds row group rg, which scan s has handed out.
+const HostBatch *held_batch(ScanCtx &s, uint32_t rg);
+int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);
+// Per row group of the slot's batch its (first vector, vector count) within
+// the batch into tab[2 * sl.nrg], and the most vectors one of them has (at
+// least 1) into rg_vecs; fails when they do not fit the batch's hb.nvec vectors.
+int rg_vec_table(const fls_table *t, const Slot &sl, uint32_t *tab, uint32_t &rg_vecs);
+
+// ---- a batch's reduction, by ScanCtx::reduce (fill_batch calls one) ---------------
+
+int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);        // fls_scan_agg.hip
+int enqueue_group_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);  // fls_scan_agg.hip
+int enqueue_topn(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);             // fls_scan_topn.hip
+
+// A reducing scan on the table's scan context under its filter: nothing is
+// delivered; fold(rg, hb) sees every surviving row group once, in scan order,
+// with the host batch that holds its partial results, and returns 0 or the
+// error that ends the scan.  plan names the range and the reduction; `what`
+// ("aggregate", "top-N") goes into the internal error of a missing batch.
+template <class Fold>
+int reduce_scan(fls_table *t, ScanPlan plan, const char *what, Fold &&fold) {
+    const std::vector<uint8_t> none(std::max<size_t>(1, t->meta.cols.size()), 0);  // nothing is delivered
+    plan.devices = t->devices;
+    plan.col_mask = none.data();
+    plan.filter = &t->filter;
+    ScanCtx &s = t->scan;
+    int rc = scan_setup(t, s, plan);
+    if (!rc) rc = scan_start(t, s);
+    if (rc) return rc;
+    fls_rowgroup rg;
+    while ((rc = scan_next(t, s, &rg)) == 1) {
+        const HostBatch *hb = held_batch(s, rg.rowgroup);
+        if (!hb) return fail(FLS_ERR_STATE, "internal: %s batch of row group %u not found", what, rg.rowgroup);
+        if (const int frc = fold(rg, *hb)) return frc;
+    }
+    return rc < 0 ? rc : 0;
+}
+
+FLS_ENGINE_END

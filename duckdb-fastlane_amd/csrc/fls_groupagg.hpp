@@ -8,7 +8,7 @@
 // with fls_agg.hip's reduction order; stage 2 (one block per row group) merges
 // the vectors' keys, in vector order, into the row group's table and folds
 // their records.  The host merges the row groups' tables by key VALUE
-// (flsgpu.hip): a dictionary code means a string of its row group only.
+// (fls_scan_agg.hip): a dictionary code means a string of its row group only.
 //
 // Packed key (<= 128 bits): key q's value -- the decoded column's raw bytes,
 // or a DICT VARCHAR chunk's code in 16 bits -- at bit DevKey::shift, and one

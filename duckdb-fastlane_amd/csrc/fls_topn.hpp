@@ -15,7 +15,7 @@
 // and leaves its best min(k, eligible) records; stage 2 (topn_merge_kernel, one
 // launch per level of a pairwise tree) merges the vectors of each row group
 // into the row group's best k, and those lists -- 16 + 16 k bytes per row group -- are the
-// batch's only D2H.  The host merges the row groups' lists (flsgpu.hip).  A row
+// batch's only D2H.  The host merges the row groups' lists (fls_scan_topn.hip).  A row
 // is eligible when the mask selects it (or, without a mask, always) and it
 // lies below the batch's row count; the value at a NULL key is a placeholder
 // and is never loaded.

@@ -1,14 +1,23 @@
-// flsgpu.hip -- host engine behind include/flsgpu.h.
+// flsgpu.hip -- host engine behind include/flsgpu.h: connections, files and
+// the scan pipeline.
 //
 // Replaces FastLanes' connect/read_fls/get_rowgroup_reader/materialize
 // (reference src/fastlanes_facade.cpp:33-56) with:
 //   * footer parse on the host (fls_reader.hpp) -- no GPU needed for schema;
-//   * device-resident mode: a shard of row groups is uploaded verbatim to HBM
-//     and decoded by ONE fused kernel launch per pass (bench / roofline);
 //   * streaming scan: row groups sharded contiguously over the connection's
 //     GPUs (no collectives: row groups are independent); per
 //     GPU a two-slot pipeline H2D(compressed batch) -> decode -> D2H(pinned)
-//     runs ahead of the consumer (DuckDB's scan thread).
+//     runs ahead of the consumer (DuckDB's scan thread);
+//   * the launch policy every decode goes through (order_for_launch,
+//     launch_all), a scan's batches and a device-resident table alike.
+//
+// The rest of the engine is in units of its own, over the types and
+// declarations of fls_engine.hpp: what a scan does with a batch instead of
+// delivering it (ScanCtx::reduce) in fls_scan_agg.hip and fls_scan_topn.hip,
+// key sets in fls_scan_keyset.hip, and the device-resident mode (a shard of
+// row groups uploaded verbatim to HBM and decoded by one fused launch per
+// pass: bench / roofline) in fls_device_table.hip.  What those units call here
+// is declared in fls_engine.hpp; every other function of this file is static.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -16,54 +25,14 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <algorithm>
-#include <atomic>
-#include <condition_variable>
-#include <cstring>
-#include <map>
-#include <mutex>
-#include <memory>
-#include <string>
-#include <chrono>
-#include <cmath>
-#include <thread>
-#include <unordered_map>
-#include <vector>
-
-#include "../../include/flsgpu.h"
-#include "fls_agg.hpp"
-#include "fls_common.hpp"
-#include "fls_config.hpp"
-#include "fls_decode.hpp"
-#include "fls_filter.hpp"
-#include "fls_format.hpp"
-#include "fls_groupagg.hpp"
-#include "fls_keyset.hpp"
-#include "fls_pinned.hpp"
-#include "fls_reader.hpp"
-#include "fls_resident.hpp"
-#include "fls_topn.hpp"
+#include "fls_engine.hpp"
 
 using namespace fls;
+using namespace fls::engine;
 
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(FLS_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                        __LINE__);                                                                 \
-    } while (0)
+FLS_ENGINE_BEGIN
 
-namespace {
-
-// DuckDB v1.3.2 string_t (16 B): len <= 12 inlined, else 4-byte prefix + pointer
-struct StrT {
-    uint32_t len;
-    char data[12];
-};
-static_assert(sizeof(StrT) == 16, "string_t is 16 B");
-
-StrT make_string_t(const char *p, uint32_t n) {
+static StrT make_string_t(const char *p, uint32_t n) {
     StrT s;
     memset(&s, 0, sizeof(s));
     s.len = n;
@@ -76,130 +45,10 @@ StrT make_string_t(const char *p, uint32_t n) {
     return s;
 }
 
-// Scan set-up profile (FLS_SCAN_PROFILE=1): process-wide time and bytes per
-// phase, printed to stderr when a table that scanned closes -- where a cold
-// query's first milliseconds go (pinned and device allocations, string_t
-// tables, the resident image, staging copies, the consumers' waits), and
-// per batch on the GPU (HIP events on the slot's stream: the decode kernels,
-// then the D2H of its columns; batches of different slots overlap, so these
-// are summed stream time, not wall time).
-enum ProfPhase {
-    PROF_PIN_ALLOC, PROF_DEV_ALLOC, PROF_SETUP, PROF_STRTABS, PROF_IMAGE, PROF_STAGE_COPY, PROF_FILL, PROF_FILL_DESC,
-    PROF_FILL_LIST, PROF_REFILL_LAT, PROF_WAIT, PROF_GPU_DECODE, PROF_D2H, PROF_N
-};
-struct ScanProf {
-    std::atomic<uint64_t> ns[PROF_N] = {}, bytes[PROF_N] = {}, calls[PROF_N] = {};
-    static bool on() {
-        static const bool e = getenv("FLS_SCAN_PROFILE") && atoi(getenv("FLS_SCAN_PROFILE")) != 0;
-        return e;
-    }
-    void print() {
-        static const char *names[PROF_N] = {"pinned host alloc", "device alloc", "scan_setup", "string_t tables",
-                                            "resident image", "staging copy", "fill_batch (all)",
-                                            "fill: descriptors", "fill: chunk list", "batch seen -> refill",
-                                            "consumer wait",
-                                            "GPU decode (events)", "D2H (events)"};
-        fprintf(stderr, "FLS_SCAN_PROFILE (process, since the last report):\n");
-        for (int i = 0; i < PROF_N; ++i)
-            fprintf(stderr, "  %-20s %9.3f ms  %8llu calls  %10.1f MB\n", names[i], ns[i].exchange(0) / 1e6,
-                    (unsigned long long)calls[i].exchange(0), bytes[i].exchange(0) / 1e6);
-    }
-};
 ScanProf &scan_prof() {
     static auto *p = new ScanProf();
     return *p;
 }
-struct ProfTimer {
-    int ph;
-    uint64_t b;
-    std::chrono::steady_clock::time_point t0;
-    explicit ProfTimer(int phase, uint64_t bytes = 0) : ph(ScanProf::on() ? phase : -1), b(bytes) {
-        if (ph >= 0) t0 = std::chrono::steady_clock::now();
-    }
-    void stop() {  // record now (once)
-        if (ph < 0) return;
-        ScanProf &p = scan_prof();
-        p.ns[ph] += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-        p.bytes[ph] += b;
-        p.calls[ph] += 1;
-        ph = -1;
-    }
-    void cancel() { ph = -1; }
-    ~ProfTimer() { stop(); }
-};
-
-// Frees every HBM-resident image no running scan uses on GPU dev (defined
-// with the image registry); a device allocation that runs out of memory calls
-// it once and retries, so the image cache never fails a scan's own buffers.
-uint64_t release_idle_images(int dev);
-
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    int dev = -1;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n), dev(o.dev) { o.p = nullptr; o.n = 0; }
-    void release() {
-        if (p) {
-            int cur;
-            hipGetDevice(&cur);
-            hipSetDevice(dev);
-            hipFree(p);
-            hipSetDevice(cur);
-        }
-        p = nullptr;
-        n = 0;
-    }
-    hipError_t alloc(int d, size_t count) {
-        if (count <= n && p && d == dev) return hipSuccess;
-        release();
-        dev = d;
-        n = count;
-        ProfTimer pt(PROF_DEV_ALLOC, count * sizeof(T));
-        hipError_t e = hipMalloc((void **)&p, std::max<size_t>(1, count * sizeof(T)));
-        if (e == hipErrorOutOfMemory && release_idle_images(d) > 0) {
-            (void)hipGetLastError();
-            e = hipMalloc((void **)&p, std::max<size_t>(1, count * sizeof(T)));
-        }
-        if (e != hipSuccess) {
-            p = nullptr;
-            n = 0;
-        }
-        return e;
-    }
-    ~DevBuf() { release(); }
-};
-
-template <typename T>
-struct PinBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    PinBuf() = default;
-    PinBuf(const PinBuf &) = delete;
-    PinBuf &operator=(const PinBuf &) = delete;
-    PinBuf(PinBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
-    void release() {
-        if (p) pinned_free(p);
-        p = nullptr;
-        n = 0;
-    }
-    hipError_t alloc(size_t count) {
-        if (count <= n && p) return hipSuccess;
-        release();
-        n = count;
-        ProfTimer pt(PROF_PIN_ALLOC, count * sizeof(T));
-        const hipError_t e = pinned_alloc((void **)&p, std::max<size_t>(1, count * sizeof(T)));
-        if (e != hipSuccess) {
-            p = nullptr;
-            n = 0;
-        }
-        return e;
-    }
-    ~PinBuf() { release(); }
-};
 
 // Host threads that split a large memcpy: a scan stages each batch's
 // compressed bytes from the mapped file into pinned memory for its H2D
@@ -283,42 +132,6 @@ class CopyPool {
     bool started_ = false, stop_ = false;
 };
 
-}  // namespace
-
-struct DevImage;  // a file's compressed image resident in HBM (defined with MappedFile)
-namespace {
-
-// Device images are allocated this much past their last chunk: kernels read
-// whole 16 B blocks of a stream whose last block may end inside it.
-constexpr uint64_t kImagePad = 256;
-
-// FSST chunks of a launch, one kernel group after another (order_for_launch):
-// 0 = segment tables and every string <= 255 bytes, 1 = segment tables,
-// 2 = strings <= 255 bytes, 3 = the rest (DevChunk.vbits: bit 0 = small
-// strings, bit 1 = segment tables); each group numbers its vectors through
-// DevChunk.vec_base.
-constexpr int kFsstGroups = 4;
-inline int fsst_group(uint8_t vbits) { return vbits == 3 ? 0 : vbits == 2 ? 1 : vbits == 1 ? 2 : 3; }
-struct FsstCounts {
-    uint32_t n[kFsstGroups] = {}, vecs[kFsstGroups] = {};
-    uint32_t first(int g) const {
-        uint32_t f = 0;
-        for (int k = 0; k < g; ++k) f += n[k];
-        return f;
-    }
-    uint64_t total_vecs() const {
-        uint64_t t = 0;
-        for (int k = 0; k < kFsstGroups; ++k) t += vecs[k];
-        return t;
-    }
-};
-
-// Per-chunk algorithmic byte accounting (roofline numerator).
-struct ByteCount {
-    uint64_t values = 0, packed = 0, meta = 0, out = 0;
-    DecodeGeom geom;   // max LDS need over the counted chunks
-};
-
 // Byte range of the file covering row groups [rg0, rg1).
 void rg_byte_range(const FileMeta &m, uint32_t rg0, uint32_t rg1, uint64_t &lo, uint64_t &hi) {
     lo = UINT64_MAX;
@@ -331,289 +144,15 @@ void rg_byte_range(const FileMeta &m, uint32_t rg0, uint32_t rg1, uint64_t &lo, 
     lo &= ~uint64_t(255);
 }
 
-// Pinned host side of one decoded batch: what consumers read.  It belongs to
-// the batch's row groups, not to the device slot that produced it: once every
-// row group of the batch has been handed out (fls_scan_acquire) the slot is
-// refilled with a fresh HostBatch from the pool, and this one goes back to the
-// pool when the last of its row groups is released.  So a consumer that keeps
-// a row group (DuckDB vectors that reference the pinned columns) never holds
-// up the GPU pipeline, and no consumer waits for another one's release.
-struct HostBatch {
-    uint32_t rg0 = 0, nrg = 0;
-    uint32_t handed = 0, released = 0;    // row groups handed out / handed back
-    std::vector<PinBuf<uint8_t>> h_out;   // per delivered column (pinned)
-    std::vector<PinBuf<uint8_t>> h_heap;  // per FSST column: pinned copy string_t points into
-    std::vector<const void *> col_ptrs;   // per (rg - rg0) * ncols + col: pinned host column start
-    PinBuf<uint32_t> h_counts;            // filtered: selected rows per vector
-    PinBuf<uint32_t> h_sel;               // filtered: selected row indices within their row group
-    uint32_t nvec = 0;                    // vectors of the batch
-    bool sel_ready = false;               // sel_off computed from h_counts
-    std::vector<uint32_t> sel_off;        // per row group of the batch (+1): first selected row
-    // per (rg - rg0) * ncols + col: the delivered rows' validity words (NULL:
-    // all valid) -- the file image's bitmaps, or, filtered, gathered into vbits
-    std::vector<const uint64_t *> valid_ptrs;
-    std::vector<std::vector<uint64_t>> vbits;
-    // dictionary-coded delivery (fls_scan_dict_codes): per column the bytes
-    // delivered per row (string_t 16, or a code width 1 / 2), per (rg - rg0) *
-    // ncols + col the host string_t dictionary and its size (NULL: not coded)
-    std::vector<uint8_t> ob;
-    std::vector<const void *> dict_ptrs;
-    std::vector<uint32_t> dict_sizes;
-    // narrowed delivery (fls_scan_narrow): per column 1 when it crosses PCIe
-    // as value - base in ob bytes, per (rg - rg0) * ncols + col that base
-    std::vector<uint8_t> narrowed;
-    std::vector<uint64_t> nbase;
-    // FSST columns delivered as string lengths (fls_scan_narrow, unfiltered
-    // scans): per column the length width (0: string_t records cross PCIe);
-    // per (rg - rg0) * ncols + col the row group's heap offset in h_heap; the
-    // string_t records rebuilt on the consumer's thread (scan_acquire) into
-    // h_rec; narrow_out = narrowed with these columns cleared (the consumer
-    // sees string_t)
-    std::vector<uint8_t> strlen_w, narrow_out, ob_out;
-    std::vector<uint64_t> heap_off;
-    std::vector<std::unique_ptr<uint8_t[]>> h_rec;
-    std::vector<uint64_t> h_rec_cap;      // rows h_rec[c] holds
-    // completion of the batch's device work, per batch rather than per slot:
-    // the slot takes its next batch as soon as this one's D2H is complete (its
-    // first acquire), while consumers still take this one's row groups
-    hipEvent_t done = nullptr;            // recorded after the D2H (fill_batch)
-    hipEvent_t pt[3] = {};                // FLS_SCAN_PROFILE: decode start, D2H start, end (timing events)
-    uint64_t prof_d2h = 0;                // ... and the batch's D2H bytes
-    std::atomic<bool> prof_pending{false};  // the batch's times not yet counted (its first acquire does)
-    std::atomic<bool> upload_resident{false};  // the batch uploads into the resident image (marked present once done)
-    PinBuf<uint32_t> h_err;               // the device error flags, copied after the batch's kernels
-    PinBuf<AggRec> h_agg;                 // aggregate scan: nvec x naggs partial records (vector-major)
-    // grouped aggregate scan: per row group of the batch its table of groups
-    // (fls_groupagg.hpp, group_rg_stride(naggs, g_nfsum, g_rg_vecs) bytes each)
-    PinBuf<uint8_t> h_grp;
-    uint32_t g_nfsum = 0, g_rg_vecs = 0;
-    // top-N scan: per row group of the batch its list of candidates
-    // (fls_topn.hpp, topn_stride(k) bytes each)
-    PinBuf<uint8_t> h_topn;
-    HostBatch() = default;
-    HostBatch(const HostBatch &) = delete;
-    HostBatch &operator=(const HostBatch &) = delete;
-    ~HostBatch() {
-        if (done) hipEventDestroy(done);
-        for (hipEvent_t e : pt)
-            if (e) hipEventDestroy(e);
-    }
-};
-
-struct Slot {                       // one batch of row groups in flight
-    uint32_t rg0 = 0, nrg = 0;      // absolute row groups (consecutive, all surviving pruning)
-    bool busy = false;              // a batch is enqueued and its D2H not yet seen complete by an acquire
-    bool filling = false;           // claimed, its work being enqueued (fill_batch, outside s.mu)
-    bool starved = false;           // refill deferred: the host-batch pool is at its cap
-    HostBatch *hb = nullptr;        // host side of the batch in flight
-    std::vector<DevBuf<uint8_t>> d_out;   // per decoded column
-    std::vector<DevBuf<uint8_t>> d_heap;  // per FSST column: decoded string bytes
-    std::vector<uint64_t> heap_bytes;     // per column: heap bytes of this batch
-    PinBuf<DevChunk> h_chunks;
-    DevBuf<DevChunk> d_chunks;
-    DevBuf<uint8_t> d_in;           // streamed compressed bytes of the batch (no resident image)
-    const uint8_t *in_dev = nullptr;  // device address of the batch's first compressed byte
-    PinBuf<uint8_t> h_stage;        // pinned bounce buffer when the image cannot be pinned
-    DevBuf<uint32_t> queue;         // decode work-queue counter
-    uint64_t in_base = 0;
-    hipStream_t stream = nullptr;   // one stream per slot: slot b's H2D+decode overlap slot a's D2H
-    // filtered batches (fls_scan_filter)
-    DevBuf<uint64_t> d_mask;        // selection bits, 16 words per 1024-row vector
-    DevBuf<uint32_t> d_counts;      // selected rows per vector
-    PinBuf<uint8_t> h_fdesc;        // DevTerm[] + DevOut[] + constant strings
-    DevBuf<uint8_t> d_fdesc;
-    PinBuf<DevSetTerm> h_sdesc;     // the filter's key-set terms
-    DevBuf<DevSetTerm> d_sdesc;
-    std::vector<DevBuf<uint64_t>> d_valid;  // per filtered / aggregated column with a NULL: batch validity words
-    std::vector<uint8_t> valid_staged;      // per column: d_valid[c] holds this batch's words (stage_validity)
-    std::vector<DevBuf<uint8_t>> d_narrow;  // per narrowed column: its narrowed copy
-    PinBuf<uint8_t> h_ndesc;                // DevNarrow[] + per-row-group bases
-    DevBuf<uint8_t> d_ndesc;
-    // aggregate batches (fls_aggregate)
-    PinBuf<DevAgg> h_adesc;
-    DevBuf<DevAgg> d_adesc;
-    DevBuf<AggRec> d_agg;           // partial records of the batch
-    // grouped aggregate batches (fls_aggregate_grouped)
-    PinBuf<uint8_t> h_gdesc;        // DevKey[kMaxKeys] + per row group its first vector and vector count
-    DevBuf<uint8_t> d_gdesc;
-    DevBuf<uint8_t> d_gvec;         // stage 1: the vectors' groups
-    DevBuf<uint8_t> d_grg;          // stage 2: the row groups' groups
-    // top-N batches (fls_topn)
-    PinBuf<uint32_t> h_tdesc;       // per row group its first vector and vector count
-    DevBuf<uint32_t> d_tdesc;
-    DevBuf<uint8_t> d_tvec;         // stage 1: the vectors' candidate lists
-    DevBuf<uint8_t> d_ttmp;         // stage 2: the other side of the merge tree's ping-pong
-    DevBuf<uint8_t> d_trg;          // stage 2: the row groups' candidate lists
-};
-
-// One GPU's scan pipeline: streams, the two device slots and the pinned
-// host-batch pool.  A scan borrows one per GPU from its connection
-// (ConnRes::take) and the table gives it back when it closes, so the next
-// table -- a new DuckDB query -- starts without stream creation, hipMalloc or
-// hipHostMalloc.
-constexpr size_t kIdent16 = 256;  // ScanDev::ident: where the u16 identity table starts
-
-struct ScanDev {
-    int dev = -1;
-    hipStream_t stream = nullptr;
-    uint32_t rg0 = 0, rg1 = 0;      // span of row groups this GPU owns within the scan
-    uint32_t p0 = 0, p1 = 0;        // ... as positions in ScanCtx::rgs
-    uint32_t next_p = 0;            // next position to enqueue
-    // device slots: batches in flight at once (ScanCtx::nslots of them used)
-    static constexpr int kMaxSlots = 4;
-    Slot slots[kMaxSlots];
-    std::shared_ptr<DevImage> dimg;  // the scanned file's resident image on this GPU (none: per-slot uploads)
-    std::vector<std::unique_ptr<HostBatch>> batches;  // host-batch pool of this GPU
-    std::vector<HostBatch *> free_batches;
-    DevBuf<StrT> strtab;
-    std::vector<uint64_t> strtab_off;
-    std::vector<StrT> h_strtab;     // host copy of strtab (the dictionaries coded columns reference)
-    // identity "dictionaries" a coded column gathers its codes from: u8 0..255
-    // at byte 0, u16 0..65535 at byte kIdent16
-    DevBuf<uint8_t> ident;
-    DevBuf<uint32_t> err;
-    int grid = 0;
-    ScanDev() = default;
-    ScanDev(const ScanDev &) = delete;
-    ScanDev &operator=(const ScanDev &) = delete;
-    void sync() {
-        if (dev < 0) return;
-        hipSetDevice(dev);
-        if (stream) hipStreamSynchronize(stream);
-        for (auto &sl : slots)
-            if (sl.stream) hipStreamSynchronize(sl.stream);
-    }
-    ~ScanDev() {
-        sync();
-        for (auto &sl : slots)
-            if (sl.stream) hipStreamDestroy(sl.stream);
-        if (stream) hipStreamDestroy(stream);
-    }
-};
-
-// A key set (fls_keyset_create): the host image and its copies in HBM, one
-// per GPU, made by the first scan that probes the set there.  Filters hold a
-// reference, so the handle may be freed while a filter or a scan uses the set;
-// the copies go with the last reference.  They are not resident images and do
-// not count against FLS_SCAN_RESIDENT_MB.
-struct KeySet {
-    KeysetImage img;
-    const fls_connection *conn = nullptr;
-    std::mutex mu;
-    std::vector<std::unique_ptr<DevBuf<uint64_t>>> copies;
-    // the image on GPU dev (the current device), uploaded on first use
-    hipError_t device_image(int dev, const uint64_t **out) {
-        std::lock_guard<std::mutex> lk(mu);
-        for (auto &c : copies)
-            if (c->dev == dev) {
-                *out = c->p;
-                return hipSuccess;
-            }
-        auto b = std::make_unique<DevBuf<uint64_t>>();
-        hipError_t e = b->alloc(dev, img.words.size());
-        // a synchronous copy: complete before any kernel enqueued after this call
-        if (e == hipSuccess && !img.words.empty())
-            e = hipMemcpy(b->p, img.words.data(), img.bytes(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return e;
-        *out = b->p;
-        copies.push_back(std::move(b));
-        return hipSuccess;
-    }
-};
-
-// Live key sets by handle.  A handle is a counter value, never an address:
-// a stale or foreign fls_predicate.value is looked up here and refused
-// without being dereferenced.
-struct KeySetRegistry {
-    std::mutex mu;
-    uint64_t next = 1;
-    std::unordered_map<uint64_t, std::shared_ptr<KeySet>> live;
-    static uint64_t handle_of(uint64_t id) { return (id << 4) | 0x5; }
-    std::shared_ptr<KeySet> find(uint64_t handle) {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = live.find(handle);
-        return it == live.end() ? nullptr : it->second;
-    }
-};
-KeySetRegistry &keyset_registry() {
-    static auto *r = new KeySetRegistry();
-    return *r;
-}
-
-// One term of a pushed-down filter (fls_scan_filter), host side.
-struct HostTerm {
-    uint32_t col = 0, clause = 0;
-    uint8_t op = 0, kind = 0;
-    uint64_t value = 0;             // comparison domain: int64 / uint64 / double bits
-    std::string str;
-    std::shared_ptr<KeySet> set;    // OP_IN_SET / OP_NOT_IN_SET
-};
-inline bool is_set_op(uint8_t op) { return op == OP_IN_SET || op == OP_NOT_IN_SET; }
-
-// One aggregate of fls_aggregate, host side.
-struct HostAgg {
-    uint8_t fn = 0;                 // AggFn
-    uint32_t col = 0, col2 = 0;
-    // SUM_EXPR: the product of the factors fk + (fneg ? -1 : +1) * column fcol
-    uint32_t nf = 0;
-    uint32_t fcol[kMaxFactors] = {};
-    uint8_t fneg[kMaxFactors] = {};
-    int64_t fk[kMaxFactors] = {};
-};
-
-struct ScanCtx {
-    bool active = false;
-    std::vector<uint8_t> mask;      // delivered columns
-    std::vector<uint8_t> dmask;     // decoded columns (delivered + filter columns)
-    std::vector<HostTerm> terms;    // filter of this scan, sorted by clause (empty: none)
-    // aggregate scan (fls_aggregate; empty: a delivering scan): no column is
-    // delivered, each batch's partial records ride in its HostBatch
-    std::vector<HostAgg> aggs;
-    // GROUP BY columns of a grouped aggregate scan (fls_aggregate_grouped;
-    // empty: ungrouped): decoded like operands, VARCHAR keys as dictionary codes
-    std::vector<uint32_t> keys;
-    // top-N scan (fls_topn; tk == 0: none): no column is delivered, each
-    // batch's candidate lists ride in its HostBatch
-    fls_order_key tkey = {};
-    uint32_t tk = 0;
-    bool dict_codes = false;        // deliver DICT string chunks as codes + dictionary
-    bool narrow = false;            // deliver integer columns narrowed to their row groups' ranges
-    bool defer_records = false;     // FSST-as-lengths records built by fls_scan_build_records, not scan_acquire
-    std::vector<uint32_t> rgs;      // row groups to scan, in order (pruned ones left out)
-    uint32_t cur = 0;               // next position in rgs to hand out
-    uint32_t pruned = 0;
-    uint32_t batch = 8;
-    std::vector<std::unique_ptr<ScanDev>> devs;  // borrowed from the connection (ConnRes)
-    int64_t held = -1;              // row group fls_scan_next handed out last (released on the next call)
-    std::vector<std::pair<uint32_t, HostBatch *>> out;  // row groups handed out and not yet released
-    // batches whose D2H an acquire saw complete and whose slot took its next
-    // batch: (device index, batch) until their last row group is handed out
-    std::vector<std::pair<int, HostBatch *>> ready;
-    bool early_refill = true;       // FLS_SCAN_EARLY_REFILL
-    bool spin_wait = false;         // FLS_SCAN_SPIN_WAIT (A/B): acquires poll the batch event
-    uint32_t max_batches = 64;      // host-batch pool cap per GPU (FLS_SCAN_HOST_BATCHES)
-    int nslots = 2;                 // device slots per GPU (FLS_SCAN_SLOTS, 1..ScanDev::kMaxSlots)
-    // sticky error of a failed batch refill (scan_release): consumers waiting
-    // for a row group of that batch, and every later acquire, return it
-    // instead of waiting for a batch that will never be enqueued
-    int err_rc = 0;
-    std::string err_msg;
-    // fls_scan_acquire/release may be called from several consumer threads:
-    // claiming a row group, releasing one and refilling a slot happen under mu;
-    // waiting for a batch's decode does not.
-    std::mutex mu;
-    std::condition_variable cv;
-};
-
 // Pinned bytes a host batch holds (its columns, FSST heaps, selection).
-size_t pinned_bytes(const HostBatch &b) {
+static size_t pinned_bytes(const HostBatch &b) {
     size_t t = b.h_counts.n * sizeof(uint32_t) + b.h_sel.n * sizeof(uint32_t) + b.h_agg.n * sizeof(AggRec) + b.h_grp.n +
                b.h_topn.n;
     for (auto &x : b.h_out) t += x.n;
     for (auto &x : b.h_heap) t += x.n;
     return t;
 }
-size_t pinned_bytes(const ScanDev &d) {
+static size_t pinned_bytes(const ScanDev &d) {
     size_t t = 0;
     for (auto &b : d.batches) t += pinned_bytes(*b);
     for (auto &sl : d.slots)
@@ -705,101 +244,13 @@ struct ConnRes {
     }
 };
 
-}  // namespace
+FLS_ENGINE_END
 
 struct fls_connection {
     std::vector<int> devices;
     std::shared_ptr<ConnRes> res = std::make_shared<ConnRes>();
 };
 
-// Second stream a table decode overlaps its FSST kernels on (launch_all).
-struct SideStream {
-    hipStream_t stream = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    // CU-partitioned overlap (FLS_OVERLAP_CU_SPLIT = m): two streams whose
-    // kernels may only use disjoint CU sets -- set A (CU index mod 32 < m) for
-    // the main decode, set B for FSST -- made on first use for that m
-    int cu_m = 0;
-    hipStream_t cu_a = nullptr, cu_b = nullptr;
-    hipEvent_t join_a = nullptr, join_b = nullptr;
-    void release_cu() {
-        for (hipStream_t *st : {&cu_a, &cu_b})
-            if (*st) {
-                hipStreamSynchronize(*st);
-                hipStreamDestroy(*st);
-                *st = nullptr;
-            }
-        for (hipEvent_t *e : {&join_a, &join_b})
-            if (*e) {
-                hipEventDestroy(*e);
-                *e = nullptr;
-            }
-        cu_m = 0;
-    }
-};
-
-namespace {
-
-// One GPU's part of a device-resident table (fls_device_*): a contiguous
-// range of row groups uploaded verbatim to its HBM with their string_t
-// tables, the decoded columns, the launch descriptor list and the streams and
-// events of its decode launches.  A table is split over the connection's GPUs
-// like a scan (no data crosses GPUs: row groups are independent).
-struct Resident {
-    int dev = -1;
-    uint32_t rg0 = 0, rg1 = 0;
-    uint64_t base = 0;                 // file offset of img[0]
-    uint64_t first_row = 0, rows = 0;  // resident rows, relative to the file's first row
-    DevBuf<uint8_t> img;               // compressed bytes of [rg0, rg1)
-    DevBuf<StrT> strtab;               // string_t tables of VARCHAR chunks
-    std::vector<uint64_t> strtab_off;  // per (rg - rg0) * ncols + col: index into strtab
-    DevBuf<uint32_t> err;
-    DevBuf<uint32_t> queue;                // decode work-queue counters
-    std::vector<DevBuf<uint8_t>> d_heap;   // per FSST column: decoded string bytes
-    std::vector<PinBuf<uint8_t>> h_heap;   // per FSST column: host copy string_t points into
-    std::vector<uint64_t> heap_off;        // per (rg - rg0) * ncols + col: chunk heap offset
-    std::vector<DevBuf<uint8_t>> d_out;    // per column, rows of [rg0, rg1)
-    double placement_q = 0;                // write-probe rating of d_out's placement (choose_placement; 0: not rated)
-    float placement_ms = 0;                // decode-time rating of d_out's placement (0: not rated)
-    DevBuf<DevChunk> d_chunks;
-    std::vector<DevChunk> h_chunks;
-    std::vector<uint8_t> mask;         // column mask h_chunks was built for
-    uint32_t nmain = 0;                // h_chunks[0, nmain) main kernel, the rest FSST
-    DevBuf<DictVec> d_dictvecs;        // the dictionary-string grid's vectors (launch_dictstr), built with h_chunks
-    uint32_t ndictvecs = 0;            // ... and how many (their chunks are not in h_chunks)
-    bool list_built = false;           // h_chunks / d_dictvecs describe the current mask, policy and outputs
-    void invalidate() {                // a new mask, policy or set of outputs: rebuild both at the next decode
-        h_chunks.clear();
-        ndictvecs = 0;
-        list_built = false;
-    }
-    int64_t policy = -1;               // decode_policy() h_chunks was ordered for
-    int64_t lpolicy = 0;                // ... and the launch policy it resolved to (launch_policy)
-    FsstCounts fsst;                   // FSST chunks of h_chunks
-    SplitPlan split;                   // balanced split after h_chunks on the device (waves 0: none)
-    ByteCount bytes;                   // algorithmic bytes of one launch
-    hipStream_t stream = nullptr;
-    SideStream side;                   // FSST kernels overlapping the main decode kernel
-    std::vector<hipEvent_t> ev_pool;   // per-launch (start, stop) pairs since last sync
-    uint32_t ev_used = 0;
-    Resident() = default;
-    Resident(const Resident &) = delete;
-    Resident &operator=(const Resident &) = delete;
-    ~Resident() {
-        if (dev < 0) return;
-        hipSetDevice(dev);
-        if (stream) hipStreamSynchronize(stream);
-        if (side.stream) hipStreamSynchronize(side.stream);
-        if (stream) hipStreamDestroy(stream);
-        if (side.stream) hipStreamDestroy(side.stream);
-        if (side.fork) hipEventDestroy(side.fork);
-        if (side.join) hipEventDestroy(side.join);
-        side.release_cu();
-        for (auto e : ev_pool) hipEventDestroy(e);
-    }
-};
-
-}  // namespace
 
 // A mapped, validated file shared by the tables that read it: fls_read_fls
 // keeps the last few in a process-wide cache keyed by (device, inode, size,
@@ -855,7 +306,7 @@ ImageRegistry &image_registry() {
 uint64_t resident_budget() {
     return (uint64_t)std::max<int64_t>(0, knob_value("FLS_SCAN_RESIDENT_MB")) << 20;
 }
-namespace {
+FLS_ENGINE_BEGIN
 uint64_t release_idle_images(int dev) {
     ImageRegistry &R = image_registry();
     ResidentSet<DevImage>::Evicted ev;
@@ -864,7 +315,7 @@ uint64_t release_idle_images(int dev) {
     ev.clear();
     return b;
 }
-}  // namespace
+FLS_ENGINE_END
 void drop_file_images(const void *owner) {
     ImageRegistry &R = image_registry();
     ResidentSet<DevImage>::Evicted ev;
@@ -873,41 +324,25 @@ void drop_file_images(const void *owner) {
     ev.clear();
 }
 
-struct fls_table {
-    std::vector<int> devices;          // the connection's GPUs (row groups shard over them)
-    std::shared_ptr<MappedFile> mapped;  // fls_read_fls: the file and its validated metadata (shared)
-    std::shared_ptr<ConnRes> res;      // the connection's scan resources (outlive a disconnect)
-    std::vector<uint8_t> owned;
-    const uint8_t *img = nullptr;
-    uint64_t len = 0;
-    FileMeta meta;
-    std::vector<std::string> names;
-    bool registered = false;        // img pinned with hipHostRegister (FLS_SCAN_PIN=1)
-    bool pin_tried = false;
-    void *map = nullptr;            // fls_read_fls: the file, mapped read-only
-    size_t map_len = 0;
 
-    // device-resident mode: one part per GPU (fls_device_upload)
-    std::vector<std::unique_ptr<Resident>> resident;
-    uint32_t launches = 0;
-
-    ScanCtx scan, mat;
-    std::vector<HostTerm> filter;   // fls_scan_filter: applies to the next fls_scan_begin / fls_aggregate
-    std::vector<fls_agg_expr> exprs;  // fls_aggregate_exprs: what FLS_AGG_SUM_EXPR's spec.col indexes
-    bool dict_codes = false;        // fls_scan_dict_codes: applies to the next fls_scan_begin
-    bool narrow = false;            // fls_scan_narrow: applies to the next fls_scan_begin
-    bool defer_records = false;     // fls_scan_defer_records: applies to the next fls_scan_begin
-    bool profiled = false;          // scanned with FLS_SCAN_PROFILE=1 (prints the totals at close)
-    ~fls_table();
-};
-
-namespace {
+FLS_ENGINE_BEGIN
 
 int out_bytes_of(const fls_table *t, uint32_t c) { return type_out_bytes(t->meta.cols[c].type); }
 
+uint8_t col_kind(const fls_table *t, uint32_t c) {
+    const uint8_t ty = t->meta.cols[c].type;
+    return type_is_float(ty) ? FK_FLOAT : type_is_signed(ty) ? FK_INT : FK_UINT;
+}
+
+int check_rowgroup_range(const fls_table *t, uint32_t rg0, uint32_t rg1, const char *prefix) {
+    if (rg1 > t->meta.rgs.size() || rg0 > rg1)
+        return fail(FLS_ERR_ARG, "%srow-group range [%u,%u) out of bounds", prefix, rg0, rg1);
+    return 0;
+}
+
 // The validity bitmaps of chunk (rg, c) in the host image, or nullptr when the
 // chunk has no NULL (fls_format.hpp "Validity")
-const uint64_t *chunk_validity_host(const fls_table *t, uint32_t rg, uint32_t c) {
+static const uint64_t *chunk_validity_host(const fls_table *t, uint32_t rg, uint32_t c) {
     const ChunkRef &ch = t->meta.rgs[rg].chunks[c];
     if (!chunk_has_validity(ch.hdr)) return nullptr;
     return (const uint64_t *)(t->img + ch.off + validity_off(ch.len, ch.hdr.nvec));
@@ -944,8 +379,8 @@ int build_strtabs(const fls_table *t, int dev, uint32_t rg0, uint32_t rg1, DevBu
 // code_w (1 or 2): a DICT string chunk delivered as its codes, gathered from
 // the identity table d_ident instead of the string_t dictionary
 DevChunk make_devchunk(const fls_table *t, uint32_t rg, uint32_t col, const uint8_t *d_chunk, const uint8_t *d_dict,
-                       uint8_t *d_out, ByteCount *bc, uint8_t *d_heap = nullptr, const uint8_t *h_heap = nullptr,
-                       uint32_t code_w = 0, const uint8_t *d_ident = nullptr) {
+                       uint8_t *d_out, ByteCount *bc, uint8_t *d_heap, const uint8_t *h_heap, uint32_t code_w,
+                       const uint8_t *d_ident) {
     const ChunkRef &ch = t->meta.rgs[rg].chunks[col];
     const ChunkHeader &h = ch.hdr;
     DevChunk d;
@@ -1024,7 +459,7 @@ DevChunk make_devchunk(const fls_table *t, uint32_t rg, uint32_t col, const uint
     return d;
 }
 
-bool col_selected(const std::vector<uint8_t> &mask, uint32_t c) { return mask.empty() || mask[c]; }
+static bool col_selected(const std::vector<uint8_t> &mask, uint32_t c) { return mask.empty() || mask[c]; }
 
 bool is_fsst(const fls_table *t, uint32_t rg, uint32_t c) { return t->meta.rgs[rg].chunks[c].hdr.enc == ENC_FSST; }
 
@@ -1064,7 +499,7 @@ struct DictWgCfg {
     uint32_t min_vecs_per_cu = 64;
     uint32_t streams = 4;
 };
-DictWgCfg dict_wg_cfg() {
+static DictWgCfg dict_wg_cfg() {
     DictWgCfg c;
     if (const char *e = getenv("FLS_DICT_WG")) c.mode = std::min(2, std::max(0, atoi(e)));
     if (const char *e = getenv("FLS_DICT_WG_MIN_VECS_PER_CU")) c.min_vecs_per_cu = (uint32_t)std::min(255, std::max(0, atoi(e)));
@@ -1123,7 +558,7 @@ int64_t launch_policy(int64_t policy, const std::vector<DevChunk> &v, DecodeGeom
 // workgroups are laid out in: ascending output address, as S interleaved
 // streams (below).
 uint32_t order_for_launch(std::vector<DevChunk> &v, FsstCounts *fc, int64_t policy,
-                          std::vector<DevChunk> *dictwg = nullptr) {
+                          std::vector<DevChunk> *dictwg) {
     if (dictwg) {
         dictwg->clear();
         const int mode = (int)((policy >> 48) & 3);
@@ -1236,7 +671,7 @@ struct OverlapSplit {
     // items (whole chunks, then pieces) instead of whole chunks
     bool guided = false;
 };
-OverlapSplit overlap_split() {
+static OverlapSplit overlap_split() {
     OverlapSplit o;
     if (const char *e = getenv("FLS_OVERLAP_CU_SPLIT")) o.cu_split = std::min(31, std::max(0, atoi(e)));
     if (const char *e = getenv("FLS_OVERLAP_DECODE_BPC")) o.decode_bpc = std::max(1, atoi(e));
@@ -1299,8 +734,6 @@ int fsst_config_check(int64_t policy) {
     return 0;
 }
 
-constexpr uint32_t kQueueWords = 1 + kFsstGroups;
-
 // Fused launch knobs (launch_all -> launch_fused): the default for a table
 // decode whose FSST chunks are of one segmented kind; FLS_FUSED=0 turns it
 // off (serial or overlapped kernels), FLS_FUSED=1 forces it even without FSST
@@ -1319,7 +752,7 @@ struct FusedCfg {
     bool variant = false;    // a non-default FLS_FSST_VARIANT: no fused launch
     FusedLaunch how;
 };
-FusedCfg fused_cfg() {
+static FusedCfg fused_cfg() {
     FusedCfg f;
     if (const char *e = getenv("FLS_FUSED")) f.mode = std::min(2, std::max(0, atoi(e) == 1 ? 2 : atoi(e)));
     if (const char *e = getenv("FLS_FUSED_FSST16")) {
@@ -1354,7 +787,7 @@ FusedCfg fused_cfg() {
 // the same share whether the mask's bits run XCD by XCD or round-robin over
 // the XCDs (m a multiple of 8).
 template <class LaunchGroup>
-hipError_t launch_cu_split(const DevChunk *d_chunks, uint32_t nmain, const FsstCounts &fc, uint32_t *d_err,
+static hipError_t launch_cu_split(const DevChunk *d_chunks, uint32_t nmain, const FsstCounts &fc, uint32_t *d_err,
                            const DecodeGeom &geom, hipStream_t stream, uint32_t *d_queue, SideStream *side,
                            const OverlapSplit &ov, int cus, const FsstLaunch (&how)[kFsstGroups],
                            LaunchGroup &launch_group) {
@@ -1415,8 +848,7 @@ hipError_t launch_cu_split(const DevChunk *d_chunks, uint32_t nmain, const FsstC
 
 hipError_t launch_all(const DevChunk *d_chunks, uint32_t nmain, uint32_t ntotal, const FsstCounts &fc,
                       uint32_t *d_err, const DecodeGeom &geom, hipStream_t stream, uint32_t *d_queue, int64_t policy,
-                      SplitPlan plan, const SideStream *side = nullptr, const DictVec *d_dictvecs = nullptr,
-                      uint32_t ndictvecs = 0) {
+                      SplitPlan plan, const SideStream *side, const DictVec *d_dictvecs, uint32_t ndictvecs) {
     // the dictionary-string grid first, on the same stream: its chunks are not
     // in d_chunks, and a launch may consist of it alone
     if (ndictvecs) {
@@ -1517,7 +949,7 @@ hipError_t launch_all(const DevChunk *d_chunks, uint32_t nmain, uint32_t ntotal,
     return e;
 }
 
-}  // namespace
+FLS_ENGINE_END
 
 fls_table::~fls_table() {
     if (profiled && ScanProf::on()) scan_prof().print();
@@ -1540,10 +972,10 @@ fls_table::~fls_table() {
 // ------------------------------------------------------------------------------
 // scan pipeline
 
-namespace {
+FLS_ENGINE_BEGIN
 
 // May any row of row group rg satisfy term h?  (zone maps / dictionary)
-bool term_may_match(const fls_table *t, uint32_t rg, const HostTerm &h) {
+static bool term_may_match(const fls_table *t, uint32_t rg, const HostTerm &h) {
     const RowGroupMeta &r = t->meta.rgs[rg];
     const ChunkRef &ch = r.chunks[h.col];
     // NULLs: the chunk's validity flag, and the zone map's all-NULL mark
@@ -1622,7 +1054,7 @@ bool topn_key_type(const ColumnMeta &c) {
 // row groups without a zone map (they guarantee nothing) and, under NULLS
 // FIRST, those with a NULL (NULLS LAST: a NULL is worse than T's record, so
 // the strict test on the values decides).  Returns the row groups dropped.
-uint32_t topn_prune(const fls_table *t, const fls_order_key &key, uint32_t k, std::vector<uint32_t> &rgs) {
+static uint32_t topn_prune(const fls_table *t, const fls_order_key &key, uint32_t k, std::vector<uint32_t> &rgs) {
     const uint8_t ty = t->meta.cols[key.col].type;
     if (k == 0 || type_is_float(ty) || !topn_key_type(t->meta.cols[key.col])) return 0;
     const uint8_t kind = type_is_signed(ty) ? FK_INT : FK_UINT;
@@ -1681,7 +1113,7 @@ uint32_t select_rowgroups(const fls_table *t, const std::vector<HostTerm> &terms
 // after evicting the least recently used images no running scan holds.  The
 // image holds the file bytes of shard g of G: the row groups this GPU owns
 // when the whole table is split over the connection's GPUs.
-std::shared_ptr<DevImage> resident_image(fls_table *t, int dev, uint32_t g, uint32_t G) {
+static std::shared_ptr<DevImage> resident_image(fls_table *t, int dev, uint32_t g, uint32_t G) {
     if (!t->mapped) return nullptr;
     const uint64_t budget = resident_budget();
     const uint32_t N = (uint32_t)t->meta.rgs.size();
@@ -1746,14 +1178,13 @@ std::shared_ptr<DevImage> resident_image(fls_table *t, int dev, uint32_t g, uint
     return di;
 }
 
-int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uint8_t *col_mask, uint32_t rg0,
-               uint32_t rg1, const std::vector<HostTerm> *filter, const std::vector<HostAgg> *aggs = nullptr,
-               const std::vector<uint32_t> *keys = nullptr, const fls_order_key *order = nullptr,
-               uint32_t topk = 0, const std::vector<uint32_t> *only = nullptr) {
+int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     ProfTimer prof(PROF_SETUP);
     t->profiled = t->profiled || ScanProf::on();
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    if (rg1 > t->meta.rgs.size() || rg0 > rg1) return fail(FLS_ERR_ARG, "row-group range [%u,%u) out of bounds", rg0, rg1);
+    const std::vector<int> &devs = p.devices;
+    const uint32_t rg0 = p.rg0, rg1 = p.rg1;
+    if (int rc = check_rowgroup_range(t, rg0, rg1, "")) return rc;
     // tear down a previous scan on this context
     for (auto &dp : s.devs) {
         ScanDev &d = *dp;
@@ -1771,22 +1202,41 @@ int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uin
     s.out.clear();
     s.ready.clear();
     s.mask.assign(ncols, 1);
-    if (col_mask)
-        for (uint32_t c = 0; c < ncols; ++c) s.mask[c] = col_mask[c] ? 1 : 0;
+    if (p.col_mask)
+        for (uint32_t c = 0; c < ncols; ++c) s.mask[c] = p.col_mask[c] ? 1 : 0;
     s.terms.clear();
-    if (filter) s.terms = *filter;
-    s.dict_codes = filter != nullptr && t->dict_codes;  // scans (not materialize) only
-    s.narrow = filter != nullptr && t->narrow;
-    s.defer_records = filter != nullptr && t->defer_records;
+    if (p.filter) s.terms = *p.filter;
+    // the one place that decides what kind of scan this is
+    s.reduce = Reduce::None;
+    if (p.aggs) s.reduce = p.keys ? Reduce::GroupAggregate : Reduce::Aggregate;
+    else if (p.order && p.k) s.reduce = Reduce::TopN;
+    // the delivery options: consumers' scans only (not materialize); a reducing scan delivers nothing
+    const bool options = p.delivering_scan && s.reduce == Reduce::None;
+    s.dict_codes = options && t->dict_codes;
+    s.narrow = options && t->narrow;
+    s.defer_records = options && t->defer_records;
     s.dmask = s.mask;
     for (auto &h : s.terms)
         if (h.op < OP_IS_NULL || is_set_op(h.op)) s.dmask[h.col] = 1;
     s.aggs.clear();
-    if (aggs) {
-        // an aggregate scan delivers nothing and decodes the filter's columns
-        // and the numeric operands (a COUNT reads its column's validity only)
-        s.aggs = *aggs;
-        s.dict_codes = s.narrow = s.defer_records = false;
+    s.keys.clear();
+    s.tk = 0;
+    s.tkey = fls_order_key{};
+    bool string_key = false;
+    switch (s.reduce) {
+    case Reduce::None: break;
+    case Reduce::GroupAggregate:
+        // the GROUP BY columns of a grouped aggregate scan are decoded too
+        s.keys = *p.keys;
+        for (uint32_t c : s.keys) {
+            s.dmask[c] = 1;
+            string_key = string_key || type_is_string(t->meta.cols[c].type);
+        }
+        [[fallthrough]];
+    case Reduce::Aggregate:
+        // an aggregate scan decodes the filter's columns and the numeric
+        // operands (a COUNT reads its column's validity only)
+        s.aggs = *p.aggs;
         for (auto &a : s.aggs) {
             if (a.fn == AGG_SUM_EXPR) {
                 for (uint32_t i = 0; i < a.nf; ++i) s.dmask[a.fcol[i]] = 1;
@@ -1795,29 +1245,19 @@ int scan_setup(fls_table *t, ScanCtx &s, const std::vector<int> &devs, const uin
             if (a.fn >= AGG_SUM) s.dmask[a.col] = 1;
             if (a.fn == AGG_SUM_PRODUCT) s.dmask[a.col2] = 1;
         }
-    }
-    // the GROUP BY columns of a grouped aggregate scan are decoded too
-    s.keys.clear();
-    bool string_key = false;
-    if (aggs && keys) {
-        s.keys = *keys;
-        for (uint32_t c : s.keys) {
-            s.dmask[c] = 1;
-            string_key = string_key || type_is_string(t->meta.cols[c].type);
-        }
-    }
-    // a top-N scan delivers nothing either and decodes the filter's columns and its key column
-    s.tk = order ? topk : 0;
-    s.tkey = order ? *order : fls_order_key{};
-    if (s.tk) {
-        s.dict_codes = s.narrow = s.defer_records = false;
+        break;
+    case Reduce::TopN:
+        // a top-N scan decodes the filter's columns and its key column
+        s.tk = p.k;
+        s.tkey = *p.order;
         s.dmask[s.tkey.col] = 1;
+        break;
     }
     // row-group pruning on zone maps / dictionaries (a top-N scan without a
     // filter: by the k-th bound of the key's zone maps)
-    s.pruned = select_rowgroups(t, s.terms, s.tk ? &s.tkey : nullptr, s.tk, rg0, rg1, s.rgs);
-    if (only) {  // a scan of listed row groups (ascending, inside the range): fls_topn's late materialisation
-        s.rgs = *only;
+    s.pruned = select_rowgroups(t, s.terms, s.reduce == Reduce::TopN ? &s.tkey : nullptr, s.tk, rg0, rg1, s.rgs);
+    if (p.only) {  // a scan of listed row groups: fls_topn's late materialisation
+        s.rgs = *p.only;
         s.pruned = 0;
     }
     s.cur = 0;
@@ -1922,7 +1362,7 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
         if (a.fn == AGG_SUM_PRODUCT) need[a.col2] = 1;
     }
     for (uint32_t c : s.keys) need[c] = 1;
-    if (s.tk) need[s.tkey.col] = 1;
+    if (s.reduce == Reduce::TopN) need[s.tkey.col] = 1;
     for (uint32_t c = 0; c < ncols; ++c) {
         bool any = false;
         for (uint32_t r = sl.rg0; need[c] && r < sl.rg0 + sl.nrg; ++r)
@@ -1946,9 +1386,24 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
     return 0;
 }
 
+int rg_vec_table(const fls_table *t, const Slot &sl, uint32_t *tab, uint32_t &rg_vecs) {
+    uint64_t vecs = 0;
+    rg_vecs = 1;
+    for (uint32_t r = 0; r < sl.nrg; ++r) {
+        const RowGroupMeta &rg = t->meta.rgs[sl.rg0 + r];
+        uint32_t *rv = tab + 2 * r;
+        rv[0] = (uint32_t)((rg.first_row - t->meta.rgs[sl.rg0].first_row) / kVectorSize);
+        rv[1] = (uint32_t)((rg.nrows + kVectorSize - 1) / kVectorSize);
+        vecs = std::max<uint64_t>(vecs, (uint64_t)rv[0] + rv[1]);
+        rg_vecs = std::max(rg_vecs, rv[1]);
+    }
+    if (vecs > sl.hb->nvec) return fail(FLS_ERR_STATE, "internal: row groups of a batch past its %u vectors", sl.hb->nvec);
+    return 0;
+}
+
 // Filter descriptors of a batch: the terms over the slot's decoded columns,
 // the delivered columns' compaction targets, then the constant strings.
-int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo, uint64_t in_len) {
+static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo, uint64_t in_len) {
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
     std::vector<DevOut> outs;
     for (uint32_t c = 0; c < ncols; ++c) {
@@ -2039,7 +1494,7 @@ int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
         HIP_TRY(launch_keyset(sl.d_sdesc.p, (uint32_t)ns, (uint32_t)rows, sl.d_mask.p, sl.d_counts.p, d.err.p,
                               sl.stream));
     }
-    if (!s.aggs.empty() || s.tk) return 0;  // an aggregate / top-N scan reduces under the mask: nothing is compacted or delivered
+    if (s.reduce != Reduce::None) return 0;  // an aggregate / top-N scan reduces under the mask: nothing is compacted or delivered
     HIP_TRY(hb.h_counts.alloc(hb.nvec));
     HIP_TRY(hb.h_sel.alloc(std::max<uint64_t>(rows, 1)));
     HIP_TRY(launch_compact((const DevOut *)(sl.d_fdesc.p + nt * sizeof(DevTerm)), (uint32_t)no, sl.d_mask.p,
@@ -2050,201 +1505,6 @@ int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
     return 0;
 }
 
-// The aggregates of a batch as the kernels see them (sl.h_adesc -> sl.d_adesc
-// on the slot's stream), over the slot's decoded columns and staged validity.
-int upload_agg_descs(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl) {
-    const std::vector<uint8_t> &need = sl.valid_staged;
-    const uint32_t na = (uint32_t)s.aggs.size();
-    HIP_TRY(sl.h_adesc.alloc(na));
-    HIP_TRY(sl.d_adesc.alloc(d.dev, na));
-    uint8_t nfsum = 0;
-    auto kind_of = [&](uint32_t c) -> uint8_t {
-        const uint8_t ty = t->meta.cols[c].type;
-        return type_is_float(ty) ? FK_FLOAT : type_is_signed(ty) ? FK_INT : FK_UINT;
-    };
-    for (uint32_t i = 0; i < na; ++i) {
-        const HostAgg &a = s.aggs[i];
-        DevAgg &da = sl.h_adesc.p[i];
-        memset(&da, 0, sizeof(da));
-        da.fn = a.fn;
-        if (a.fn == AGG_COUNT_STAR) continue;
-        if (a.fn == AGG_SUM_EXPR) {
-            da.nf = (uint8_t)a.nf;
-            for (uint32_t k = 0; k < a.nf; ++k) {
-                const uint32_t c = a.fcol[k];
-                da.f[k].col = sl.d_out[c].p;
-                da.f[k].valid = need[c] ? sl.d_valid[c].p : nullptr;
-                da.f[k].k = a.fk[k];
-                da.fob[k] = (uint8_t)out_bytes_of(t, c);
-                da.fkind[k] = kind_of(c);
-                da.fneg[k] = a.fneg[k];
-            }
-            continue;
-        }
-        da.valid = need[a.col] ? sl.d_valid[a.col].p : nullptr;
-        if (a.fn == AGG_COUNT) continue;
-        da.col = sl.d_out[a.col].p;
-        da.ob = (uint8_t)out_bytes_of(t, a.col);
-        da.kind = kind_of(a.col);
-        if (a.fn == AGG_SUM && da.kind == FK_FLOAT) da.fslot = nfsum++;
-        if (a.fn != AGG_SUM_PRODUCT) continue;
-        da.col2 = sl.d_out[a.col2].p;
-        da.ob2 = (uint8_t)out_bytes_of(t, a.col2);
-        da.kind2 = kind_of(a.col2);
-        da.valid2 = need[a.col2] ? sl.d_valid[a.col2].p : nullptr;
-    }
-    HIP_TRY(hipMemcpyAsync(sl.d_adesc.p, sl.h_adesc.p, na * sizeof(DevAgg), hipMemcpyHostToDevice, sl.stream));
-    return 0;
-}
-
-// Aggregate descriptors of a batch and the launch that reduces it: one
-// partial record per (vector, aggregate) into sl.d_agg, copied to the host
-// batch on the slot's stream.  The selection mask is the filter kernel's
-// (enqueue_filter ran before) or none.
-int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
-    HostBatch &hb = *sl.hb;
-    const bool filtered = !s.terms.empty();
-    if (!filtered)  // (enqueue_filter staged the filter's and the operands' validity together)
-        if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
-    const uint32_t na = (uint32_t)s.aggs.size();
-    hb.nvec = (uint32_t)((rows + 1023) / 1024);
-    HIP_TRY(sl.d_agg.alloc(d.dev, (size_t)hb.nvec * na));
-    HIP_TRY(hb.h_agg.alloc((size_t)hb.nvec * na));
-    if (int rc = upload_agg_descs(t, s, d, sl)) return rc;
-    HIP_TRY(launch_aggregate(sl.d_adesc.p, na, (uint32_t)rows, filtered ? sl.d_mask.p : nullptr, sl.d_agg.p,
-                             sl.stream));
-    HIP_TRY(hipMemcpyAsync(hb.h_agg.p, sl.d_agg.p, (size_t)hb.nvec * na * sizeof(AggRec), hipMemcpyDeviceToHost,
-                           sl.stream));
-    return 0;
-}
-
-// Bit layout of the packed key of a grouped aggregate (fls_groupagg.hpp): key
-// q's value at shift[q] in bits[q] bits -- 8 x the decoded value's bytes, 16
-// for a VARCHAR key's dictionary code -- then one NULL bit per key.
-struct KeyLayout {
-    uint32_t shift[kMaxKeys] = {}, bits[kMaxKeys] = {}, null_bit[kMaxKeys] = {};
-    uint32_t total = 0;
-};
-KeyLayout key_layout(const fls_table *t, const std::vector<uint32_t> &keys) {
-    KeyLayout L;
-    for (size_t q = 0; q < keys.size() && q < kMaxKeys; ++q) {
-        const uint8_t ty = t->meta.cols[keys[q]].type;
-        L.shift[q] = L.total;
-        L.bits[q] = type_is_string(ty) ? 16 : (uint32_t)type_value_bits(ty);
-        L.total += L.bits[q];
-    }
-    for (size_t q = 0; q < keys.size() && q < kMaxKeys; ++q) L.null_bit[q] = L.total++;
-    return L;
-}
-
-// The grouped counterpart of enqueue_aggregate: stage 1 reduces every vector
-// per distinct key into sl.d_gvec, stage 2 merges the vectors of each row
-// group into sl.d_grg, and the row groups' tables are the batch's only D2H.
-int enqueue_group_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
-    HostBatch &hb = *sl.hb;
-    const bool filtered = !s.terms.empty();
-    if (!filtered)  // (enqueue_filter staged the filter's, the operands' and the keys' validity together)
-        if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
-    const std::vector<uint8_t> &need = sl.valid_staged;
-    const uint32_t na = (uint32_t)s.aggs.size(), nk = (uint32_t)s.keys.size();
-    hb.nvec = (uint32_t)((rows + 1023) / 1024);
-    if (int rc = upload_agg_descs(t, s, d, sl)) return rc;
-    uint32_t nfsum = 0, rg_vecs = 1;
-    for (uint32_t i = 0; i < na; ++i) nfsum += s.aggs[i].fn == AGG_SUM && sl.h_adesc.p[i].kind == FK_FLOAT;
-    for (uint32_t r = sl.rg0; r < sl.rg0 + sl.nrg; ++r)
-        rg_vecs = std::max(rg_vecs, (t->meta.rgs[r].nrows + kVectorSize - 1) / kVectorSize);
-    hb.g_nfsum = nfsum;
-    hb.g_rg_vecs = rg_vecs;
-    const size_t gd_bytes = kMaxKeys * sizeof(DevKey) + 2ull * sl.nrg * sizeof(uint32_t);
-    HIP_TRY(sl.h_gdesc.alloc(gd_bytes));
-    HIP_TRY(sl.d_gdesc.alloc(d.dev, gd_bytes));
-    memset(sl.h_gdesc.p, 0, gd_bytes);
-    DevKey *dk = (DevKey *)sl.h_gdesc.p;
-    uint32_t *rgvec = (uint32_t *)(sl.h_gdesc.p + kMaxKeys * sizeof(DevKey));
-    const KeyLayout L = key_layout(t, s.keys);
-    for (uint32_t q = 0; q < nk; ++q) {
-        const uint32_t c = s.keys[q];
-        // hb.ob: the decode's bytes per row (a VARCHAR key: its codes' width in this batch)
-        if (hb.ob[c] * 8u > L.bits[q])
-            return fail(FLS_ERR_STATE, "internal: key column %u decoded %u bytes wide", c, hb.ob[c]);
-        dk[q].col = sl.d_out[c].p;
-        dk[q].valid = need[c] ? sl.d_valid[c].p : nullptr;
-        dk[q].ob = hb.ob[c];
-        dk[q].shift = (uint8_t)L.shift[q];
-        dk[q].null_bit = (uint8_t)L.null_bit[q];
-    }
-    uint64_t vecs = 0;
-    for (uint32_t r = 0; r < sl.nrg; ++r) {
-        const RowGroupMeta &rg = t->meta.rgs[sl.rg0 + r];
-        rgvec[2 * r] = (uint32_t)((rg.first_row - t->meta.rgs[sl.rg0].first_row) / kVectorSize);
-        rgvec[2 * r + 1] = (uint32_t)((rg.nrows + kVectorSize - 1) / kVectorSize);
-        vecs = std::max<uint64_t>(vecs, (uint64_t)rgvec[2 * r] + rgvec[2 * r + 1]);
-    }
-    if (vecs > hb.nvec) return fail(FLS_ERR_STATE, "internal: row groups of a batch past its %u vectors", hb.nvec);
-    const size_t rg_stride = group_rg_stride(na, nfsum, rg_vecs);
-    HIP_TRY(sl.d_gvec.alloc(d.dev, (size_t)hb.nvec * group_vec_stride(na)));
-    HIP_TRY(sl.d_grg.alloc(d.dev, (size_t)sl.nrg * rg_stride));
-    HIP_TRY(hb.h_grp.alloc((size_t)sl.nrg * rg_stride));
-    HIP_TRY(hipMemcpyAsync(sl.d_gdesc.p, sl.h_gdesc.p, gd_bytes, hipMemcpyHostToDevice, sl.stream));
-    HIP_TRY(launch_group_vectors((const DevKey *)sl.d_gdesc.p, nk, sl.d_adesc.p, na, (uint32_t)rows,
-                                 filtered ? sl.d_mask.p : nullptr, sl.d_gvec.p, d.err.p, sl.stream));
-    HIP_TRY(launch_group_rowgroups(sl.d_adesc.p, na, nfsum,
-                                   (const uint32_t *)(sl.d_gdesc.p + kMaxKeys * sizeof(DevKey)), sl.nrg, rg_vecs,
-                                   sl.d_gvec.p, sl.d_grg.p, d.err.p, sl.stream));
-    HIP_TRY(hipMemcpyAsync(hb.h_grp.p, sl.d_grg.p, (size_t)sl.nrg * rg_stride, hipMemcpyDeviceToHost, sl.stream));
-    return 0;
-}
-
-// The top-N counterpart: stage 1 leaves every vector's best k candidates in
-// sl.d_tvec, stage 2 merges the vectors of each row group pairwise (between
-// sl.d_tvec and sl.d_ttmp) into sl.d_trg, and
-// the row groups' lists are the batch's only D2H.
-int enqueue_topn(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
-    HostBatch &hb = *sl.hb;
-    const bool filtered = !s.terms.empty();
-    if (!filtered)  // (enqueue_filter staged the filter's and the key's validity together)
-        if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
-    const uint32_t c = s.tkey.col;
-    const uint8_t ty = t->meta.cols[c].type;
-    hb.nvec = (uint32_t)((rows + 1023) / 1024);
-    HIP_TRY(sl.h_tdesc.alloc(2ull * sl.nrg));
-    HIP_TRY(sl.d_tdesc.alloc(d.dev, 2ull * sl.nrg));
-    uint64_t vecs = 0;
-    uint32_t rg_vecs = 1;
-    for (uint32_t r = 0; r < sl.nrg; ++r) {
-        const RowGroupMeta &rg = t->meta.rgs[sl.rg0 + r];
-        uint32_t *rv = sl.h_tdesc.p + 2 * r;
-        rv[0] = (uint32_t)((rg.first_row - t->meta.rgs[sl.rg0].first_row) / kVectorSize);
-        rv[1] = (uint32_t)((rg.nrows + kVectorSize - 1) / kVectorSize);
-        vecs = std::max<uint64_t>(vecs, (uint64_t)rv[0] + rv[1]);
-        rg_vecs = std::max(rg_vecs, rv[1]);
-    }
-    if (rows > (1ull << 30)) return fail(FLS_ERR_LIMIT, "fls_topn: a batch of more than 2^30 rows");
-    if (vecs > hb.nvec) return fail(FLS_ERR_STATE, "internal: row groups of a batch past its %u vectors", hb.nvec);
-    const size_t stride = topn_stride(s.tk);
-    HIP_TRY(sl.d_tvec.alloc(d.dev, (size_t)hb.nvec * stride));
-    HIP_TRY(sl.d_ttmp.alloc(d.dev, (size_t)hb.nvec * stride));
-    HIP_TRY(sl.d_trg.alloc(d.dev, (size_t)sl.nrg * stride));
-    HIP_TRY(hb.h_topn.alloc((size_t)sl.nrg * stride));
-    DevTopn p;
-    memset(&p, 0, sizeof(p));
-    p.col = sl.d_out[c].p;
-    p.valid = sl.valid_staged[c] ? sl.d_valid[c].p : nullptr;
-    p.mask = filtered ? sl.d_mask.p : nullptr;
-    p.nrows = (uint32_t)rows;
-    p.k = s.tk;
-    p.ob = (uint8_t)out_bytes_of(t, c);
-    p.kind = type_is_float(ty) ? FK_FLOAT : type_is_signed(ty) ? FK_INT : FK_UINT;
-    p.desc = s.tkey.desc ? 1 : 0;
-    p.nulls_first = s.tkey.nulls_first ? 1 : 0;
-    HIP_TRY(hipMemcpyAsync(sl.d_tdesc.p, sl.h_tdesc.p, 2ull * sl.nrg * sizeof(uint32_t), hipMemcpyHostToDevice,
-                           sl.stream));
-    HIP_TRY(launch_topn_vectors(p, sl.d_tvec.p, sl.stream));
-    HIP_TRY(launch_topn_rowgroups(sl.d_tdesc.p, sl.nrg, rg_vecs, hb.nvec, s.tk, sl.d_tvec.p, sl.d_ttmp.p, sl.d_trg.p,
-                                  sl.stream));
-    HIP_TRY(hipMemcpyAsync(hb.h_topn.p, sl.d_trg.p, (size_t)sl.nrg * stride, hipMemcpyDeviceToHost, sl.stream));
-    return 0;
-}
 
 // enqueue the next batch of device d into slot si: up to s.batch consecutive
 // surviving row groups
@@ -2256,8 +1516,8 @@ int enqueue_topn(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, 
 // recorded.  The read_fastlanes profile of round 3's inline refill: of 1.8 s
 // of scan-thread time (16 threads, lineitem_full SF10), 1.2 s was waiting for
 // the claim lock while one thread ran a refill (profiles/r4/).
-int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si);
-int claim_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
+static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si);
+static int claim_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     Slot &sl = d.slots[si];
     sl.busy = false;
     sl.starved = false;
@@ -2297,7 +1557,7 @@ int claim_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     return 1;
 }
 // Both parts (the scan's first batches, a refill a release unblocks).
-int enqueue_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
+static int enqueue_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     const int c = claim_batch(t, s, d, si);
     if (c <= 0) return c;
     const int rc = fill_batch(t, s, d, si);
@@ -2305,7 +1565,7 @@ int enqueue_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     d.slots[si].busy = rc == 0;
     return rc;
 }
-int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
+static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     ProfTimer prof(PROF_FILL), pdesc(PROF_FILL_DESC);
     Slot &sl = d.slots[si];
     HostBatch &hb = *sl.hb;
@@ -2521,7 +1781,7 @@ int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     if (fsst.total_vecs() > 0)
         if (const int rc = fsst_config_check(policy)) return rc;
     // (an aggregate scan of counts without a filter decodes no column)
-    if (kk || s.aggs.empty())
+    if (kk || !s.aggregating())
         HIP_TRY(launch_all(sl.d_chunks.p, nmain, (uint32_t)k, fsst, d.err.p, bc.geom, sl.stream, sl.queue.p, policy,
                            plan));
     const uint64_t rows = t->meta.rgs[sl.rg0 + sl.nrg - 1].first_row + t->meta.rgs[sl.rg0 + sl.nrg - 1].nrows -
@@ -2560,15 +1820,17 @@ int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
         int rc = enqueue_filter(t, s, d, sl, rows, lo, hi - lo);
         if (rc) return rc;
     }
-    // 3b. aggregate scan: reduce under the mask; the partial records are the batch's only D2H
-    // (grouped: the row groups' tables of groups)
-    if (!s.aggs.empty())
-        if (int rc = s.keys.empty() ? enqueue_aggregate(t, s, d, sl, rows, lo)
-                                    : enqueue_group_aggregate(t, s, d, sl, rows, lo))
-            return rc;
-    // 3c. top-N scan: select under the mask; the row groups' candidate lists are the batch's only D2H
-    if (s.tk)
-        if (int rc = enqueue_topn(t, s, d, sl, rows, lo)) return rc;
+    // 3b. a reducing scan: reduce under the mask; what it leaves is the batch's only D2H
+    {
+        int rc = 0;
+        switch (s.reduce) {
+        case Reduce::None: break;
+        case Reduce::Aggregate: rc = enqueue_aggregate(t, s, d, sl, rows, lo); break;             // partial records
+        case Reduce::GroupAggregate: rc = enqueue_group_aggregate(t, s, d, sl, rows, lo); break;  // tables of groups
+        case Reduce::TopN: rc = enqueue_topn(t, s, d, sl, rows, lo); break;                       // candidate lists
+        }
+        if (rc) return rc;
+    }
     // 3. D2H into pinned host columns (and string heaps)
     if (hb.pt[1]) HIP_TRY(hipEventRecord(hb.pt[1], sl.stream));
     hb.prof_d2h = 0;
@@ -2618,7 +1880,7 @@ int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     return 0;  // the caller marks the slot busy (under s.mu)
 }
 
-void build_records(const fls_table *t, HostBatch &hb, uint32_t rg) {
+static void build_records(const fls_table *t, HostBatch &hb, uint32_t rg) {
     // FSST columns delivered as lengths: this row group's string_t records,
     // rebuilt here (the consumer's thread) over the pinned heap copy -- inline
     // bytes for strings of <= 12 bytes, else a 4-byte prefix and the pointer --
@@ -2681,7 +1943,7 @@ int scan_start(fls_table *t, ScanCtx &s) {
 
 // the device and host batch holding row group rg (a batch already released by
 // its slot, or one a slot holds), or false if its batch is not enqueued
-bool find_batch(ScanCtx &s, uint32_t rg, int &g, HostBatch *&hb) {
+static bool find_batch(ScanCtx &s, uint32_t rg, int &g, HostBatch *&hb) {
     for (auto &[dg, b] : s.ready)
         if (rg >= b->rg0 && rg < b->rg0 + b->nrg) {
             g = dg;
@@ -2702,7 +1964,7 @@ bool find_batch(ScanCtx &s, uint32_t rg, int &g, HostBatch *&hb) {
 
 // filtered batch: selected-row offsets of its row groups from the per-vector
 // counts (every row group of a batch but the table's last is whole vectors)
-void batch_selection(fls_table *t, ScanCtx &s, HostBatch &hb) {
+static void batch_selection(fls_table *t, ScanCtx &s, HostBatch &hb) {
     std::lock_guard<std::mutex> lk(s.mu);
     if (hb.sel_ready) return;
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
@@ -2723,7 +1985,7 @@ void batch_selection(fls_table *t, ScanCtx &s, HostBatch &hb) {
 
 // sticky scan error (call with s.mu held): every waiting and later acquire
 // returns it instead of waiting for a batch that will never arrive
-void set_scan_error(ScanCtx &s, int rc) {
+static void set_scan_error(ScanCtx &s, int rc) {
     if (rc && !s.err_rc) {
         s.err_rc = rc;
         s.err_msg = fls_last_error();
@@ -2737,7 +1999,7 @@ void set_scan_error(ScanCtx &s, int rc) {
 // error flags are the HostBatch's), and the batch's other row groups are found
 // on s.ready: the next batch's fill, decode and D2H overlap the hand-out of
 // this one's, and no consumer waits on another one's release.
-int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
+static int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
     if (!s.active) return fail(FLS_ERR_STATE, "scan not started");
     int g = -1;
     uint32_t rg;
@@ -2814,7 +2076,7 @@ int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
     out->ncols = ncols;
     out->nrows_scanned = out->nrows;
     out->sel = nullptr;
-    if (!s.terms.empty() && s.aggs.empty() && !s.tk) {
+    if (!s.terms.empty() && s.reduce == Reduce::None) {
         batch_selection(t, s, *hb);
         const uint32_t i = rg - hb->rg0;
         out->nrows = hb->sel_off[i + 1] - hb->sel_off[i];
@@ -2896,7 +2158,7 @@ int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
     return 1;
 }
 
-int scan_release(fls_table *t, ScanCtx &s, uint32_t rg) {
+static int scan_release(fls_table *t, ScanCtx &s, uint32_t rg) {
     std::lock_guard<std::mutex> lk(s.mu);
     auto it = std::find_if(s.out.begin(), s.out.end(), [&](const auto &o) { return o.first == rg; });
     if (!s.active || it == s.out.end()) return fail(FLS_ERR_ARG, "row group %u is not held by this scan", rg);
@@ -2937,7 +2199,7 @@ int scan_next(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
 }
 
 // fls_predicate[] -> host terms in the comparison domain, sorted by clause
-int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std::vector<HostTerm> &out) {
+static int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std::vector<HostTerm> &out) {
     out.clear();
     if (n && !p) return fail(FLS_ERR_ARG, "fls_scan_filter: NULL predicates");
     for (uint32_t i = 0; i < n; ++i) {
@@ -2996,7 +2258,7 @@ int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std::vector
     return 0;
 }
 
-int open_common(fls_connection *conn, fls_table *t, fls_table **out) {
+static int open_common(fls_connection *conn, fls_table *t, fls_table **out) {
     std::string why = parse_file(t->img, t->len, t->meta);
     if (!why.empty()) {
         delete t;
@@ -3012,7 +2274,16 @@ int open_common(fls_connection *conn, fls_table *t, fls_table **out) {
     return 0;
 }
 
-}  // namespace
+
+// The host batch that holds row group rg of the aggregate scan s.
+const HostBatch *held_batch(ScanCtx &s, uint32_t rg) {
+    std::lock_guard<std::mutex> lk(s.mu);
+    for (const auto &o : s.out)
+        if (o.first == rg) return o.second;
+    return nullptr;
+}
+
+FLS_ENGINE_END
 
 // ------------------------------------------------------------------------------
 // C-ABI
@@ -3042,36 +2313,6 @@ const char *fls_config_name(int i) {
     return i >= 0 && i < fls_config_count() ? kKnobs[i].name : nullptr;
 }
 
-int fls_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-int fls_device_alloc(int device, uint64_t bytes, void **ptr) {
-    if (!ptr) return fail(FLS_ERR_ARG, "fls_device_alloc: NULL out");
-    *ptr = nullptr;
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMalloc(ptr, std::max<uint64_t>(bytes, 1)));
-    return 0;
-}
-
-int fls_device_free(int device, void *ptr) {
-    if (!ptr) return 0;
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipFree(ptr));
-    return 0;
-}
-
-int fls_device_memcpy(int device, void *dst, const void *src, uint64_t bytes, int kind) {
-    if (!dst || !src) return fail(FLS_ERR_ARG, "fls_device_memcpy: NULL pointer");
-    const hipMemcpyKind k = kind == 0 ? hipMemcpyHostToDevice : kind == 1 ? hipMemcpyDeviceToHost
-                                                                           : hipMemcpyDeviceToDevice;
-    if (kind < 0 || kind > 2) return fail(FLS_ERR_ARG, "fls_device_memcpy: kind %d", kind);
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMemcpy(dst, src, bytes, k));
-    return 0;
-}
 
 int fls_connect(const int *devices, int ndevices, fls_connection **out) {
     if (!out) return fail(FLS_ERR_ARG, "fls_connect: NULL out");
@@ -3099,66 +2340,6 @@ void fls_disconnect(fls_connection *conn) {
     delete conn;
 }
 
-int fls_keyset_create(fls_connection *conn, const uint64_t *keys, uint64_t n, int kind, int form, fls_keyset **out) {
-    if (!conn || !out) return fail(FLS_ERR_ARG, "fls_keyset_create: NULL argument");
-    if (kind != FLS_KEYSET_SIGNED && kind != FLS_KEYSET_UNSIGNED)
-        return fail(FLS_ERR_ARG, "fls_keyset_create: kind %d (0 signed, 1 unsigned)", kind);
-    if (form < 0 || form > 2) return fail(FLS_ERR_ARG, "fls_keyset_create: form %d (0 auto, 1 bitmap, 2 hash)", form);
-    if (n > kMaxKeysetKeys)  // before keys is read
-        return fail(FLS_ERR_LIMIT, "fls_keyset_create: %llu keys (at most %llu, kMaxKeysetKeys)", (unsigned long long)n,
-                    (unsigned long long)kMaxKeysetKeys);
-    if (n && !keys) return fail(FLS_ERR_ARG, "fls_keyset_create: NULL keys");
-    auto ks = std::make_shared<KeySet>();
-    ks->conn = conn;
-    int rc;
-    try {
-        rc = keyset_build(keys, n, kind == FLS_KEYSET_SIGNED, (uint32_t)form, ks->img);
-    } catch (const std::bad_alloc &) {
-        return fail(FLS_ERR_NOMEM, "fls_keyset_create: out of memory");
-    }
-    if (rc == KS_TOO_WIDE)
-        return fail(FLS_ERR_LIMIT, "fls_keyset_create: a bitmap over [min, max] would cover more than 2^32 values");
-    if (rc != KS_OK) return fail(FLS_ERR_ARG, "fls_keyset_create: cannot build the set (%d)", rc);
-    KeySetRegistry &R = keyset_registry();
-    std::lock_guard<std::mutex> lk(R.mu);
-    const uint64_t h = KeySetRegistry::handle_of(R.next++);
-    R.live[h] = std::move(ks);
-    *out = (fls_keyset *)(uintptr_t)h;
-    return 0;
-}
-
-void fls_keyset_free(fls_keyset *set) {
-    KeySetRegistry &R = keyset_registry();
-    std::shared_ptr<KeySet> dead;  // released outside the lock
-    std::lock_guard<std::mutex> lk(R.mu);
-    auto it = R.live.find((uint64_t)(uintptr_t)set);
-    if (it == R.live.end()) return;
-    dead = std::move(it->second);
-    R.live.erase(it);
-}
-
-int fls_keyset_info(const fls_keyset *set, fls_keyset_info_t *info) {
-    auto ks = keyset_registry().find((uint64_t)(uintptr_t)set);
-    if (!ks || !info) return fail(FLS_ERR_ARG, "fls_keyset_info: not a live key set");
-    const KeysetImage &k = ks->img;
-    memset(info, 0, sizeof(*info));
-    info->count = k.keys.size();
-    info->form = k.form;
-    info->kind = k.is_signed ? FLS_KEYSET_SIGNED : FLS_KEYSET_UNSIGNED;
-    info->device_bytes = k.bytes();
-    info->capacity = k.capacity();
-    info->max_probe = k.max_probe;
-    info->min = k.min;
-    info->max = k.max;
-    info->empty = k.empty;
-    return 0;
-}
-
-int fls_keyset_contains(const fls_keyset *set, uint64_t key) {
-    auto ks = keyset_registry().find((uint64_t)(uintptr_t)set);
-    if (!ks) return fail(FLS_ERR_ARG, "fls_keyset_contains: not a live key set");
-    return keyset_contains(ks->img, key) ? 1 : 0;
-}
 
 int fls_release_device_memory(int device, uint64_t *freed_bytes) {
     const uint64_t b = release_idle_images(device < 0 ? -1 : device);
@@ -3338,7 +2519,12 @@ int fls_materialize(fls_table *t, uint32_t rg, const uint8_t *col_mask, fls_rowg
     const uint32_t G = (uint32_t)t->devices.size(), N = (uint32_t)t->meta.rgs.size();
     uint32_t g = 0;
     while (g + 1 < G && rg >= (uint64_t)N * (g + 1) / G) ++g;
-    int rc = scan_setup(t, t->mat, {t->devices[g]}, col_mask, rg, rg + 1, nullptr);
+    ScanPlan plan;
+    plan.devices = {t->devices[g]};
+    plan.col_mask = col_mask;
+    plan.rg0 = rg;
+    plan.rg1 = rg + 1;
+    int rc = scan_setup(t, t->mat, plan);
     if (!rc) rc = scan_start(t, t->mat);
     if (rc) return rc;
     rc = scan_next(t, t->mat, out);
@@ -3347,7 +2533,14 @@ int fls_materialize(fls_table *t, uint32_t rg, const uint8_t *col_mask, fls_rowg
 
 int fls_scan_begin(fls_table *t, const uint8_t *col_mask, uint32_t rg_begin, uint32_t rg_end) {
     if (!t) return fail(FLS_ERR_ARG, "fls_scan_begin: NULL table");
-    int rc = scan_setup(t, t->scan, t->devices, col_mask, rg_begin, rg_end, &t->filter);
+    ScanPlan plan;
+    plan.devices = t->devices;
+    plan.col_mask = col_mask;
+    plan.rg0 = rg_begin;
+    plan.rg1 = rg_end;
+    plan.filter = &t->filter;
+    plan.delivering_scan = true;
+    int rc = scan_setup(t, t->scan, plan);
     if (rc) return rc;
     return scan_start(t, t->scan);
 }
@@ -3360,668 +2553,6 @@ int fls_scan_filter(fls_table *t, const fls_predicate *preds, uint32_t n) {
     t->filter.swap(terms);
     return 0;
 }
-
-int fls_aggregate_exprs(fls_table *t, const fls_agg_expr *exprs, uint32_t n) {
-    if (!t || (!exprs && n)) return fail(FLS_ERR_ARG, "fls_aggregate_exprs: NULL argument");
-    if (n > kMaxAggs) return fail(FLS_ERR_ARG, "fls_aggregate_exprs: %u expressions (at most %u)", n, kMaxAggs);
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    for (uint32_t i = 0; i < n; ++i) {
-        const fls_agg_expr &e = exprs[i];
-        if (e.nfactors == 0 || e.nfactors > kMaxFactors)
-            return fail(FLS_ERR_ARG, "expression %u: %u factors (1 to %u)", i, e.nfactors, kMaxFactors);
-        for (uint32_t k = 0; k < e.nfactors; ++k) {
-            const fls_agg_factor &f = e.f[k];
-            if (f.sign != 1 && f.sign != -1)
-                return fail(FLS_ERR_ARG, "expression %u: factor %u has sign %d (+1 or -1)", i, k, (int)f.sign);
-            if (f.col >= ncols) return fail(FLS_ERR_ARG, "expression %u: column %u out of range", i, f.col);
-            const uint8_t ty = t->meta.cols[f.col].type;
-            if (type_is_string(ty) || type_is_float(ty))
-                return fail(FLS_ERR_ARG, "expression %u: a VARCHAR / BLOB / FLOAT / DOUBLE column (%u) cannot be a factor",
-                            i, f.col);
-        }
-    }
-    t->exprs.assign(exprs, exprs + n);
-    return 0;
-}
-
-}  // extern "C"
-
-namespace {
-
-// Largest magnitude of column c's non-NULL values in row group rg: from the
-// zone map, else the type's range.
-uint64_t max_magnitude(const fls_table *t, uint32_t rg, uint32_t c) {
-    const uint8_t ty = t->meta.cols[c].type;
-    const bool sign = type_is_signed(ty);
-    const auto &zs = t->meta.rgs[rg].zones;
-    if (!zs.empty() && (zs[c].flags & ZM_ALL_NULL)) return 0;
-    if (zs.empty() || !(zs[c].flags & ZM_VALID)) {
-        const int bits = type_value_bits(ty);
-        return sign ? 1ull << (bits - 1) : (bits == 64 ? ~0ull : (1ull << bits) - 1);
-    }
-    if (!sign) return std::max(zs[c].min, zs[c].max);
-    auto mag = [](uint64_t v) { return (int64_t)v < 0 ? 0 - v : v; };
-    return std::max(mag(zs[c].min), mag(zs[c].max));
-}
-
-// a * b rounded upwards (a, b >= 0)
-double mul_up(double a, double b) { return std::nextafter(a * b, HUGE_VAL); }
-// an upper bound of v as a double
-double dbl_up(uint64_t v) { return v == 0 ? 0.0 : std::nextafter((double)v, HUGE_VAL); }
-
-// An upper bound, as a double, of |k + s * x| over column c's non-NULL values
-// in row group rg (s = -1 when neg): the larger magnitude at the two ends of
-// the zone-map range (else the type's range), exact in 128 bits, then rounded
-// upwards.  0 for an all-NULL chunk: no row of it contributes.
-double max_factor(const fls_table *t, uint32_t rg, uint32_t c, bool neg, int64_t k) {
-    const uint8_t ty = t->meta.cols[c].type;
-    const bool sign = type_is_signed(ty);
-    const auto &zs = t->meta.rgs[rg].zones;
-    if (!zs.empty() && (zs[c].flags & ZM_ALL_NULL)) return 0.0;
-    __int128 lo, hi;
-    if (zs.empty() || !(zs[c].flags & ZM_VALID)) {
-        const int bits = type_value_bits(ty);
-        lo = sign ? -((__int128)1 << (bits - 1)) : 0;
-        hi = sign ? ((__int128)1 << (bits - 1)) - 1 : ((__int128)1 << bits) - 1;
-    } else if (sign) {
-        lo = (int64_t)zs[c].min;
-        hi = (int64_t)zs[c].max;
-    } else {
-        lo = zs[c].min;
-        hi = zs[c].max;
-    }
-    auto mag = [&](__int128 x) {
-        const __int128 v = (__int128)k + (neg ? -x : x);
-        return (unsigned __int128)(v < 0 ? -v : v);
-    };
-    const unsigned __int128 m = std::max(mag(lo), mag(hi));  // < 2^65
-    return m == 0 ? 0.0 : std::nextafter((double)m, HUGE_VAL);
-}
-
-// The argument checks fls_aggregate and fls_aggregate_grouped (`who`) share:
-// the aggregates into ha, or FLS_ERR_ARG before any device work.
-int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_spec *aggs, uint32_t n,
-                     uint32_t rg_begin, uint32_t rg_end, std::vector<HostAgg> &ha) {
-    if (n == 0 || n > kMaxAggs) return fail(FLS_ERR_ARG, "%s: %u aggregates (1 to %u per call)", who, n, kMaxAggs);
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    if (rg_end > t->meta.rgs.size() || rg_begin > rg_end)
-        return fail(FLS_ERR_ARG, "row-group range [%u,%u) out of bounds", rg_begin, rg_end);
-    ha.assign(n, HostAgg());
-    for (uint32_t i = 0; i < n; ++i) {
-        const fls_aggregate_spec &a = aggs[i];
-        if (a.fn > FLS_AGG_SUM_EXPR) return fail(FLS_ERR_ARG, "aggregate %u: unknown function %u", i, a.fn);
-        ha[i].fn = a.fn;
-        if (a.fn == FLS_AGG_COUNT_STAR) continue;
-        if (a.fn == FLS_AGG_SUM_EXPR) {  // (fls_aggregate_exprs checked the factors)
-            if (a.col >= t->exprs.size())
-                return fail(FLS_ERR_ARG, "aggregate %u: expression %u out of range (%u set by fls_aggregate_exprs)", i,
-                            a.col, (uint32_t)t->exprs.size());
-            const fls_agg_expr &e = t->exprs[a.col];
-            ha[i].nf = e.nfactors;
-            for (uint32_t k = 0; k < e.nfactors; ++k) {
-                ha[i].fcol[k] = e.f[k].col;
-                ha[i].fneg[k] = e.f[k].sign < 0;
-                ha[i].fk[k] = e.f[k].k;
-            }
-            continue;
-        }
-        if (a.col >= ncols) return fail(FLS_ERR_ARG, "aggregate %u: column %u out of range", i, a.col);
-        ha[i].col = a.col;
-        if (a.fn == FLS_AGG_COUNT) continue;
-        const uint8_t ty = t->meta.cols[a.col].type;
-        if (type_is_string(ty))
-            return fail(FLS_ERR_ARG, "aggregate %u: SUM / MIN / MAX of string column %u is not supported", i, a.col);
-        if (a.fn != FLS_AGG_SUM_PRODUCT) continue;
-        if (a.col2 >= ncols) return fail(FLS_ERR_ARG, "aggregate %u: column %u out of range", i, a.col2);
-        ha[i].col2 = a.col2;
-        const uint8_t ty2 = t->meta.cols[a.col2].type;
-        if (type_is_string(ty2))
-            return fail(FLS_ERR_ARG, "aggregate %u: SUM_PRODUCT of string column %u is not supported", i, a.col2);
-        if (type_is_float(ty) || type_is_float(ty2))
-            return fail(FLS_ERR_ARG, "aggregate %u: SUM_PRODUCT of a FLOAT / DOUBLE column is not supported", i);
-    }
-    // SUM_PRODUCT must stay below 2^127: bound it over the row groups the scan
-    // will read (rounded upwards) before anything is decoded
-    for (uint32_t i = 0; i < n; ++i) {
-        if (ha[i].fn == AGG_SUM_EXPR) {
-            // the same bound with max|k + s * x| per factor, which an affine
-            // term takes at an end of the column's range
-            double bound = 0;
-            for (uint32_t r = rg_begin; r < rg_end; ++r) {
-                if (!t->filter.empty() && !rowgroup_may_match(t, r, t->filter)) continue;
-                double term = dbl_up(t->meta.rgs[r].nrows);
-                for (uint32_t k = 0; k < ha[i].nf; ++k)
-                    term = mul_up(term, max_factor(t, r, ha[i].fcol[k], ha[i].fneg[k], ha[i].fk[k]));
-                bound = std::nextafter(bound + term, HUGE_VAL);
-            }
-            if (bound >= 0x1p127)
-                return fail(FLS_ERR_ARG, "aggregate %u: SUM_EXPR of expression %u may overflow 128 bits", i, aggs[i].col);
-            continue;
-        }
-        if (ha[i].fn != AGG_SUM_PRODUCT) continue;
-        double bound = 0;
-        for (uint32_t r = rg_begin; r < rg_end; ++r) {
-            if (!t->filter.empty() && !rowgroup_may_match(t, r, t->filter)) continue;
-            const double term = mul_up(mul_up(dbl_up(t->meta.rgs[r].nrows), dbl_up(max_magnitude(t, r, ha[i].col))),
-                                       dbl_up(max_magnitude(t, r, ha[i].col2)));
-            bound = std::nextafter(bound + term, HUGE_VAL);
-        }
-        if (bound >= 0x1p127)
-            return fail(FLS_ERR_ARG, "aggregate %u: SUM_PRODUCT of columns %u and %u may overflow 128 bits", i, ha[i].col,
-                        ha[i].col2);
-    }
-    return 0;
-}
-
-// The running value of one aggregate (of one group) on the host.
-struct AggAcc {
-    uint64_t count = 0;
-    unsigned __int128 sum = 0;
-    double fsum = -0.0;
-    uint64_t key = 0;
-    explicit AggAcc(uint8_t fn = 0) : key(fn == AGG_MIN ? ~0ull : 0ull) {}
-};
-
-bool agg_is_float(const fls_table *t, const HostAgg &h) {
-    return h.fn >= AGG_SUM && h.fn != AGG_SUM_EXPR && type_is_float(t->meta.cols[h.col].type);
-}
-
-// The grouped fold's addition of a vector's partial binary64 sum onto the
-// running sum.  It differs from acc + x only in which NaN comes back when both
-// are NaN: the partial's, which is what fls_aggregate's `fsum += x` returns as
-// built (x86 keeps its first operand's NaN, and that is the record); the
-// one-group test compares the two calls' NaN bits
-// (tests/test_group_aggregate.py).  fold_record keeps the plain expression.
-inline double add_partial(double acc, double x) { return x != x ? x : acc + x; }
-
-// One partial record into the running value; the records come in row order.
-void fold_record(AggAcc &a, uint8_t fn, bool flt, const AggRec &r) {
-    a.count += r.count;
-    if (r.count == 0) return;
-    switch (fn) {
-    case AGG_SUM:
-    case AGG_SUM_PRODUCT:
-    case AGG_SUM_EXPR:
-        if (flt) a.fsum += as_double(r.lo);
-        else a.sum += ((unsigned __int128)r.hi << 64) | r.lo;
-        break;
-    case AGG_MIN: a.key = std::min(a.key, r.lo); break;
-    case AGG_MAX: a.key = std::max(a.key, r.lo); break;
-    default: break;
-    }
-}
-
-// The running value as the caller sees it.
-void finish_value(const fls_table *t, const HostAgg &h, const AggAcc &a, fls_aggregate_value &o) {
-    memset(&o, 0, sizeof(o));
-    o.count = a.count;
-    if (h.fn <= AGG_COUNT) {
-        o.kind = FLS_AGGV_INT;
-        o.lo = a.count;
-        return;
-    }
-    if (a.count == 0) return;  // FLS_AGGV_NULL
-    const bool flt = agg_is_float(t, h);
-    o.kind = flt ? FLS_AGGV_DOUBLE : FLS_AGGV_INT;
-    if (h.fn == AGG_SUM || h.fn == AGG_SUM_PRODUCT || h.fn == AGG_SUM_EXPR) {
-        if (flt) {
-            memcpy(&o.lo, &a.fsum, 8);
-        } else {
-            o.lo = (uint64_t)a.sum;
-            o.hi = (uint64_t)(a.sum >> 64);
-        }
-    } else if (flt) {
-        const double d = agg_unkey_float(a.key);
-        memcpy(&o.lo, &d, 8);
-    } else if (type_is_signed(t->meta.cols[h.col].type)) {
-        const int64_t v = agg_unkey_int(a.key);
-        o.lo = (uint64_t)v;
-        o.hi = v < 0 ? ~0ull : 0ull;
-    } else {
-        o.lo = a.key;
-    }
-}
-
-// The host batch that holds row group rg of the aggregate scan s.
-const HostBatch *held_batch(ScanCtx &s, uint32_t rg) {
-    std::lock_guard<std::mutex> lk(s.mu);
-    for (const auto &o : s.out)
-        if (o.first == rg) return o.second;
-    return nullptr;
-}
-
-}  // namespace
-
-// One group's key values and running aggregates; the strings are copies.
-struct fls_group_result {
-    struct Key {
-        uint8_t kind = FLS_KEYV_NULL;
-        uint64_t lo = 0, hi = 0;
-        std::string str;
-    };
-    uint32_t nkeys = 0, naggs = 0;
-    std::vector<Key> keys;                    // ngroups x nkeys
-    std::vector<fls_aggregate_value> values;  // ngroups x naggs
-};
-
-extern "C" {
-
-int fls_aggregate(fls_table *t, const fls_aggregate_spec *aggs, uint32_t n, uint32_t rg_begin, uint32_t rg_end,
-                  fls_aggregate_value *out) {
-    if (!t || !aggs || !out) return fail(FLS_ERR_ARG, "fls_aggregate: NULL argument");
-    std::vector<HostAgg> ha;
-    if (int rc = check_aggregates(t, "fls_aggregate", aggs, n, rg_begin, rg_end, ha)) return rc;
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    const std::vector<uint8_t> none(std::max(1u, ncols), 0);  // nothing is delivered
-    ScanCtx &s = t->scan;
-    int rc = scan_setup(t, s, t->devices, none.data(), rg_begin, rg_end, &t->filter, &ha);
-    if (!rc) rc = scan_start(t, s);
-    if (rc) return rc;
-    // fold the per-vector records in row order
-    std::vector<AggAcc> acc;
-    for (uint32_t i = 0; i < n; ++i) acc.emplace_back(ha[i].fn);
-    fls_rowgroup rg;
-    while ((rc = scan_next(t, s, &rg)) == 1) {
-        const HostBatch *hb = held_batch(s, rg.rowgroup);
-        if (!hb) return fail(FLS_ERR_STATE, "internal: aggregate batch of row group %u not found", rg.rowgroup);
-        const uint64_t v0 = (t->meta.rgs[rg.rowgroup].first_row - t->meta.rgs[hb->rg0].first_row) / kVectorSize;
-        const uint64_t nv = (t->meta.rgs[rg.rowgroup].nrows + kVectorSize - 1) / kVectorSize;
-        for (uint64_t v = v0; v < v0 + nv && v < hb->nvec; ++v)
-            for (uint32_t i = 0; i < n; ++i) fold_record(acc[i], ha[i].fn, agg_is_float(t, ha[i]), hb->h_agg.p[v * n + i]);
-    }
-    if (rc < 0) return rc;
-    for (uint32_t i = 0; i < n; ++i) finish_value(t, ha[i], acc[i], out[i]);
-    return 0;
-}
-
-int fls_aggregate_grouped(fls_table *t, const uint32_t *keys, uint32_t nkeys, const fls_aggregate_spec *aggs,
-                          uint32_t n, uint32_t rg_begin, uint32_t rg_end, fls_group_result **out) {
-    if (!t || !out || (!keys && nkeys) || !aggs) return fail(FLS_ERR_ARG, "fls_aggregate_grouped: NULL argument");
-    *out = nullptr;
-    if (nkeys == 0 || nkeys > kMaxKeys)
-        return fail(FLS_ERR_ARG, "fls_aggregate_grouped: %u keys (1 to %u per call)", nkeys, kMaxKeys);
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    if (rg_end > t->meta.rgs.size() || rg_begin > rg_end)
-        return fail(FLS_ERR_ARG, "row-group range [%u,%u) out of bounds", rg_begin, rg_end);
-    std::vector<uint32_t> hk(keys, keys + nkeys);
-    for (uint32_t q = 0; q < nkeys; ++q) {
-        const uint32_t c = hk[q];
-        if (c >= ncols) return fail(FLS_ERR_ARG, "key %u: column %u out of range", q, c);
-        for (uint32_t p = 0; p < q; ++p)
-            if (hk[p] == c) return fail(FLS_ERR_ARG, "key %u: column %u is key %u already", q, c, p);
-        const uint8_t ty = t->meta.cols[c].type;
-        if (type_is_float(ty) || ty == TY_BLOB)
-            return fail(FLS_ERR_ARG, "key %u: a FLOAT / DOUBLE / BLOB column (%u) cannot be a GROUP BY key", q, c);
-        if (ty != TY_VARCHAR) continue;
-        for (const HostTerm &h : t->filter)
-            if (h.col == c)
-                return fail(FLS_ERR_ARG,
-                            "key %u: VARCHAR column %u is read by a filter term, which needs it decoded as strings, "
-                            "not as the dictionary codes a key is made of", q, c);
-        // the row groups the scan will read (the same set the SUM_PRODUCT bound walks)
-        for (uint32_t r = rg_begin; r < rg_end; ++r) {
-            if (!t->filter.empty() && !rowgroup_may_match(t, r, t->filter)) continue;
-            const ChunkHeader &h = t->meta.rgs[r].chunks[c].hdr;
-            if (h.enc != ENC_DICT)
-                return fail(FLS_ERR_ARG, "key %u: VARCHAR column %u is not dictionary-encoded in row group %u", q, c, r);
-            if (h.dict_count > 65536)
-                return fail(FLS_ERR_ARG, "key %u: the dictionary of VARCHAR column %u has %u entries in row group %u "
-                            "(at most 65536)", q, c, h.dict_count, r);
-        }
-    }
-    const KeyLayout L = key_layout(t, hk);
-    if (L.total > 128)
-        for (uint32_t q = 0, bits = nkeys; q < nkeys; ++q)
-            if ((bits += L.bits[q]) > 128)
-                return fail(FLS_ERR_ARG, "key %u: the packed key needs %u bits (at most 128: 8 x value bytes per integer "
-                            "key, 16 per VARCHAR key, 1 per key for NULL)", q, L.total);
-    std::vector<HostAgg> ha;
-    if (int rc = check_aggregates(t, "fls_aggregate_grouped", aggs, n, rg_begin, rg_end, ha)) return rc;
-    const std::vector<uint8_t> none(std::max(1u, ncols), 0);  // nothing is delivered
-    ScanCtx &s = t->scan;
-    int rc = scan_setup(t, s, t->devices, none.data(), rg_begin, rg_end, &t->filter, &ha, &hk);
-    if (!rc) rc = scan_start(t, s);
-    if (rc) return rc;
-    auto res = std::make_unique<fls_group_result>();
-    res->nkeys = nkeys;
-    res->naggs = n;
-    // the table's groups in first-occurrence order, found by key VALUE: per key
-    // its kind, then the integer's 16 bytes or the string's length and bytes
-    std::unordered_map<std::string, uint64_t> index;
-    std::vector<AggAcc> acc;  // ngroups x n
-    std::vector<uint32_t> fslot(n, 0);  // the FLOAT / DOUBLE sums, numbered as upload_agg_descs numbers them
-    for (uint32_t i = 0, k = 0; i < n; ++i)
-        if (ha[i].fn == AGG_SUM && agg_is_float(t, ha[i])) fslot[i] = k++;
-    std::vector<fls_group_result::Key> kv(nkeys);
-    std::string ser;
-    fls_rowgroup rg;
-    while ((rc = scan_next(t, s, &rg)) == 1) {
-        const HostBatch *hb = held_batch(s, rg.rowgroup);
-        if (!hb) return fail(FLS_ERR_STATE, "internal: aggregate batch of row group %u not found", rg.rowgroup);
-        const uint32_t nfsum = hb->g_nfsum, rg_vecs = hb->g_rg_vecs;
-        const uint8_t *base = hb->h_grp.p + (size_t)(rg.rowgroup - hb->rg0) * group_rg_stride(n, nfsum, rg_vecs);
-        GroupHdr hdr;
-        memcpy(&hdr, base, sizeof(hdr));
-        if (hdr.overflow || hdr.ngroups > kMaxRgGroups)  // (the device flag fails the batch's acquire first)
-            return fail(FLS_ERR_LIMIT, "grouped aggregate: row group %u exceeds the group capacity; fall back to a scan",
-                        rg.rowgroup);
-        const uint64_t *gkeys = (const uint64_t *)(base + sizeof(GroupHdr));
-        const AggRec *recs = (const AggRec *)(base + group_rg_recs_off());
-        const double *fvec = (const double *)(base + group_rg_fvec_off(n));
-        const uint32_t nv = (t->meta.rgs[rg.rowgroup].nrows + kVectorSize - 1) / kVectorSize;
-        for (uint32_t g = 0; g < hdr.ngroups; ++g) {
-            const unsigned __int128 pk = ((unsigned __int128)gkeys[2 * g + 1] << 64) | gkeys[2 * g];
-            ser.clear();
-            for (uint32_t q = 0; q < nkeys; ++q) {
-                fls_group_result::Key &k = kv[q];
-                k = fls_group_result::Key();
-                const uint8_t ty = t->meta.cols[hk[q]].type;
-                if (!((pk >> L.null_bit[q]) & 1)) {
-                    const uint64_t raw = (uint64_t)(pk >> L.shift[q]) & (L.bits[q] >= 64 ? ~0ull : (1ull << L.bits[q]) - 1);
-                    if (ty == TY_VARCHAR) {
-                        // the code through this row group's dictionary in the file image
-                        const ChunkRef &ch = t->meta.rgs[rg.rowgroup].chunks[hk[q]];
-                        if (raw >= ch.hdr.dict_count)
-                            return fail(FLS_ERR_FORMAT, "corrupt chunk: dictionary code %llu of %u in key column %u",
-                                        (unsigned long long)raw, ch.hdr.dict_count, hk[q]);
-                        const uint8_t *p;
-                        uint32_t len;
-                        dict_string(t->img + ch.off + ch.hdr.aux_off, ch.hdr.dict_count, (uint32_t)raw, p, len);
-                        k.kind = FLS_KEYV_STRING;
-                        k.str.assign((const char *)p, len);
-                    } else {
-                        k.kind = FLS_KEYV_INT;
-                        k.lo = raw;
-                        if (type_is_signed(ty) && L.bits[q] < 64 && ((raw >> (L.bits[q] - 1)) & 1)) k.lo |= ~0ull << L.bits[q];
-                        k.hi = type_is_signed(ty) && (int64_t)k.lo < 0 ? ~0ull : 0ull;
-                    }
-                }
-                ser.push_back((char)k.kind);
-                if (k.kind == FLS_KEYV_INT) {
-                    ser.append((const char *)&k.lo, 8);
-                } else if (k.kind == FLS_KEYV_STRING) {
-                    const uint64_t len = k.str.size();
-                    ser.append((const char *)&len, 8);
-                    ser.append(k.str);
-                }
-            }
-            auto it = index.find(ser);
-            uint64_t gi;
-            if (it == index.end()) {
-                gi = index.size();
-                index.emplace(ser, gi);
-                for (uint32_t q = 0; q < nkeys; ++q) res->keys.push_back(kv[q]);
-                for (uint32_t i = 0; i < n; ++i) acc.emplace_back(ha[i].fn);
-            } else {
-                gi = it->second;
-            }
-            for (uint32_t i = 0; i < n; ++i) {
-                const AggRec &r = recs[(size_t)g * n + i];
-                AggAcc &a = acc[gi * n + i];
-                if (ha[i].fn == AGG_SUM && agg_is_float(t, ha[i])) {
-                    // the vectors' sums one after the other, as the ungrouped fold adds them
-                    // (-0.0, which changes nothing, where the group has no row)
-                    a.count += r.count;
-                    const double *fv = fvec + ((size_t)g * nfsum + fslot[i]) * rg_vecs;
-                    for (uint32_t v = 0; v < nv && v < rg_vecs; ++v) a.fsum = add_partial(a.fsum, fv[v]);
-                } else {
-                    fold_record(a, ha[i].fn, false, r);
-                }
-            }
-        }
-    }
-    if (rc < 0) return rc;
-    const uint64_t ngroups = index.size();
-    res->values.resize(ngroups * n);
-    for (uint64_t g = 0; g < ngroups; ++g)
-        for (uint32_t i = 0; i < n; ++i) finish_value(t, ha[i], acc[g * n + i], res->values[g * n + i]);
-    *out = res.release();
-    return 0;
-}
-
-uint64_t fls_group_result_ngroups(const fls_group_result *r) { return r && r->nkeys ? r->keys.size() / r->nkeys : 0; }
-
-int fls_group_result_key(const fls_group_result *r, uint64_t group, uint32_t key, fls_group_key *out) {
-    if (!r || !out || key >= r->nkeys || group >= fls_group_result_ngroups(r))
-        return fail(FLS_ERR_ARG, "fls_group_result_key: key %u of group %llu out of range", key, (unsigned long long)group);
-    const fls_group_result::Key &k = r->keys[group * r->nkeys + key];
-    memset(out, 0, sizeof(*out));
-    out->kind = k.kind;
-    out->lo = k.lo;
-    out->hi = k.hi;
-    if (k.kind == FLS_KEYV_STRING) {
-        out->str = k.str.data();
-        out->str_len = k.str.size();
-    }
-    return 0;
-}
-
-const fls_aggregate_value *fls_group_result_values(const fls_group_result *r, uint64_t group) {
-    if (!r || group >= fls_group_result_ngroups(r)) return nullptr;
-    return r->values.data() + group * r->naggs;
-}
-
-void fls_group_result_free(fls_group_result *r) { delete r; }
-
-}  // extern "C"
-
-// The winners of fls_topn in result order: their global rows and, per
-// delivered column, their values (the scan's physical layout), validity words
-// and the bytes of their long strings -- all copies.
-struct fls_topn_result {
-    uint32_t ncols = 0;
-    std::vector<uint64_t> rows;
-    std::vector<uint8_t> delivered;               // per column
-    std::vector<std::vector<uint8_t>> values;     // per column: rows x out_bytes
-    std::vector<std::vector<uint64_t>> validity;  // per column: (rows + 63) / 64 words
-    std::vector<uint8_t> has_null;                // per column: a returned row is NULL
-    std::vector<std::unique_ptr<uint8_t[]>> heap; // strings over 12 bytes, one allocation each
-    double phase_ms[2] = {0, 0};                  // host clock: the selection scan, the late materialisation
-};
-
-namespace {
-
-// fls_topn's argument checks (no device work); FLS_ERR_ARG messages start "order key:".
-int check_topn(const fls_table *t, const fls_order_key *key, uint32_t k, const uint8_t *col_mask, uint32_t rg_begin,
-               uint32_t rg_end) {
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    if (key->col >= ncols) return fail(FLS_ERR_ARG, "order key: column %u out of range", key->col);
-    const ColumnMeta &cm = t->meta.cols[key->col];
-    if (type_is_string(cm.type))
-        return fail(FLS_ERR_ARG, "order key: a VARCHAR / BLOB column (%u) cannot be an ORDER BY key", key->col);
-    if (!topn_key_type(cm))
-        return fail(FLS_ERR_ARG, "order key: DECIMAL(%u) column %u is wider than 64 bits", (unsigned)cm.width, key->col);
-    if (col_mask) {
-        bool any = false;
-        for (uint32_t c = 0; c < ncols; ++c) any = any || col_mask[c];
-        if (!any) return fail(FLS_ERR_ARG, "order key: col_mask names no column to deliver");
-    }
-    if (rg_end > t->meta.rgs.size() || rg_begin > rg_end)
-        return fail(FLS_ERR_ARG, "order key: row-group range [%u,%u) out of bounds", rg_begin, rg_end);
-    if (k > kMaxTopN)
-        return fail(FLS_ERR_LIMIT, "fls_topn: k = %u is above %u (kMaxTopN); scan the columns (fls_scan_begin) and sort "
-                    "the rows instead", k, kMaxTopN);
-    for (uint32_t r = rg_begin; r < rg_end; ++r)
-        if (t->meta.rgs[r].nrows > (1u << 30))
-            return fail(FLS_ERR_LIMIT, "fls_topn: row group %u has more than 2^30 rows", r);
-    return 0;
-}
-
-struct TopnCand {
-    uint32_t rank;
-    uint64_t key;
-    uint64_t row;   // global
-    uint32_t rg, rg_row;
-};
-inline bool cand_less(const TopnCand &a, const TopnCand &b) {
-    if (a.rank != b.rank) return a.rank < b.rank;
-    if (a.key != b.key) return a.key < b.key;
-    return a.row < b.row;
-}
-
-// Phase 2 of fls_topn: the winners' values of the masked columns, copied out
-// of their row groups (ascending), decoded on the context and by the path
-// fls_materialize uses.
-int topn_gather(fls_table *t, const std::vector<TopnCand> &win, const uint8_t *col_mask, fls_topn_result &res) {
-    const uint32_t ncols = res.ncols;
-    const size_t n = win.size();
-    std::vector<uint32_t> order(n);
-    for (size_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return win[a].row < win[b].row; });
-    for (uint32_t c = 0; c < ncols; ++c) {
-        if (!res.delivered[c]) continue;
-        res.values[c].assign(n * (size_t)out_bytes_of(t, c), 0);
-        res.validity[c].assign(std::max<size_t>(1, (n + 63) / 64), ~0ull);
-    }
-    // one delivering scan of the winners' row groups on the materialize context: no filter, every row
-    // delivered at full width, the batches pipelined and sharded as in any scan
-    std::vector<uint32_t> rgs;
-    for (size_t j = 0; j < n; ++j)
-        if (rgs.empty() || rgs.back() != win[order[j]].rg) rgs.push_back(win[order[j]].rg);
-    ScanCtx &s = t->mat;
-    int rc = scan_setup(t, s, t->devices, col_mask, rgs.front(), rgs.back() + 1, nullptr, nullptr, nullptr, nullptr, 0, &rgs);
-    if (!rc) rc = scan_start(t, s);
-    if (rc) return rc;
-    size_t i = 0;
-    while (i < n) {
-        const uint32_t rg = win[order[i]].rg;
-        fls_rowgroup out;
-        rc = scan_next(t, s, &out);
-        if (rc < 0) return rc;
-        if (rc == 0 || out.rowgroup != rg)
-            return fail(FLS_ERR_STATE, "internal: the winners' scan did not deliver row group %u", rg);
-        for (; i < n && win[order[i]].rg == rg; ++i) {
-            const uint32_t dst = order[i], row = win[dst].rg_row;
-            if (row >= out.nrows) return fail(FLS_ERR_STATE, "internal: winner row %u past row group %u", row, rg);
-            for (uint32_t c = 0; c < ncols; ++c) {
-                if (!res.delivered[c]) continue;
-                if (!out.columns[c]) return fail(FLS_ERR_STATE, "internal: column %u of row group %u not decoded", c, rg);
-                const size_t ob = (size_t)out_bytes_of(t, c);
-                uint8_t *d = res.values[c].data() + dst * ob;
-                const uint64_t *vw = out.validity[c];
-                if (vw && !((vw[row >> 6] >> (row & 63)) & 1)) {  // NULL: the placeholder stays behind
-                    res.validity[c][dst >> 6] &= ~(1ull << (dst & 63));
-                    res.has_null[c] = 1;
-                    continue;
-                }
-                memcpy(d, (const uint8_t *)out.columns[c] + row * ob, ob);
-                if (!type_is_string(t->meta.cols[c].type)) continue;
-                uint32_t len;
-                memcpy(&len, d, 4);
-                if (len <= 12) continue;  // inline
-                const uint8_t *src;
-                memcpy(&src, d + 8, 8);
-                res.heap.emplace_back(new uint8_t[len]);
-                memcpy(res.heap.back().get(), src, len);
-                const uint8_t *own = res.heap.back().get();
-                memcpy(d + 8, &own, 8);
-            }
-        }
-    }
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int fls_topn(fls_table *t, const fls_order_key *key, uint32_t k, const uint8_t *col_mask, uint32_t rg_begin,
-             uint32_t rg_end, fls_topn_result **out) {
-    if (!t || !key || !out) return fail(FLS_ERR_ARG, "fls_topn: NULL argument");
-    *out = nullptr;
-    if (int rc = check_topn(t, key, k, col_mask, rg_begin, rg_end)) return rc;
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    auto res = std::make_unique<fls_topn_result>();
-    res->ncols = ncols;
-    res->delivered.assign(ncols, 1);
-    if (col_mask)
-        for (uint32_t c = 0; c < ncols; ++c) res->delivered[c] = col_mask[c] ? 1 : 0;
-    res->values.resize(ncols);
-    res->validity.resize(ncols);
-    res->has_null.assign(ncols, 0);
-    std::vector<TopnCand> best;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (k > 0) {
-        // phase 1: the row groups' candidate lists, merged in row-group order
-        const std::vector<uint8_t> none(std::max(1u, ncols), 0);  // nothing is delivered
-        ScanCtx &s = t->scan;
-        int rc = scan_setup(t, s, t->devices, none.data(), rg_begin, rg_end, &t->filter, nullptr, nullptr, key, k);
-        if (!rc) rc = scan_start(t, s);
-        if (rc) return rc;
-        const size_t stride = topn_stride(k);
-        std::vector<TopnCand> inc, merged;
-        fls_rowgroup rg;
-        while ((rc = scan_next(t, s, &rg)) == 1) {
-            const HostBatch *hb = held_batch(s, rg.rowgroup);
-            if (!hb) return fail(FLS_ERR_STATE, "internal: top-N batch of row group %u not found", rg.rowgroup);
-            const uint8_t *base = hb->h_topn.p + (size_t)(rg.rowgroup - hb->rg0) * stride;
-            TopnHdr hdr;
-            memcpy(&hdr, base, sizeof(hdr));
-            const uint32_t rg_rows = t->meta.rgs[rg.rowgroup].nrows;
-            // a record's row counts from the batch's first row
-            const uint64_t rg_off = t->meta.rgs[rg.rowgroup].first_row - t->meta.rgs[hb->rg0].first_row;
-            if (hdr.count > k || hdr.count > rg_rows)  // never indexed with
-                return fail(FLS_ERR_FORMAT, "top-N: row group %u reports %u candidates (k = %u, %u rows)", rg.rowgroup,
-                            hdr.count, k, rg_rows);
-            const TopnRec *recs = (const TopnRec *)(base + sizeof(TopnHdr));
-            inc.clear();
-            for (uint32_t i = 0; i < hdr.count; ++i) {
-                const TopnRec &r = recs[i];
-                if (r.row < rg_off || r.row - rg_off >= rg_rows || r.rank > 1)
-                    return fail(FLS_ERR_FORMAT, "top-N: candidate %u of row group %u names batch row %u (its rows: %llu "
-                                "to %llu; rank %u)", i, rg.rowgroup, r.row, (unsigned long long)rg_off,
-                                (unsigned long long)(rg_off + rg_rows), r.rank);
-                const uint32_t rg_row = (uint32_t)(r.row - rg_off);
-                inc.push_back(TopnCand{r.rank, r.key, rg.first_row + rg_row, rg.rowgroup, rg_row});
-            }
-            if (!std::is_sorted(inc.begin(), inc.end(), cand_less))
-                return fail(FLS_ERR_FORMAT, "top-N: the candidates of row group %u are not in order", rg.rowgroup);
-            merged.resize(best.size() + inc.size());
-            std::merge(best.begin(), best.end(), inc.begin(), inc.end(), merged.begin(), cand_less);
-            if (merged.size() > k) merged.resize(k);
-            best.swap(merged);
-        }
-        if (rc < 0) return rc;
-    }
-    res->rows.reserve(best.size());
-    for (const TopnCand &c : best) res->rows.push_back(c.row);
-    const auto t1 = std::chrono::steady_clock::now();
-    // phase 2: late materialisation of the winners
-    if (!best.empty())
-        if (int rc = topn_gather(t, best, col_mask, *res)) return rc;
-    res->phase_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    res->phase_ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    *out = res.release();
-    return 0;
-}
-
-int fls_topn_pruned(const fls_table *t, const fls_order_key *key, uint32_t k, uint32_t rg_begin, uint32_t rg_end) {
-    if (!t || !key) return fail(FLS_ERR_ARG, "fls_topn_pruned: NULL argument");
-    if (int rc = check_topn(t, key, k, nullptr, rg_begin, rg_end)) return rc;
-    std::vector<uint32_t> rgs;
-    return (int)select_rowgroups(t, t->filter, key, k, rg_begin, rg_end, rgs);
-}
-
-uint64_t fls_topn_result_nrows(const fls_topn_result *r) { return r ? r->rows.size() : 0; }
-
-const uint64_t *fls_topn_result_rows(const fls_topn_result *r) { return r ? r->rows.data() : nullptr; }
-
-int fls_topn_result_column(const fls_topn_result *r, uint32_t col, const void **values, const uint64_t **validity) {
-    if (!r || col >= r->ncols || !r->delivered[col])
-        return fail(FLS_ERR_ARG, "fls_topn_result_column: column %u was not delivered", col);
-    if (values) *values = r->values[col].data();
-    if (validity) *validity = r->has_null[col] ? r->validity[col].data() : nullptr;
-    return 0;
-}
-
-int fls_topn_result_times(const fls_topn_result *r, double *phase1_ms, double *phase2_ms) {
-    if (!r) return fail(FLS_ERR_ARG, "fls_topn_result_times: NULL result");
-    if (phase1_ms) *phase1_ms = r->phase_ms[0];
-    if (phase2_ms) *phase2_ms = r->phase_ms[1];
-    return 0;
-}
-
-void fls_topn_result_free(fls_topn_result *r) { delete r; }
 
 int fls_scan_pruned(const fls_table *t) {
     if (!t) return fail(FLS_ERR_ARG, "fls_scan_pruned: NULL table");
@@ -4100,530 +2631,5 @@ int fls_scan_release(fls_table *t, uint32_t rowgroup) {
     if (!t) return fail(FLS_ERR_ARG, "fls_scan_release: NULL table");
     return scan_release(t, t->scan, rowgroup);
 }
-
-// ---- device-resident mode -------------------------------------------------
-
-}  // extern "C"
-
-namespace {
-
-// ---- HBM placement of the resident output columns --------------
-// The decode's write stream runs at a speed set by where the driver placed
-// the output buffers (the same decode at the same virtual addresses: 2.63-3.13
-// ms on lineitem_full SF12.5 from one allocation to the next,
-// profiles/r6/placement_*.txt).  A candidate set of output columns is rated by
-// probe_placement: the decode's chunk-order write stream against a linear fill
-// of the same buffers (the fill runs at the same speed on every placement, so
-// the ratio q rates the placement on this box).  Up to FLS_PLACEMENT_TRIES
-// sets (default 8) are tried, the best kept, the search ending early once
-// q >= FLS_PLACEMENT_GOOD / 1000 (default 990: at 0.93-0.97 some placements
-// still decoded slowly, profiles/r6/placement_q_sf25_r6q.txt).
-int placement_tries() { return (int)std::max<int64_t>(1, knob_value("FLS_PLACEMENT_TRIES")); }
-
-struct PlacementRating {
-    float chunk_ms = 0, fill_ms = 0;
-    double q = 0;
-};
-
-int rate_outputs(const fls_table *t, const Resident &r, const std::vector<DevBuf<uint8_t>> &outs,
-                 PlacementRating &pr) {
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    std::vector<ProbeRegion> reg;
-    for (uint32_t c = 0; c < ncols; ++c)
-        for (uint32_t g = r.rg0; g < r.rg1; ++g) {
-            const uint64_t ob = out_bytes_of(t, c);
-            const uint64_t bytes = (t->meta.rgs[g].nrows * ob) & ~1023ull;
-            if (bytes) reg.push_back({outs[c].p + (t->meta.rgs[g].first_row - r.first_row) * ob, bytes});
-        }
-    // the decode's queue order: largest output first
-    std::stable_sort(reg.begin(), reg.end(), [](const ProbeRegion &a, const ProbeRegion &b) { return a.bytes > b.bytes; });
-    DevBuf<ProbeRegion> d;
-    HIP_TRY(d.alloc(r.dev, reg.size()));
-    HIP_TRY(hipMemcpy(d.p, reg.data(), reg.size() * sizeof(ProbeRegion), hipMemcpyHostToDevice));
-    std::vector<uint8_t *> bufs(ncols);
-    std::vector<uint64_t> sizes(ncols);
-    for (uint32_t c = 0; c < ncols; ++c) {
-        bufs[c] = outs[c].p;
-        sizes[c] = (r.rows * out_bytes_of(t, c)) & ~4095ull;
-    }
-    HIP_TRY(probe_placement(d.p, (uint32_t)reg.size(), bufs.data(), sizes.data(), ncols, 2, r.stream, &pr.chunk_ms,
-                            &pr.fill_ms));
-    pr.q = pr.chunk_ms > 0 ? pr.fill_ms / pr.chunk_ms : 0;
-    return 0;
-}
-
-int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask);
-
-// A candidate set rated by one real decode launch of every column (the
-// launch after a warm-up one, HIP events): at SF100 the write probe rated every
-// set >= 0.99 while the main columns still decoded up to 5 % slower on some
-// sets (profiles/r6/placement_sels_sf100_r6w.txt), and four sets rated by
-// their decode differed by 3-4 % within one upload, the kept one decoding
-// within 0.3 % of its rating afterwards (placement_dec_sf100_r6x.txt).  The
-// launch's errors are not the upload's: a failure (ms < 0) falls back to the
-// write probe.
-float decode_rating(fls_table *t, Resident &r) {
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    const std::vector<uint8_t> mask(ncols, 1);
-    r.invalidate();  // descriptors point at the current outputs
-    const uint32_t ev0 = r.ev_used;
-    struct RatingScope {
-        RatingScope() { rating_launch() = true; }
-        ~RatingScope() { rating_launch() = false; }
-    } scope;
-    // two warm-up launches (a fresh set decodes ~4 % slower at first), then
-    // the fastest of three
-    constexpr int kWarm = 2, kTimed = 3;
-    bool ok = true;
-    for (int i = 0; i < kWarm + kTimed && ok; ++i) ok = decode_part(t, r, mask) == 0;
-    ok = ok && hipStreamSynchronize(r.stream) == hipSuccess;
-    float ms = -1;
-    for (int i = kWarm; i < kWarm + kTimed && ok; ++i) {
-        float x = 0;
-        ok = hipEventElapsedTime(&x, r.ev_pool[ev0 + 2 * i], r.ev_pool[ev0 + 2 * i + 1]) == hipSuccess;
-        if (ok && (ms < 0 || x < ms)) ms = x;
-    }
-    uint32_t e = 0;
-    ok = ok && hipMemcpy(&e, r.err.p, sizeof(e), hipMemcpyDeviceToHost) == hipSuccess && e == 0;
-    (void)hipGetLastError();
-    (void)hipMemset(r.err.p, 0, sizeof(uint32_t));
-    r.ev_used = ev0;
-    r.invalidate();
-    return ok ? ms : -1.0f;
-}
-
-// A candidate placement: a new set of output columns, new FSST heaps
-// (FLS_PLACEMENT_HEAPS, default 1) and a new copy of the compressed image
-// (FLS_PLACEMENT_IMAGE, default 1): with all three re-drawn the decode-rated
-// SF100 step ran 20.65-20.75 ms against 20.91-21.05 for outputs alone, four
-// interleaved bench runs each (profiles/r6/ab_placement_candidates_r6af.txt).
-// swap_into exchanges it with the part's current buffers.
-struct Candidate {
-    std::vector<DevBuf<uint8_t>> out, heap;
-    DevBuf<uint8_t> img;
-    void clear() {
-        out.clear();
-        heap.clear();
-        img.release();
-    }
-    void swap_into(Resident &r) {
-        std::swap(r.d_out, out);
-        if (!heap.empty()) std::swap(r.d_heap, heap);
-        if (img.p) {
-            std::swap(r.img.p, img.p);
-            std::swap(r.img.n, img.n);
-            std::swap(r.img.dev, img.dev);
-        }
-    }
-};
-bool placement_flag(const char *name) { return knob_value(name) != 0; }
-
-// a new candidate (plain hipMalloc: a speculative set must not evict cached
-// images), or false when it does not fit
-bool alloc_candidate(const fls_table *t, const Resident &r, uint64_t set_bytes, Candidate &cand) {
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    const bool heaps = placement_flag("FLS_PLACEMENT_HEAPS"), image = placement_flag("FLS_PLACEMENT_IMAGE");
-    uint64_t extra = image ? r.img.n : 0;
-    for (uint32_t c = 0; heaps && c < ncols; ++c) extra += r.d_heap[c].p ? r.d_heap[c].n : 0;
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < set_bytes + extra + (set_bytes + extra) / 8 + (1ull << 30)) {
-        (void)hipGetLastError();
-        return false;  // no room for a second set
-    }
-    cand.clear();
-    auto make = [&](DevBuf<uint8_t> &b, size_t n) {
-        if (hipMalloc((void **)&b.p, std::max<size_t>(1, n)) != hipSuccess) {
-            (void)hipGetLastError();
-            b.p = nullptr;
-            return false;
-        }
-        b.n = n;
-        b.dev = r.dev;
-        return true;
-    };
-    cand.out.resize(ncols);
-    bool ok = true;
-    for (uint32_t c = 0; c < ncols && ok; ++c) ok = make(cand.out[c], r.rows * out_bytes_of(t, c));
-    if (ok && heaps) {
-        cand.heap.resize(ncols);
-        for (uint32_t c = 0; c < ncols && ok; ++c)
-            if (r.d_heap[c].p) ok = make(cand.heap[c], r.d_heap[c].n);
-    }
-    if (ok && image) ok = make(cand.img, r.img.n) && hipMemcpy(cand.img.p, r.img.p, r.img.n, hipMemcpyDeviceToDevice) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        cand.clear();  // frees the ones made
-    }
-    return ok;
-}
-
-int choose_placement(fls_table *t, Resident &r) {
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    uint64_t set_bytes = 0;
-    for (uint32_t c = 0; c < ncols; ++c) set_bytes += r.rows * out_bytes_of(t, c);
-    if (set_bytes < (256ull << 20)) return 0;  // small outputs: nothing to gain
-    const bool dbg = getenv("FLS_DEBUG") != nullptr;
-    // 1. by decode time: FLS_PLACEMENT_DECODE sets (default 6), the fastest kept
-    const int ndec = (int)std::max<int64_t>(0, knob_value("FLS_PLACEMENT_DECODE"));
-    float best_ms = ndec > 1 ? decode_rating(t, r) : -1.0f;
-    if (best_ms > 0) {
-        if (dbg) fprintf(stderr, "DEBUG: placement dev %d set 0: decode %.3f ms\n", r.dev, best_ms);
-        int kept = 0;
-        Candidate cand;
-        for (int k = 1; k < ndec && alloc_candidate(t, r, set_bytes, cand); ++k) {
-            cand.swap_into(r);  // the candidate decodes in place of the current set
-            const float ms = decode_rating(t, r);
-            if (dbg) fprintf(stderr, "DEBUG: placement dev %d set %d: decode %.3f ms\n", r.dev, k, ms);
-            if (ms > 0 && ms < best_ms) {
-                best_ms = ms;  // keep it: the previous set is freed with cand
-                kept = k;
-            } else {
-                cand.swap_into(r);  // back to the current set; the candidate goes
-            }
-            cand.clear();
-        }
-        r.placement_ms = best_ms;
-        if (dbg) fprintf(stderr, "DEBUG: placement dev %d kept set %d (decode %.3f ms)\n", r.dev, kept, best_ms);
-        return 0;
-    }
-    // 2. by the write probe: up to FLS_PLACEMENT_TRIES sets, stop at q >= good
-    const int tries = placement_tries();
-    if (tries <= 1) return 0;
-    const double good = knob_value("FLS_PLACEMENT_GOOD") / 1000.0;  // per mille
-    PlacementRating best;
-    if (const int rc = rate_outputs(t, r, r.d_out, best)) return rc;
-    if (dbg)
-        fprintf(stderr, "DEBUG: placement dev %d set 0: chunk order %.3f ms, fill %.3f ms, q %.3f\n", r.dev,
-                best.chunk_ms, best.fill_ms, best.q);
-    int kept = 0;
-    Candidate cand;
-    for (int k = 1; k < tries && best.q < good && alloc_candidate(t, r, set_bytes, cand); ++k) {
-        PlacementRating pr;
-        if (const int rc = rate_outputs(t, r, cand.out, pr)) return rc;
-        if (dbg)
-            fprintf(stderr, "DEBUG: placement dev %d set %d: chunk order %.3f ms, fill %.3f ms, q %.3f\n", r.dev, k,
-                    pr.chunk_ms, pr.fill_ms, pr.q);
-        if (pr.q > best.q) {
-            cand.swap_into(r);  // the previous set is freed with cand
-            best = pr;
-            kept = k;
-        }
-        cand.clear();
-    }
-    r.placement_q = best.q;
-    if (dbg) fprintf(stderr, "DEBUG: placement dev %d kept set %d (q %.3f)\n", r.dev, kept, best.q);
-    return 0;
-}
-
-// Upload one GPU's part: row groups [rg0, rg1) verbatim, their string_t
-// tables, HBM output columns and FSST heaps.
-int upload_part(fls_table *t, Resident &r) {
-    HIP_TRY(hipSetDevice(r.dev));
-    if (!r.stream) HIP_TRY(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));
-    uint64_t lo, hi;
-    rg_byte_range(t->meta, r.rg0, r.rg1, lo, hi);
-    r.base = lo;
-    HIP_TRY(r.img.alloc(r.dev, hi - lo + kImagePad));
-    HIP_TRY(hipMemcpy(r.img.p, t->img + lo, hi - lo, hipMemcpyHostToDevice));
-    std::vector<StrT> host;  // (the resident part keeps only the device tables)
-    int rc = build_strtabs(t, r.dev, r.rg0, r.rg1, r.strtab, r.strtab_off, host);
-    if (rc) return rc;
-    HIP_TRY(r.err.alloc(r.dev, 1));
-    HIP_TRY(hipMemset(r.err.p, 0, sizeof(uint32_t)));
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    r.first_row = t->meta.rgs[r.rg0].first_row;
-    r.rows = t->meta.rgs[r.rg1 - 1].first_row + t->meta.rgs[r.rg1 - 1].nrows - r.first_row;
-    r.d_out.resize(ncols);
-    for (uint32_t c = 0; c < ncols; ++c) HIP_TRY(r.d_out[c].alloc(r.dev, r.rows * out_bytes_of(t, c)));
-    // FSST heaps: chunk heaps back to back per column, host copy for string_t
-    r.heap_off.assign((size_t)(r.rg1 - r.rg0) * ncols, 0);
-    r.d_heap.resize(ncols);
-    r.h_heap.resize(ncols);
-    for (uint32_t c = 0; c < ncols; ++c) {
-        uint64_t tot = 0;
-        for (uint32_t g = r.rg0; g < r.rg1; ++g) {
-            r.heap_off[(size_t)(g - r.rg0) * ncols + c] = tot;
-            if (is_fsst(t, g, c)) tot += t->meta.rgs[g].chunks[c].hdr.reserved1;
-        }
-        if (tot) {
-            HIP_TRY(r.d_heap[c].alloc(r.dev, tot));
-            HIP_TRY(r.h_heap[c].alloc(tot));
-        } else {
-            r.d_heap[c].release();
-            r.h_heap[c].release();
-        }
-    }
-    r.invalidate();
-    r.mask.clear();
-    if (const int prc = choose_placement(t, r)) return prc;
-    if (getenv("FLS_DEBUG")) {  // buffer placement (decode speed by buffer address)
-        fprintf(stderr, "DEBUG: part dev %d rg [%u, %u) image %p %llu B\n", r.dev, r.rg0, r.rg1, (void *)r.img.p,
-                (unsigned long long)(hi - lo));
-        for (uint32_t c = 0; c < ncols; ++c)
-            fprintf(stderr, "DEBUG:   col %u out %p %llu B heap %p\n", c, (void *)r.d_out[c].p,
-                    (unsigned long long)(r.rows * out_bytes_of(t, c)), (void *)r.d_heap[c].p);
-    }
-    return 0;
-}
-
-// Enqueue one decode launch of the selected columns on part r (asynchronous).
-int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask) {
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    HIP_TRY(hipSetDevice(r.dev));
-    const int64_t policy = decode_policy();
-    if (mask != r.mask || !r.list_built || policy != r.policy) {
-        // (re)build the launch descriptor list: column-major task order, so
-        // concurrent waves stream one column's consecutive row groups
-        std::vector<DevChunk> chunks;
-        ByteCount bc;
-        for (uint32_t c = 0; c < ncols; ++c) {
-            if (!mask[c]) continue;
-            for (uint32_t g = r.rg0; g < r.rg1; ++g) {
-                const ChunkRef &ch = t->meta.rgs[g].chunks[c];
-                const uint64_t so = r.strtab_off[(size_t)(g - r.rg0) * ncols + c];
-                const uint8_t *dict = so == UINT64_MAX ? nullptr : (const uint8_t *)(r.strtab.p + so);
-                uint8_t *out = r.d_out[c].p + (t->meta.rgs[g].first_row - r.first_row) * out_bytes_of(t, c);
-                const uint64_t ho = r.heap_off[(size_t)(g - r.rg0) * ncols + c];
-                chunks.push_back(make_devchunk(t, g, c, r.img.p + (ch.off - r.base), dict, out, &bc,
-                                               r.d_heap[c].p ? r.d_heap[c].p + ho : nullptr,
-                                               r.h_heap[c].p ? r.h_heap[c].p + ho : nullptr));
-            }
-        }
-        const int64_t lpol = launch_policy(policy, chunks, bc.geom);
-        std::vector<DevChunk> dictwg;
-        r.nmain = order_for_launch(chunks, &r.fsst, lpol, &dictwg);
-        // one DictVec per vector of the chunks the dictionary-string grid takes,
-        // from the host image's VecMeta arrays (validated when the file was read)
-        std::vector<DictVec> dvecs;
-        for (const DevChunk &d : dictwg) {
-            const uint8_t *meta = t->img + r.base + (d.chunk - r.img.p) + d.meta_off;
-            for (uint32_t v = 0; v < d.nvec; ++v) {
-                VecMeta vm;
-                memcpy(&vm, meta + 32ull * v, 32);
-                dvecs.push_back(DictVec{d.chunk + d.packed_off + vm.packed_off, d.dict,
-                                        d.out + (size_t)v * kVectorSize * 16, (uint32_t)vm.for_base,
-                                        (uint32_t)vm.nvals | (uint32_t)vm.bw << 11 | d.dict_count << 17});
-            }
-        }
-        if (getenv("FLS_DEBUG")) {
-            size_t kept = 0;
-            for (size_t i = 0; i < r.nmain; ++i) kept += chunks[i].enc == ENC_DICT && chunks[i].ob == 16;
-            fprintf(stderr, "DEBUG: dictstr_decode_kernel takes %zu chunks (%zu vectors), %zu DICT VARCHAR chunks stay "
-                            "on the main decode\n", dictwg.size(), dvecs.size(), kept);
-        }
-        r.policy = policy;
-        r.lpolicy = lpol;
-        const size_t k = chunks.size();
-        r.split = append_split(chunks, r.nmain, bc.geom, lpol);
-        HIP_TRY(hipStreamSynchronize(r.stream));
-        HIP_TRY(r.d_chunks.alloc(r.dev, chunks.size()));
-        HIP_TRY(hipMemcpy(r.d_chunks.p, chunks.data(), chunks.size() * sizeof(DevChunk), hipMemcpyHostToDevice));
-        HIP_TRY(r.d_dictvecs.alloc(r.dev, dvecs.size()));
-        if (!dvecs.empty())
-            HIP_TRY(hipMemcpy(r.d_dictvecs.p, dvecs.data(), dvecs.size() * sizeof(DictVec), hipMemcpyHostToDevice));
-        r.ndictvecs = (uint32_t)dvecs.size();
-        r.list_built = true;
-        chunks.resize(k);
-        r.h_chunks.swap(chunks);
-        r.mask = mask;
-        r.bytes = bc;
-    }
-    if (r.ev_used + 2 > r.ev_pool.size()) {
-        for (int i = 0; i < 2; ++i) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            r.ev_pool.push_back(e);
-        }
-    }
-    // queue counters and the side stream exist before the timed region
-    HIP_TRY(r.queue.alloc(r.dev, kQueueWords));
-    if (!r.side.stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&r.side.stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&r.side.fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&r.side.join, hipEventDisableTiming));
-    }
-    if (r.fsst.total_vecs() > 0)
-        if (const int rc = fsst_config_check(r.lpolicy)) return rc;
-    hipEvent_t e0 = r.ev_pool[r.ev_used], e1 = r.ev_pool[r.ev_used + 1];
-    r.ev_used += 2;
-    HIP_TRY(hipEventRecord(e0, r.stream));
-    HIP_TRY(launch_all(r.d_chunks.p, r.nmain, (uint32_t)r.h_chunks.size(), r.fsst, r.err.p, r.bytes.geom, r.stream,
-                       r.queue.p, r.lpolicy, r.split, &r.side, r.d_dictvecs.p, r.ndictvecs));
-    HIP_TRY(hipEventRecord(e1, r.stream));
-    return 0;
-}
-
-uint64_t resident_rows(const fls_table *t) {
-    uint64_t n = 0;
-    for (auto &r : t->resident) n += r->rows;
-    return n;
-}
-
-const Resident *part_of(const fls_table *t, uint32_t part) {
-    return t && part < t->resident.size() ? t->resident[part].get() : nullptr;
-}
-
-}  // namespace
-
-extern "C" {
-
-int fls_device_upload(fls_table *t, uint32_t rg_begin, uint32_t rg_end) {
-    if (!t) return fail(FLS_ERR_ARG, "fls_device_upload: NULL table");
-    if (rg_end > t->meta.rgs.size() || rg_begin >= rg_end)
-        return fail(FLS_ERR_ARG, "row-group range [%u,%u) out of bounds", rg_begin, rg_end);
-    // contiguous shards over the connection's GPUs, as a scan splits them
-    const uint32_t G = (uint32_t)t->devices.size(), n = rg_end - rg_begin;
-    t->resident.clear();
-    t->launches = 0;
-    for (uint32_t g = 0; g < G; ++g) {
-        const uint32_t a = rg_begin + (uint32_t)((uint64_t)n * g / G), b = rg_begin + (uint32_t)((uint64_t)n * (g + 1) / G);
-        if (a == b) continue;
-        auto r = std::make_unique<Resident>();
-        r->dev = t->devices[g];
-        r->rg0 = a;
-        r->rg1 = b;
-        int rc = upload_part(t, *r);
-        t->resident.push_back(std::move(r));
-        if (rc) {
-            t->resident.clear();
-            return rc;
-        }
-    }
-    return 0;
-}
-
-int fls_device_decode(fls_table *t, const uint8_t *col_mask) {
-    if (!t) return fail(FLS_ERR_ARG, "fls_device_decode: NULL table");
-    if (t->resident.empty()) return fail(FLS_ERR_STATE, "fls_device_decode before fls_device_upload");
-    const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    std::vector<uint8_t> mask(ncols, 1);
-    if (col_mask)
-        for (uint32_t c = 0; c < ncols; ++c) mask[c] = col_mask[c] ? 1 : 0;
-    for (auto &r : t->resident) {  // every GPU's launch is queued before any waits
-        int rc = decode_part(t, *r, mask);
-        if (rc) return rc;
-    }
-    t->launches++;
-    return 0;
-}
-
-int fls_device_sync(fls_table *t, fls_decode_stats *stats) {
-    if (!t) return fail(FLS_ERR_ARG, "fls_device_sync: NULL table");
-    if (t->resident.empty()) return fail(FLS_ERR_STATE, "nothing uploaded");
-    uint32_t err = 0;
-    for (auto &r : t->resident) {
-        HIP_TRY(hipSetDevice(r->dev));
-        HIP_TRY(hipStreamSynchronize(r->stream));
-        uint32_t e = 0;
-        HIP_TRY(hipMemcpy(&e, r->err.p, sizeof(e), hipMemcpyDeviceToHost));
-        err |= e;
-    }
-    if (stats) {
-        // per launch the slowest GPU's time (the parts run concurrently)
-        memset(stats, 0, sizeof(*stats));
-        const uint32_t nl = t->resident[0]->ev_used / 2;
-        double total = 0, last = 0;
-        for (uint32_t i = 0; i < nl; ++i) {
-            double span = 0;
-            for (auto &r : t->resident) {
-                if (2 * i + 1 >= r->ev_used) continue;
-                float ms = 0;
-                HIP_TRY(hipSetDevice(r->dev));
-                HIP_TRY(hipEventElapsedTime(&ms, r->ev_pool[2 * i], r->ev_pool[2 * i + 1]));
-                span = std::max(span, (double)ms);
-            }
-            total += span;
-            last = span;
-        }
-        stats->kernel_ms = last;
-        stats->kernel_ms_total = total;
-        stats->timed_launches = nl;
-        for (auto &r : t->resident) {
-            stats->values += r->bytes.values;
-            stats->packed_bytes += r->bytes.packed;
-            stats->meta_bytes += r->bytes.meta;
-            stats->out_bytes += r->bytes.out;
-        }
-        stats->launches = t->launches;
-    }
-    for (auto &r : t->resident) r->ev_used = 0;
-    if (err & KERR_LDS_BASE) return fail(FLS_ERR_DEVICE, "FSST kernel: dynamic LDS not at address 0 (flags 0x%x)", err);
-    if (err) return fail(FLS_ERR_FORMAT, "corrupt chunk detected while decoding (flags 0x%x)", err);
-    return 0;
-}
-
-int fls_device_parts(const fls_table *t) { return t ? (int)t->resident.size() : 0; }
-
-int fls_device_part(const fls_table *t, uint32_t part, fls_device_part_info *out) {
-    const Resident *r = part_of(t, part);
-    if (!r || !out) return fail(FLS_ERR_ARG, "resident part %u out of range", part);
-    out->device = r->dev;
-    out->rg_begin = r->rg0;
-    out->rg_end = r->rg1;
-    out->first_row = r->first_row;
-    out->nrows = r->rows;
-    return 0;
-}
-
-int fls_device_part_column(fls_table *t, uint32_t part, uint32_t col, void **dev_ptr, uint64_t *nbytes) {
-    const Resident *r = part_of(t, part);
-    if (!r || col >= r->d_out.size() || !r->d_out[col].p)
-        return fail(FLS_ERR_ARG, "column %u of part %u not resident", col, part);
-    if (dev_ptr) *dev_ptr = r->d_out[col].p;
-    if (nbytes) *nbytes = r->rows * out_bytes_of(t, col);
-    return 0;
-}
-
-int fls_device_part_heap(fls_table *t, uint32_t part, uint32_t col, void **dev_ptr, const void **host_ptr,
-                         uint64_t *nbytes) {
-    const Resident *r = part_of(t, part);
-    if (!r || col >= r->d_out.size() || !r->d_out[col].p)
-        return fail(FLS_ERR_ARG, "column %u of part %u not resident", col, part);
-    const bool has = col < r->d_heap.size() && r->d_heap[col].p;
-    if (dev_ptr) *dev_ptr = has ? r->d_heap[col].p : nullptr;
-    if (host_ptr) *host_ptr = has ? r->h_heap[col].p : nullptr;
-    if (nbytes) *nbytes = has ? r->d_heap[col].n : 0;
-    return has ? 1 : 0;
-}
-
-// single-GPU accessors: the table's only part (a table split over several
-// GPUs is addressed per part)
-int fls_device_column(fls_table *t, uint32_t col, void **dev_ptr, uint64_t *nbytes) {
-    if (t && t->resident.size() > 1)
-        return fail(FLS_ERR_STATE, "table is resident on %zu GPUs: use fls_device_part_column", t->resident.size());
-    return fls_device_part_column(t, 0, col, dev_ptr, nbytes);
-}
-
-int fls_device_heap(fls_table *t, uint32_t col, void **dev_ptr, const void **host_ptr, uint64_t *nbytes) {
-    if (t && t->resident.size() > 1)
-        return fail(FLS_ERR_STATE, "table is resident on %zu GPUs: use fls_device_part_heap", t->resident.size());
-    return fls_device_part_heap(t, 0, col, dev_ptr, host_ptr, nbytes);
-}
-
-int fls_device_copy_out(fls_table *t, uint32_t col, uint64_t row, uint64_t n, void *host_dst) {
-    if (!t || t->resident.empty() || col >= t->meta.cols.size() || !host_dst)
-        return fail(FLS_ERR_ARG, "column %u not resident", col);
-    const uint64_t total = resident_rows(t);
-    if (row > total || n > total - row) return fail(FLS_ERR_ARG, "rows out of range");
-    const int ob = out_bytes_of(t, col);
-    uint64_t at = 0;  // first resident row of the part, counted over the parts
-    for (auto &rp : t->resident) {
-        Resident &r = *rp;
-        const uint64_t a = std::max(row, at), b = std::min(row + n, at + r.rows);
-        if (a < b) {
-            HIP_TRY(hipSetDevice(r.dev));
-            HIP_TRY(hipStreamSynchronize(r.stream));
-            HIP_TRY(hipMemcpy((uint8_t *)host_dst + (a - row) * ob, r.d_out[col].p + (a - at) * ob, (b - a) * ob,
-                              hipMemcpyDeviceToHost));
-            // FSST: string_t pointers target the host copy of the part's heap
-            if (col < r.d_heap.size() && r.d_heap[col].p)
-                HIP_TRY(hipMemcpy(r.h_heap[col].p, r.d_heap[col].p, r.d_heap[col].n, hipMemcpyDeviceToHost));
-        }
-        at += r.rows;
-    }
-    return 0;
-}
-
-uint64_t fls_device_rows(const fls_table *t) { return t ? resident_rows(t) : 0; }
 
 }  // extern "C"

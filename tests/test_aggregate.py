@@ -437,6 +437,11 @@ def test_gpu_results_are_bit_identical_across_batches_and_gpus(fl, gpu, widths, 
     for batch in ("1", "3"):
         monkeypatch.setenv("FLS_SCAN_BATCH", batch)
         assert run(tf, tw) == base, batch
+    monkeypatch.setenv("FLS_SCAN_BATCH", "1")
+    monkeypatch.setenv("FLS_SCAN_SLOTS", "4")       # four batches in flight, the last two on recycled host batches
+    assert run(tf, tw) == base, "batch 1, four slots"
+    monkeypatch.delenv("FLS_SCAN_SLOTS")
+    monkeypatch.setenv("FLS_SCAN_BATCH", "3")
     # the row groups sharded over two pipelines (the same GPU listed twice)
     conn2 = fl.Connection([0, 0])
     tf2, tw2 = conn2.read_image(fimg), conn2.read_image(wimg)
@@ -448,6 +453,51 @@ def test_gpu_results_are_bit_identical_across_batches_and_gpus(fl, gpu, widths, 
         tf2.close()
         tw2.close()
         conn2.close()
+
+
+@pytest.mark.gpu
+def test_gpu_failed_refill_ends_every_reducing_scan_with_its_error(gpu):
+    """The three reducing scans (aggregate, grouped aggregate, top-N) share one
+    driver: a batch refill that cannot be enqueued (FLS_TEST_FAIL_ENQUEUE, as
+    in tests/test_scan_errors.py) must come back from each as that error, and
+    the next call on the table must start clean.  In a child process: the hook
+    counts the enqueues made while it is set, over the whole process."""
+    import os
+    import subprocess
+    code = """
+import os
+import numpy as np
+import pkgload
+fl = pkgload.load()
+RG = 1024
+v = np.arange(3 * RG, dtype=np.int32)
+img = fl.write_image([("v", fl.INT32, v, fl.ENC_FFOR), ("g", fl.INT32, v % 3, fl.ENC_FFOR)], rowgroup=RG)
+t = fl.Connection([0]).read_image(img)
+assert t.nrowgroups == 3                      # three batches of one row group on two slots
+calls = {"aggregate": lambda: t.aggregate([("sum", 0), ("count",)]),
+         "grouped": lambda: t.aggregate_grouped([1], [("sum", 0)]),
+         # (under a filter that keeps every row: without one the key's zone maps leave one row group to read)
+         "topn": lambda: t.topn(0, 5, desc=True, filt=[(0, ">=", 0)])[0].tolist()}
+want = {name: f() for name, f in calls.items()}
+assert want["aggregate"] == [int(v.sum()), len(v)] and want["topn"] == [len(v) - 1 - i for i in range(5)], want
+# a failing call makes three enqueues: two when the scan starts, then the
+# refill at the first row group's hand-out, which is the one that fails
+for i, (name, f) in enumerate(calls.items()):
+    os.environ["FLS_TEST_FAIL_ENQUEUE"] = str(3 * (i + 1))
+    try:
+        f()
+        print(name, "no error")
+    except fl.FlsError as e:
+        print(name, e.msg)
+    del os.environ["FLS_TEST_FAIL_ENQUEUE"]
+    assert f() == want[name], name
+"""
+    out = subprocess.run([sys.executable, "-c", code], env={**os.environ, "FLS_SCAN_BATCH": "1"},
+                         capture_output=True, text=True, timeout=120, cwd=str(ROOT))
+    assert out.returncode == 0, out.stderr
+    lines = out.stdout.splitlines()
+    assert [ln.split()[0] for ln in lines] == ["aggregate", "grouped", "topn"], out.stdout
+    assert all("injected batch enqueue failure" in ln for ln in lines), out.stdout
 
 
 # ---- lineitem

@@ -565,6 +565,10 @@ def test_gpu_results_are_bit_identical_across_batches_and_pipelines(fl, gpu, flo
     for batch in ("1", "3", "8"):
         monkeypatch.setenv("FLS_SCAN_BATCH", batch)
         assert run(tf, tm) == base, batch
+    monkeypatch.setenv("FLS_SCAN_BATCH", "1")
+    monkeypatch.setenv("FLS_SCAN_SLOTS", "4")       # four batches in flight, the last two on recycled host batches
+    assert run(tf, tm) == base, "batch 1, four slots"
+    monkeypatch.delenv("FLS_SCAN_SLOTS")
     # the row groups sharded over two pipelines (the same GPU listed twice)
     monkeypatch.setenv("FLS_SCAN_BATCH", "3")
     conn2 = fl.Connection([0, 0])

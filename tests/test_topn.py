@@ -509,6 +509,9 @@ def test_gpu_results_are_identical_across_batches_and_pipelines(fl, gpu, conn0, 
     for batch in ("1", "3"):
         monkeypatch.setenv("FLS_SCAN_BATCH", batch)
         assert run(t) == base, batch
+    monkeypatch.setenv("FLS_SCAN_SLOTS", "4")       # four batches in flight, the last two on recycled host batches
+    assert run(t) == base, "batch 3, four slots"
+    monkeypatch.delenv("FLS_SCAN_SLOTS")
     conn2 = fl.Connection([0, 0])       # the row groups sharded over two pipelines
     t2 = conn2.read_image(img)
     try:
