@@ -85,6 +85,24 @@ class KeySetInfo(C.Structure):     # fls_keyset_info_t
                 ("max", C.c_uint64), ("empty", C.c_uint64)]
 
 
+# fls_keymap_form, FLS_KEY_MAPPED, FLS_KEYMAP_KEEP_UNMATCHED
+KEYMAP_AUTO, KEYMAP_DENSE, KEYMAP_HASH = 0, 1, 2
+KEYMAP_ABSENT = 0xFFFF             # kKeymapAbsent: no code
+KEYMAP_MAX_SPAN = 1 << 31          # kKeymapMaxSpan
+KEY_MAPPED = 0x80000000
+KEYMAP_KEEP_UNMATCHED = 1
+
+
+class KeyMapInfo(C.Structure):     # fls_keymap_info_t
+    _fields_ = [("count", C.c_uint64), ("form", C.c_uint32), ("kind", C.c_uint32), ("device_bytes", C.c_uint64),
+                ("capacity", C.c_uint64), ("max_probe", C.c_uint32), ("max_code", C.c_uint32), ("min", C.c_uint64),
+                ("max", C.c_uint64), ("empty", C.c_uint64)]
+
+
+class KeyBinding(C.Structure):     # fls_key_binding
+    _fields_ = [("col", C.c_uint32), ("flags", C.c_uint32), ("map", C.c_uint64)]
+
+
 # fls_agg_fn / fls_aggregate_spec / fls_aggregate_value (include/flsgpu.h)
 AGG_FNS = {"count_star": 0, "count": 1, "sum": 2, "min": 3, "max": 4, "sum_product": 5, "sum_expr": 6}
 AGGV_NULL, AGGV_INT, AGGV_DOUBLE = 0, 1, 2
@@ -180,6 +198,11 @@ _sig("fls_keyset_create", C.c_int, _P, _P, C.c_uint64, C.c_int, C.c_int, C.POINT
 _sig("fls_keyset_free", None, _P)
 _sig("fls_keyset_info", C.c_int, _P, C.POINTER(KeySetInfo))
 _sig("fls_keyset_contains", C.c_int, _P, C.c_uint64)
+_sig("fls_keymap_create", C.c_int, _P, _P, _P, C.c_uint64, C.c_int, C.c_int, C.POINTER(_P))
+_sig("fls_keymap_free", None, _P)
+_sig("fls_keymap_info", C.c_int, _P, C.POINTER(KeyMapInfo))
+_sig("fls_keymap_lookup", C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint32))
+_sig("fls_aggregate_key_bindings", C.c_int, _P, C.POINTER(KeyBinding), C.c_uint32)
 _sig("fls_aggregate", C.c_int, _P, C.POINTER(AggregateSpec), C.c_uint32, C.c_uint32, C.c_uint32,
      C.POINTER(AggregateValue))
 _sig("fls_aggregate_exprs", C.c_int, _P, C.POINTER(AggExpr), C.c_uint32)
@@ -560,32 +583,88 @@ class Connection:
         UINT* and BOOLEAN columns), form 0 auto / 1 bitmap / 2 hash table.
         Built on the host; no GPU is needed.  TypeError for anything but
         integers (a float is never truncated into a key)."""
-        # (a list goes value by value: numpy would turn Python integers of mixed sign past 2^63 into floats)
-        a = values if isinstance(values, np.ndarray) else np.asarray(list(values), dtype=object)
-        if a.size == 0:
-            a = np.zeros(0, np.uint64)
-        elif a.dtype == object:
-            vals = list(a.ravel())
-            for v in vals:
-                if not isinstance(v, (int, np.integer, np.bool_)):
-                    raise TypeError(f"keyset: {v!r} is not an integer")
-            a = np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in vals], dtype=np.uint64)
-        elif a.dtype.kind not in "iub":
-            raise TypeError(f"keyset: values of dtype {a.dtype} are not integers")
-        elif a.dtype.kind == "i":
-            a = a.astype(np.int64).view(np.uint64)    # sign-extended patterns
-        else:
-            a = a.astype(np.uint64)
-        a = np.ascontiguousarray(a.ravel())
+        a = _key_patterns(values, "keyset")
         h = _P()
         _check(_lib.fls_keyset_create(self.h, a.ctypes.data if a.size else None, a.size, 0 if signed else 1, form,
                                       C.byref(h)))
         return KeySet(h.value, self)
 
+    def keymap(self, keys, values, signed: bool = True, form: int = KEYMAP_AUTO) -> "KeyMap":
+        """A key map for ("map", col, keymap) GROUP BY keys (fls_keymap_create):
+        keys as keyset() takes them, values their codes, integers in
+        [0, 65534]; a key listed with two codes is refused.  form 0 auto /
+        1 dense / 2 hash table.  Built on the host; no GPU is needed."""
+        k = _key_patterns(keys, "keymap")
+        v = _key_patterns(values, "keymap")
+        if v.size != k.size:
+            raise ValueError(f"keymap: {k.size} keys and {v.size} values")
+        if v.size and int(v.max()) > KEYMAP_ABSENT:     # (a negative value is a pattern past 2^63)
+            bad = int(v.max())
+            raise ValueError(f"keymap: value {bad - (1 << 64) if bad >> 63 else bad} is outside [0, 65534]")
+        v = np.ascontiguousarray(v.astype(np.uint16))   # (65535 itself is the library's to refuse)
+        h = _P()
+        _check(_lib.fls_keymap_create(self.h, k.ctypes.data if k.size else None, v.ctypes.data if v.size else None,
+                                      k.size, 0 if signed else 1, form, C.byref(h)))
+        return KeyMap(h.value, self)
+
     def close(self):
         if self.h:
             _lib.fls_disconnect(self.h)
             self.h = None
+
+
+def _key_patterns(values, who: str) -> np.ndarray:
+    """integers as the 64-bit patterns a key set or key map holds (uint64,
+    contiguous); TypeError for anything but integers"""
+    # (a list goes value by value: numpy would turn Python integers of mixed sign past 2^63 into floats)
+    a = values if isinstance(values, np.ndarray) else np.asarray(list(values), dtype=object)
+    if a.size == 0:
+        a = np.zeros(0, np.uint64)
+    elif a.dtype == object:
+        vals = list(a.ravel())
+        for v in vals:
+            if not isinstance(v, (int, np.integer, np.bool_)):
+                raise TypeError(f"{who}: {v!r} is not an integer")
+        a = np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in vals], dtype=np.uint64)
+    elif a.dtype.kind not in "iub":
+        raise TypeError(f"{who}: values of dtype {a.dtype} are not integers")
+    elif a.dtype.kind == "i":
+        a = a.astype(np.int64).view(np.uint64)    # sign-extended patterns
+    else:
+        a = a.astype(np.uint64)
+    return np.ascontiguousarray(a.ravel())
+
+
+class KeyMap:
+    """fls_keymap: the build side of a join whose payload is a GROUP BY code.
+    The handle is a token the library looks up; a closed map in a binding is
+    refused, never dereferenced."""
+
+    def __init__(self, h, conn):
+        self.h, self.conn = h, conn
+
+    @property
+    def info(self) -> KeyMapInfo:
+        out = KeyMapInfo()
+        _check(_lib.fls_keymap_info(self.h, C.byref(out)))
+        return out
+
+    def lookup(self, key: int):
+        """Host probe of the image a scan uploads: the code, or None."""
+        code = C.c_uint32()
+        found = _check(_lib.fls_keymap_lookup(self.h, int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(code)))
+        return code.value if found == 1 else None
+
+    def close(self):
+        if self.h:
+            _lib.fls_keymap_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class KeySet:
@@ -913,6 +992,42 @@ class Table:
         signed = ci.type in (INT8, INT16, INT32, INT64, DATE, DECIMAL)
         return self.conn.keyset(np.unique(vals), signed=signed, form=form)
 
+    def keymap(self, key_col: int, value_col: int, filt=None, form: int = KEYMAP_AUTO) -> "KeyMap":
+        """The build side of a join: the key map key_col -> value_col of two
+        integer-like columns of this (dimension) table over the rows filt
+        selects; rows with a NULL in either column are left out.  A value
+        outside [0, 65534] raises ValueError.  Use it as ("map", col, keymap)
+        in aggregate_grouped on this or another table of the same connection."""
+        cis = [self.column(c) for c in (key_col, value_col)]
+        for c, ci in zip((key_col, value_col), cis):
+            if ci.type in STRING_TYPES or ci.type in (FLOAT, DOUBLE) or ci.out_bytes > 8:
+                raise ValueError(f"keymap: column {c} ({TYPE_NAMES.get(ci.type, ci.type)}) is not integer-like")
+        terms = list(filt or []) + [(key_col, "is_not_null", None), (value_col, "is_not_null", None)]
+        ks, vs = [], []
+        for _, _, _, arrs in self.scan_filtered(terms, cols=sorted({key_col, value_col})):
+            ks.append(arrs[key_col].view(NP_DTYPE[cis[0].type]))
+            vs.append(arrs[value_col].view(NP_DTYPE[cis[1].type]))
+        keys = np.concatenate(ks) if ks else np.zeros(0, NP_DTYPE[cis[0].type])
+        vals = np.concatenate(vs) if vs else np.zeros(0, NP_DTYPE[cis[1].type])
+        if vals.size and (int(vals.min()) < 0 or int(vals.max()) >= KEYMAP_ABSENT):
+            bad = int(vals.min()) if int(vals.min()) < 0 else int(vals.max())
+            raise ValueError(f"keymap: value {bad} of column {value_col} is outside [0, 65534]")
+        signed = cis[0].type in (INT8, INT16, INT32, INT64, DATE, DECIMAL)
+        return self.conn.keymap(keys, vals.astype(np.uint16), signed=signed, form=form)
+
+    def set_key_bindings(self, bindings):
+        """fls_aggregate_key_bindings: what a key KEY_MAPPED | i names in the
+        following aggregate_grouped calls; each binding (col, keymap) or
+        (col, keymap, flags), keymap a KeyMap or a raw handle.  [] or None
+        clears."""
+        bindings = bindings or []
+        arr = (KeyBinding * max(1, len(bindings)))()
+        for i, b in enumerate(bindings[:len(arr)]):
+            arr[i].col = b[0]
+            arr[i].map = (b[1].h or 0) if isinstance(b[1], KeyMap) else int(b[1])
+            arr[i].flags = b[2] if len(b) > 2 else 0
+        _check(_lib.fls_aggregate_key_bindings(self.h, arr if bindings else None, len(bindings)))
+
     # -- aggregates reduced on the GPU
     def set_aggregate_exprs(self, exprs):
         """fls_aggregate_exprs: the expression list function code 6 (sum_expr)
@@ -957,28 +1072,48 @@ class Table:
         return [_agg_value(v) for v in vals]
 
     def aggregate_grouped(self, keys, aggs, filt=None, rg_begin=0, rg_end=None) -> list:
-        """GROUP BY keys (1 to 4 column indices of low cardinality) of the
-        aggregates aggregate() takes, evaluated on the GPU
-        (fls_aggregate_grouped).  Returns [(key_tuple, values)] in order of
-        each group's first row; a key element is an int, bytes (a VARCHAR key)
-        or None (NULL, a group of its own), values as aggregate() returns
-        them.  FlsError with code ERR_LIMIT past 64 distinct keys in a
-        1024-row vector or 256 in a row group."""
+        """GROUP BY keys (1 to 4 of low cardinality) of the aggregates
+        aggregate() takes, evaluated on the GPU (fls_aggregate_grouped).  A
+        key is a column index, or ("map", col, keymap) /
+        ("map", col, keymap, "keep_unmatched"): the code keymap gives column
+        col -- an inner join by default (rows whose value is NULL or not in
+        the map belong to no group), a left join with "keep_unmatched" (they
+        form the NULL group).  An int with KEY_MAPPED set is passed through
+        and names a binding set by set_key_bindings.  Returns
+        [(key_tuple, values)] in order of each group's first row; a key
+        element is an int (a mapped key: its code), bytes (a VARCHAR key) or
+        None (NULL, a group of its own), values as aggregate() returns them.
+        FlsError with code ERR_LIMIT past 64 distinct keys in a 1024-row
+        vector or 256 in a row group."""
         if rg_end is None:
             rg_end = self.nrowgroups
-        karr = (C.c_uint32 * max(1, len(keys)))(*keys[:max(1, len(keys))])
+        raw, binds = [], []
+        for k in keys:
+            if isinstance(k, (tuple, list)):
+                if len(k) not in (3, 4) or k[0] != "map" or (len(k) == 4 and k[3] != "keep_unmatched"):
+                    raise ValueError(f"aggregate_grouped: key {k!r} is not a column or "
+                                     '("map", col, keymap[, "keep_unmatched"])')
+                raw.append(KEY_MAPPED | len(binds))
+                binds.append((k[1], k[2], KEYMAP_KEEP_UNMATCHED if len(k) == 4 else 0))
+            else:
+                raw.append(k)
+        karr = (C.c_uint32 * max(1, len(raw)))(*raw[:max(1, len(raw))])
         arr, exprs = _agg_specs(aggs)
         res = _P()
         self.set_filter(filt)
         try:
             if exprs:
                 self.set_aggregate_exprs(exprs)
+            if binds:
+                self.set_key_bindings(binds)
             _check(_lib.fls_aggregate_grouped(self.h, karr, len(keys), arr, len(aggs), rg_begin, rg_end,
                                               C.byref(res)))
         finally:
             _check(_lib.fls_scan_filter(self.h, None, 0))
             if exprs:
                 self.set_aggregate_exprs(None)
+            if binds:
+                self.set_key_bindings(None)
         try:
             out = []
             k = GroupKey()

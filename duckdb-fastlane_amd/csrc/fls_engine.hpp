@@ -8,11 +8,14 @@
 //   fls_scan_topn.hip     fls_topn: checks, per-batch enqueue, the host merge
 //                         and the late materialisation
 //   fls_scan_keyset.hip   the key-set registry and fls_keyset_*
+//   fls_scan_keymap.hip   the key-map registry, fls_keymap_*, the bindings of
+//                         mapped GROUP BY keys and their per-batch probe
 //   fls_device_table.hip  the device-resident table (fls_device_*)
 //
 // The pushdown and device-table units depend on flsgpu.hip's scan pipeline and
 // launch helpers; flsgpu.hip depends on them only through the three enqueue_*
-// functions fill_batch switches over and keyset_registry().  Every function
+// functions fill_batch switches over, keyset_registry() and, for mapped GROUP
+// BY keys, enqueue_keymap, binding_may_match and keymap_registry().  Every function
 // and registry declared here is defined in exactly one unit.
 //
 // All of it lives in fls::engine, which is hidden: nothing here reaches
@@ -44,6 +47,7 @@
 #include "fls_filter.hpp"
 #include "fls_format.hpp"
 #include "fls_groupagg.hpp"
+#include "fls_keymap.hpp"
 #include "fls_keyset.hpp"
 #include "fls_pinned.hpp"
 #include "fls_reader.hpp"
@@ -339,6 +343,11 @@ struct Slot {                       // one batch of row groups in flight
     DevBuf<uint8_t> d_gdesc;
     DevBuf<uint8_t> d_gvec;         // stage 1: the vectors' groups
     DevBuf<uint8_t> d_grg;          // stage 2: the row groups' groups
+    // mapped keys of a grouped aggregate batch (fls_aggregate_key_bindings)
+    PinBuf<DevMapTerm> h_mdesc;
+    DevBuf<DevMapTerm> d_mdesc;
+    DevBuf<uint16_t> d_kcode;       // per binding 1024 codes per vector: the derived key columns
+    DevBuf<uint64_t> d_kvalid;      // per binding 16 words per vector: a keep-unmatched key's validity
     // top-N batches (fls_topn)
     PinBuf<uint32_t> h_tdesc;       // per row group its first vector and vector count
     DevBuf<uint32_t> d_tdesc;
@@ -438,6 +447,57 @@ struct KeySetRegistry {
 };
 KeySetRegistry &keyset_registry();  // (fls_scan_keyset.hip)
 
+// A key map (fls_keymap_create): the host image and its copies in HBM, held
+// and uploaded as a key set's are.  Bindings and running scans hold a
+// reference; the copies are outside FLS_SCAN_RESIDENT_MB.
+struct KeyMap {
+    KeymapImage img;
+    const fls_connection *conn = nullptr;
+    std::mutex mu;
+    std::vector<std::unique_ptr<DevBuf<uint64_t>>> copies;
+    // the image on GPU dev (the current device), uploaded on first use
+    hipError_t device_image(int dev, const uint64_t **out) {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto &c : copies)
+            if (c->dev == dev) {
+                *out = c->p;
+                return hipSuccess;
+            }
+        auto b = std::make_unique<DevBuf<uint64_t>>();
+        hipError_t e = b->alloc(dev, img.words.size());
+        // a synchronous copy: complete before any kernel enqueued after this call
+        if (e == hipSuccess && !img.words.empty())
+            e = hipMemcpy(b->p, img.words.data(), img.bytes(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return e;
+        *out = b->p;
+        copies.push_back(std::move(b));
+        return hipSuccess;
+    }
+};
+
+// Live key maps by handle: counter tokens like the key sets', with tag bits of
+// their own, so a key-set handle never resolves as a map (nor a map as a set).
+struct KeyMapRegistry {
+    std::mutex mu;
+    uint64_t next = 1;
+    std::unordered_map<uint64_t, std::shared_ptr<KeyMap>> live;
+    static uint64_t handle_of(uint64_t id) { return (id << 4) | 0xA; }
+    std::shared_ptr<KeyMap> find(uint64_t handle) {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = live.find(handle);
+        return it == live.end() ? nullptr : it->second;
+    }
+};
+KeyMapRegistry &keymap_registry();  // (fls_scan_keymap.hip)
+
+// One mapped GROUP BY key (fls_aggregate_key_bindings), host side: the code
+// the map gives column col.
+struct HostBinding {
+    uint32_t col = 0;
+    bool keep = false;              // FLS_KEYMAP_KEEP_UNMATCHED
+    std::shared_ptr<KeyMap> map;
+};
+
 // One term of a pushed-down filter (fls_scan_filter), host side.
 struct HostTerm {
     uint32_t col = 0, clause = 0;
@@ -480,7 +540,10 @@ struct ScanPlan {
     // and the scans the engine runs for itself deliver at full width
     bool delivering_scan = false;
     const std::vector<HostAgg> *aggs = nullptr;     // Reduce::Aggregate / GroupAggregate
-    const std::vector<uint32_t> *keys = nullptr;    // Reduce::GroupAggregate: the GROUP BY columns
+    // Reduce::GroupAggregate: the GROUP BY keys, a column each or
+    // FLS_KEY_MAPPED | i for binding i of binds
+    const std::vector<uint32_t> *keys = nullptr;
+    const std::vector<HostBinding> *binds = nullptr;  // the mapped keys' bindings (NULL: none)
     const fls_order_key *order = nullptr;           // Reduce::TopN: the key and
     uint32_t k = 0;                                 // ... how many rows
     // exactly these row groups (ascending, inside the range) instead of
@@ -500,6 +563,10 @@ struct ScanCtx {
     // GROUP BY columns of a grouped aggregate scan (Reduce::GroupAggregate):
     // decoded like operands, VARCHAR keys as dictionary codes
     std::vector<uint32_t> keys;
+    // ... where FLS_KEY_MAPPED | i stands for the code binding i gives its
+    // column (keymap_kernel).  With a binding the scan always has a mask.
+    std::vector<HostBinding> binds;
+    bool masked() const { return !terms.empty() || !binds.empty(); }
     // top-N scan (Reduce::TopN): no column is delivered, each batch's
     // candidate lists ride in its HostBatch
     fls_order_key tkey = {};
@@ -646,6 +713,7 @@ struct fls_table {
     fls::engine::ScanCtx scan, mat;
     std::vector<fls::engine::HostTerm> filter;  // fls_scan_filter: applies to the next fls_scan_begin / fls_aggregate
     std::vector<fls_agg_expr> exprs;  // fls_aggregate_exprs: what FLS_AGG_SUM_EXPR's spec.col indexes
+    std::vector<fls::engine::HostBinding> bindings;  // fls_aggregate_key_bindings: what FLS_KEY_MAPPED | i names
     bool dict_codes = false;        // fls_scan_dict_codes: applies to the next fls_scan_begin
     bool narrow = false;            // fls_scan_narrow: applies to the next fls_scan_begin
     bool defer_records = false;     // fls_scan_defer_records: applies to the next fls_scan_begin
@@ -705,6 +773,14 @@ int rg_vec_table(const fls_table *t, const Slot &sl, uint32_t *tab, uint32_t &rg
 int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);        // fls_scan_agg.hip
 int enqueue_group_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);  // fls_scan_agg.hip
 int enqueue_topn(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);             // fls_scan_topn.hip
+
+// ---- mapped GROUP BY keys (fls_scan_keymap.hip) ---------------------------------
+
+// May a row of row group rg carry a key of inner binding b?  (as IN_SET prunes)
+bool binding_may_match(const fls_table *t, uint32_t rg, const HostBinding &b);
+// The batch's probe of the scan's bindings, after the filter's kernels on the
+// slot's mask: the derived key columns into sl.d_kcode / sl.d_kvalid.
+int enqueue_keymap(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows);
 
 // A reducing scan on the table's scan context under its filter: nothing is
 // delivered; fold(rg, hb) sees every surviving row group once, in scan order,

@@ -66,6 +66,34 @@ constexpr size_t group_rg_stride(uint32_t naggs, uint32_t nfsum, uint32_t rg_vec
     return group_rg_fvec_off(naggs) + 8ull * kMaxRgGroups * nfsum * rg_vecs;
 }
 
+// One mapped key (fls_aggregate_key_bindings) as keymap_kernel sees it,
+// rebuilt per scan batch; the map's image (fls_keymap.hpp) lives in HBM with
+// the map.  The kernel writes the code of every selected, valid row's value
+// into `code`, which stage 1 then reads as a 2-byte key column.
+struct DevMapTerm {           // 80 B
+    const uint8_t *col;       // decoded column of the batch in HBM (row 0 of the batch)
+    const uint64_t *valid;    // the column's validity words for the batch rows (HBM), or NULL
+    const uint64_t *table;    // dense: uint16 codes; hash: the slots, then their uint16 codes
+    uint16_t *code;           // the derived key column: one code per batch row (HBM)
+    uint64_t *kvalid;         // keep-unmatched: the derived key's validity words, 16 per vector
+    uint64_t min, span;       // dense: code (value - min) for value - min <= span
+    uint64_t empty;           // hash: the empty slot's sentinel
+    uint32_t cap_log2;        // hash: log2 of the capacity
+    uint32_t max_probe;       // hash: slots a lookup examines at most
+    uint8_t form;             // KM_DENSE / KM_HASH
+    uint8_t ob, sign;         // bytes per decoded value; values sign-extend to 64 bits
+    uint8_t keep;             // keep-unmatched (left join): the mask is left alone
+    uint8_t pad[4];
+};
+static_assert(sizeof(DevMapTerm) == 80, "DevMapTerm is 80 B");
+// a key-map descriptor no sound map produces (the probe loop itself is bounded)
+enum : uint32_t { KERR_KEYMAP = 1024 };
+// Probes the bindings' maps under the mask launch_filter / launch_keyset wrote
+// for the same nrows rows, narrows it by the inner bindings and recomputes the
+// counts (fls_keymap.hip).
+hipError_t launch_keymap(const DevMapTerm *d_terms, uint32_t nterms, uint32_t nrows, uint64_t *d_mask,
+                         uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
+
 // Stage 1.  d_aggs[a].fslot numbers the FLOAT / DOUBLE sums (stage 2 reads it).
 hipError_t launch_group_vectors(const DevKey *d_keys, uint32_t nkeys, const DevAgg *d_aggs, uint32_t naggs,
                                 uint32_t nrows, const uint64_t *d_mask, uint8_t *d_vec_out, uint32_t *d_err,

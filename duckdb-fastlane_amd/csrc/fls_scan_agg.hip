@@ -78,15 +78,21 @@ int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t r
 
 // Bit layout of the packed key of a grouped aggregate (fls_groupagg.hpp): key
 // q's value at shift[q] in bits[q] bits -- 8 x the decoded value's bytes, 16
-// for a VARCHAR key's dictionary code -- then one NULL bit per key.
+// for a VARCHAR key's dictionary code or a mapped key's code
+// (FLS_KEY_MAPPED | i) -- then one NULL bit per key.
 struct KeyLayout {
     uint32_t shift[kMaxKeys] = {}, bits[kMaxKeys] = {}, null_bit[kMaxKeys] = {};
     uint32_t total = 0;
 };
+// The type a key's value has on the host: the column's, or for a mapped key
+// the 16-bit code's.
+static uint8_t key_type(const fls_table *t, uint32_t key) {
+    return key & FLS_KEY_MAPPED ? (uint8_t)TY_UINT16 : t->meta.cols[key].type;
+}
 static KeyLayout key_layout(const fls_table *t, const std::vector<uint32_t> &keys) {
     KeyLayout L;
     for (size_t q = 0; q < keys.size() && q < kMaxKeys; ++q) {
-        const uint8_t ty = t->meta.cols[keys[q]].type;
+        const uint8_t ty = key_type(t, keys[q]);
         L.shift[q] = L.total;
         L.bits[q] = type_is_string(ty) ? 16 : (uint32_t)type_value_bits(ty);
         L.total += L.bits[q];
@@ -100,7 +106,7 @@ static KeyLayout key_layout(const fls_table *t, const std::vector<uint32_t> &key
 // group into sl.d_grg, and the row groups' tables are the batch's only D2H.
 int enqueue_group_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
     HostBatch &hb = *sl.hb;
-    const bool filtered = !s.terms.empty();
+    const bool filtered = s.masked();
     if (!filtered)  // (enqueue_filter staged the filter's, the operands' and the keys' validity together)
         if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
     const std::vector<uint8_t> &need = sl.valid_staged;
@@ -118,6 +124,17 @@ int enqueue_group_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint
     uint32_t *rgvec = (uint32_t *)(sl.h_gdesc.p + kMaxKeys * sizeof(DevKey));
     const KeyLayout L = key_layout(t, s.keys);
     for (uint32_t q = 0; q < nk; ++q) {
+        if (s.keys[q] & FLS_KEY_MAPPED) {
+            // the derived column keymap_kernel wrote for binding i of the scan:
+            // never NULL (inner), or valid where the map had the value (keep-unmatched)
+            const uint32_t i = s.keys[q] & ~FLS_KEY_MAPPED;
+            dk[q].col = (const uint8_t *)(sl.d_kcode.p + (size_t)i * 1024 * hb.nvec);
+            dk[q].valid = s.binds[i].keep ? sl.d_kvalid.p + (size_t)i * 16 * hb.nvec : nullptr;
+            dk[q].ob = 2;
+            dk[q].shift = (uint8_t)L.shift[q];
+            dk[q].null_bit = (uint8_t)L.null_bit[q];
+            continue;
+        }
         const uint32_t c = s.keys[q];
         // hb.ob: the decode's bytes per row (a VARCHAR key: its codes' width in this batch)
         if (hb.ob[c] * 8u > L.bits[q])
@@ -412,12 +429,26 @@ int fls_aggregate_grouped(fls_table *t, const uint32_t *keys, uint32_t nkeys, co
         return fail(FLS_ERR_ARG, "fls_aggregate_grouped: %u keys (1 to %u per call)", nkeys, kMaxKeys);
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
     if (int rc = check_rowgroup_range(t, rg_begin, rg_end, "")) return rc;
+    // hk[q]: the key's column, or FLS_KEY_MAPPED | its position in `binds`,
+    // the bindings this call's keys name
     std::vector<uint32_t> hk(keys, keys + nkeys);
+    std::vector<HostBinding> binds;
     for (uint32_t q = 0; q < nkeys; ++q) {
         const uint32_t c = hk[q];
+        if (c & FLS_KEY_MAPPED) {
+            const uint32_t i = c & ~FLS_KEY_MAPPED;
+            if (i >= t->bindings.size())
+                return fail(FLS_ERR_ARG, "key %u: no binding %u (%u set by fls_aggregate_key_bindings)", q, i,
+                            (uint32_t)t->bindings.size());
+            for (uint32_t p = 0; p < q; ++p)
+                if (keys[p] == c) return fail(FLS_ERR_ARG, "key %u: binding %u is key %u already", q, i, p);
+            hk[q] = FLS_KEY_MAPPED | (uint32_t)binds.size();
+            binds.push_back(t->bindings[i]);
+            continue;
+        }
         if (c >= ncols) return fail(FLS_ERR_ARG, "key %u: column %u out of range", q, c);
         for (uint32_t p = 0; p < q; ++p)
-            if (hk[p] == c) return fail(FLS_ERR_ARG, "key %u: column %u is key %u already", q, c, p);
+            if (keys[p] == c) return fail(FLS_ERR_ARG, "key %u: column %u is key %u already", q, c, p);
         const uint8_t ty = t->meta.cols[c].type;
         if (type_is_float(ty) || ty == TY_BLOB)
             return fail(FLS_ERR_ARG, "key %u: a FLOAT / DOUBLE / BLOB column (%u) cannot be a GROUP BY key", q, c);
@@ -443,7 +474,7 @@ int fls_aggregate_grouped(fls_table *t, const uint32_t *keys, uint32_t nkeys, co
         for (uint32_t q = 0, bits = nkeys; q < nkeys; ++q)
             if ((bits += L.bits[q]) > 128)
                 return fail(FLS_ERR_ARG, "key %u: the packed key needs %u bits (at most 128: 8 x value bytes per integer "
-                            "key, 16 per VARCHAR key, 1 per key for NULL)", q, L.total);
+                            "key, 16 per VARCHAR or mapped key, 1 per key for NULL)", q, L.total);
     std::vector<HostAgg> ha;
     if (int rc = check_aggregates(t, "fls_aggregate_grouped", aggs, n, rg_begin, rg_end, ha)) return rc;
     ScanPlan plan;
@@ -451,6 +482,7 @@ int fls_aggregate_grouped(fls_table *t, const uint32_t *keys, uint32_t nkeys, co
     plan.rg1 = rg_end;
     plan.aggs = &ha;
     plan.keys = &hk;
+    plan.binds = &binds;
     auto res = std::make_unique<fls_group_result>();
     res->nkeys = nkeys;
     res->naggs = n;
@@ -481,7 +513,7 @@ int fls_aggregate_grouped(fls_table *t, const uint32_t *keys, uint32_t nkeys, co
             for (uint32_t q = 0; q < nkeys; ++q) {
                 fls_group_result::Key &k = kv[q];
                 k = fls_group_result::Key();
-                const uint8_t ty = t->meta.cols[hk[q]].type;
+                const uint8_t ty = key_type(t, hk[q]);  // (a mapped key is an integer: its code)
                 if (!((pk >> L.null_bit[q]) & 1)) {
                     const uint64_t raw = (uint64_t)(pk >> L.shift[q]) & (L.bits[q] >= 64 ? ~0ull : (1ull << L.bits[q]) - 1);
                     if (ty == TY_VARCHAR) {

@@ -14,7 +14,8 @@
 // The rest of the engine is in units of its own, over the types and
 // declarations of fls_engine.hpp: what a scan does with a batch instead of
 // delivering it (ScanCtx::reduce) in fls_scan_agg.hip and fls_scan_topn.hip,
-// key sets in fls_scan_keyset.hip, and the device-resident mode (a shard of
+// key sets in fls_scan_keyset.hip, key maps and the mapped GROUP BY keys'
+// probe in fls_scan_keymap.hip, and the device-resident mode (a shard of
 // row groups uploaded verbatim to HBM and decoded by one fused launch per
 // pass: bench / roofline) in fls_device_table.hip.  What those units call here
 // is declared in fls_engine.hpp; every other function of this file is static.
@@ -1220,6 +1221,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
         if (h.op < OP_IS_NULL || is_set_op(h.op)) s.dmask[h.col] = 1;
     s.aggs.clear();
     s.keys.clear();
+    s.binds.clear();
     s.tk = 0;
     s.tkey = fls_order_key{};
     bool string_key = false;
@@ -1228,7 +1230,10 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     case Reduce::GroupAggregate:
         // the GROUP BY columns of a grouped aggregate scan are decoded too
         s.keys = *p.keys;
+        if (p.binds) s.binds = *p.binds;
+        for (const HostBinding &b : s.binds) s.dmask[b.col] = 1;  // a mapped key's column is decoded to be probed
         for (uint32_t c : s.keys) {
+            if (c & FLS_KEY_MAPPED) continue;
             s.dmask[c] = 1;
             string_key = string_key || type_is_string(t->meta.cols[c].type);
         }
@@ -1256,6 +1261,15 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     // row-group pruning on zone maps / dictionaries (a top-N scan without a
     // filter: by the k-th bound of the key's zone maps)
     s.pruned = select_rowgroups(t, s.terms, s.reduce == Reduce::TopN ? &s.tkey : nullptr, s.tk, rg0, rg1, s.rgs);
+    // an inner binding prunes as `col IN keys(map)` would
+    for (const HostBinding &b : s.binds) {
+        if (b.keep) continue;
+        std::vector<uint32_t> keep;
+        for (uint32_t r : s.rgs)
+            if (binding_may_match(t, r, b)) keep.push_back(r);
+        s.pruned += (uint32_t)(s.rgs.size() - keep.size());
+        s.rgs.swap(keep);
+    }
     if (p.only) {  // a scan of listed row groups: fls_topn's late materialisation
         s.rgs = *p.only;
         s.pruned = 0;
@@ -1361,7 +1375,9 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
         if (a.fn != AGG_COUNT_STAR) need[a.col] = 1;
         if (a.fn == AGG_SUM_PRODUCT) need[a.col2] = 1;
     }
-    for (uint32_t c : s.keys) need[c] = 1;
+    for (uint32_t c : s.keys)
+        if (!(c & FLS_KEY_MAPPED)) need[c] = 1;
+    for (const HostBinding &b : s.binds) need[b.col] = 1;
     if (s.reduce == Reduce::TopN) need[s.tkey.col] = 1;
     for (uint32_t c = 0; c < ncols; ++c) {
         bool any = false;
@@ -1494,6 +1510,8 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
         HIP_TRY(launch_keyset(sl.d_sdesc.p, (uint32_t)ns, (uint32_t)rows, sl.d_mask.p, sl.d_counts.p, d.err.p,
                               sl.stream));
     }
+    if (!s.binds.empty())  // mapped GROUP BY keys: their codes, and the inner ones' narrowing of the mask
+        if (int rc = enqueue_keymap(t, s, d, sl, rows)) return rc;
     if (s.reduce != Reduce::None) return 0;  // an aggregate / top-N scan reduces under the mask: nothing is compacted or delivered
     HIP_TRY(hb.h_counts.alloc(hb.nvec));
     HIP_TRY(hb.h_sel.alloc(std::max<uint64_t>(rows, 1)));
@@ -1570,7 +1588,7 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     Slot &sl = d.slots[si];
     HostBatch &hb = *sl.hb;
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
-    const bool filtered = !s.terms.empty();
+    const bool filtered = s.masked();  // (a mapped key's probe needs the mask: filter_kernel with zero terms)
     HIP_TRY(hipSetDevice(d.dev));
     // 1. H2D of the batch's compressed bytes
     // (resident image: nothing when every row group of the batch is there
@@ -1620,7 +1638,8 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     // (fls_aggregate_grouped has checked the chunks).
     std::vector<uint8_t> code_w(ncols, 0), in_term(ncols, 0), is_key(ncols, 0);
     for (auto &h : s.terms) in_term[h.col] = 1;
-    for (uint32_t c : s.keys) is_key[c] = 1;
+    for (uint32_t c : s.keys)
+        if (!(c & FLS_KEY_MAPPED)) is_key[c] = 1;
     for (uint32_t c = 0; c < ncols; ++c) {
         hb.ob[c] = (uint8_t)out_bytes_of(t, c);
         const bool coded = is_key[c] || (s.dict_codes && col_selected(s.mask, c));
@@ -2043,6 +2062,7 @@ static int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
         const uint32_t err = *(volatile const uint32_t *)hb->h_err.p;
         if (err & KERR_FILTER_STR) return fail(FLS_ERR_FORMAT, "filter: string outside its batch heap (flags 0x%x)", err);
         if (err & KERR_KEYSET) return fail(FLS_ERR_FORMAT, "filter: damaged key-set descriptor (flags 0x%x)", err);
+        if (err & KERR_KEYMAP) return fail(FLS_ERR_FORMAT, "grouped aggregate: damaged key-map descriptor (flags 0x%x)", err);
         if (err & KERR_NARROW)
             return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a narrowed column (flags 0x%x)", err);
         if (err & KERR_LDS_BASE) return fail(FLS_ERR_DEVICE, "FSST kernel: dynamic LDS not at address 0 (flags 0x%x)", err);
@@ -2327,6 +2347,19 @@ void fls_disconnect(fls_connection *conn) {
     if (conn) {  // the connection's key sets go with it (a filter or scan still using one keeps it alive)
         KeySetRegistry &R = keyset_registry();
         std::vector<std::shared_ptr<KeySet>> dead;  // released outside the lock
+        std::lock_guard<std::mutex> lk(R.mu);
+        for (auto it = R.live.begin(); it != R.live.end();) {
+            if (it->second->conn == conn) {
+                dead.push_back(std::move(it->second));
+                it = R.live.erase(it);
+            } else {
+                ++it;
+            }
+        }
+    }
+    if (conn) {  // ... and its key maps (a binding or scan still using one keeps it alive)
+        KeyMapRegistry &R = keymap_registry();
+        std::vector<std::shared_ptr<KeyMap>> dead;  // released outside the lock
         std::lock_guard<std::mutex> lk(R.mu);
         for (auto it = R.live.begin(); it != R.live.end();) {
             if (it->second->conn == conn) {

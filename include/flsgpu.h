@@ -387,6 +387,92 @@ int fls_group_result_key(const fls_group_result *r, uint64_t group, uint32_t key
 /* the group's n values in the aggregates' order; NULL out of range */
 const fls_aggregate_value *fls_group_result_values(const fls_group_result *r, uint64_t group);
 void fls_group_result_free(fls_group_result *r);
+
+/* Key maps: GROUP BY an attribute of a joined dimension table.  A key map is
+ * a function from 64-bit keys to 16-bit codes, built on the host from the
+ * build side of the join (keys[i] -> values[i], i in [0, n)); bound to a
+ * foreign-key column of a fact table, it lets fls_aggregate_grouped name
+ * "the code the map gives this column" as a GROUP BY key: the nation of
+ * l_suppkey, the priority class of l_orderkey.  No GPU is needed to create a
+ * map, query it or prune with it.  keys and kind are a key set's (above);
+ * values are codes in [0, 65534]: 0xFFFF marks "absent" inside the image and
+ * is refused (FLS_ERR_ARG).  A key listed twice with one value is kept once;
+ * with two values the map is no function: FLS_ERR_ARG naming the key and
+ * both values.  n = 0 is a valid empty map.
+ * form: 0 auto, 1 dense, 2 hash table.
+ *   dense: uint16[max - min + 1] indexed by key - min (mod 2^64), holes hold
+ *          0xFFFF, padded to 8 bytes; max - min + 1 <= 2^31 (a 4 GiB image).
+ *   hash:  the key set's table (8-byte slots, capacity, home slot, ascending
+ *          insertion, sentinel and max_probe exactly as documented above),
+ *          followed at byte 8 * capacity by uint16[capacity]: the slots'
+ *          codes, 0xFFFF in empty slots, padded to 8 bytes.
+ *   auto:  dense when max - min + 1 <= 2^31 and the array is no larger than
+ *          the hash image (10 bytes per slot, padded) would be, or at most
+ *          1 MiB; else the hash table.
+ * The image is a pure function of the map, whatever the order of the input.
+ * FLS_ERR_LIMIT: n above 2^28 (returned before keys or values is read), a
+ * forced dense map spanning more than 2^31 values.
+ * Handles are a key set's: opaque counter tokens looked up among the live
+ * maps, never dereferenced; a stale, foreign or key-set handle is FLS_ERR_ARG
+ * (and a map handle is no key set).  A binding and a running scan hold
+ * references, so freeing the handle or disconnecting while they use the map
+ * is safe.  The image is uploaded to a GPU by the first batch that probes it
+ * there (synchronously, fls_keymap_info.device_bytes per GPU), cached inside
+ * the map and freed with its last reference; it does not count against
+ * FLS_SCAN_RESIDENT_MB.  One map may serve any number of tables.
+ * Not in the reference. */
+typedef struct fls_keymap fls_keymap;
+typedef enum fls_keymap_form { FLS_KEYMAP_AUTO = 0, FLS_KEYMAP_DENSE = 1, FLS_KEYMAP_HASH = 2 } fls_keymap_form;
+typedef struct fls_keymap_info_t {
+    uint64_t count;         /* distinct keys */
+    uint32_t form;          /* the form chosen: FLS_KEYMAP_DENSE or FLS_KEYMAP_HASH */
+    uint32_t kind;          /* fls_keyset_kind */
+    uint64_t device_bytes;  /* bytes of the image, per GPU that probes the map */
+    uint64_t capacity;      /* hash: slots (0 for a dense map) */
+    uint32_t max_probe;     /* hash: longest probe sequence (0 for a dense or an empty map) */
+    uint32_t max_code;      /* the largest code (0 for the empty map) */
+    uint64_t min, max;      /* patterns, in the map's order (0 for the empty map) */
+    uint64_t empty;         /* hash: the empty slot's sentinel */
+} fls_keymap_info_t;
+int fls_keymap_create(fls_connection *conn, const uint64_t *keys, const uint16_t *values, uint64_t n,
+                      int kind /* fls_keyset_kind */, int form, fls_keymap **out);
+void fls_keymap_free(fls_keymap *map);
+int fls_keymap_info(const fls_keymap *map, fls_keymap_info_t *info);
+/* Host probe of the very image a scan uploads: 1 found (*code set), 0 absent. */
+int fls_keymap_lookup(const fls_keymap *map, uint64_t key, uint32_t *code);
+
+/* Mapped GROUP BY keys.  fls_aggregate_key_bindings sets the table's bindings
+ * (copied and replaced as a whole; n <= 4; n = 0 clears; sticky like
+ * fls_aggregate_exprs): binding i says "probe map with column col".  In the
+ * following fls_aggregate_grouped calls keys[q] = FLS_KEY_MAPPED | i means the
+ * code binding i's map gives its column; bindings no key names are ignored.
+ * A mapped key comes back as FLS_KEYV_INT with the code in lo (or
+ * FLS_KEYV_NULL), takes 16 value bits and one NULL bit of the 128-bit packed
+ * key, counts towards the 4 keys, and mixes with plain and VARCHAR keys in any
+ * order; its column may also be a plain key, an operand or a filter column.
+ * Default (inner join): a selected row whose column is NULL or whose value is
+ * not in the map belongs to no group and counts nowhere, exactly as if the
+ * filter carried `col IN keys(map)` as one more clause; the key is never NULL.
+ * Row groups are pruned as under IN_SET (a zone map without a map key in
+ * [min, max], an all-NULL chunk; the empty map prunes everything: zero groups,
+ * no device work) and count in fls_scan_pruned.
+ * FLS_KEYMAP_KEEP_UNMATCHED (left join): those rows form the NULL group, like
+ * a NULL plain key, and nothing is pruned.
+ * The codes are probed on the GPU per selected row (csrc/fls_keymap.hip) into
+ * a derived 2-byte key column in HBM; everything fls_aggregate_grouped
+ * promises -- first-occurrence order, the 64 / 256 distinct-key limits, values
+ * bit-identical across batch size, slot and GPU count, one group equal to
+ * fls_aggregate under the equivalent IN_SET filter -- holds unchanged.
+ * FLS_ERR_ARG before any device work.  The setter, naming "binding i":
+ * n > 4, a column out of range, a VARCHAR / BLOB / FLOAT / DOUBLE column or a
+ * DECIMAL wider than 64 bits, a map whose kind differs from the column's
+ * signedness, a handle that is not a live map, unknown flag bits.
+ * fls_aggregate_grouped, naming "key q": FLS_KEY_MAPPED | i with no binding
+ * i, and a binding named by two keys.  Not in the reference. */
+#define FLS_KEY_MAPPED 0x80000000u     /* keys[q] = FLS_KEY_MAPPED | i : binding i of the table */
+#define FLS_KEYMAP_KEEP_UNMATCHED 1u   /* left join: unmatched rows form the NULL group */
+typedef struct fls_key_binding { uint32_t col; uint32_t flags; uint64_t map; /* the fls_keymap handle */ } fls_key_binding;
+int fls_aggregate_key_bindings(fls_table *t, const fls_key_binding *b, uint32_t n);
 /* ORDER BY key [DESC] LIMIT k selected on the GPU: the k best rows of row
  * groups [rg_begin, rg_end) under the filter set by fls_scan_filter, ordered
  * by one key column; their global row indices and the values of the columns
