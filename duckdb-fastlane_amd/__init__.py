@@ -212,6 +212,16 @@ _sig("fls_group_result_ngroups", C.c_uint64, _P)
 _sig("fls_group_result_key", C.c_int, _P, C.c_uint64, C.c_uint32, C.POINTER(GroupKey))
 _sig("fls_group_result_values", C.POINTER(AggregateValue), _P, C.c_uint64)
 _sig("fls_group_result_free", None, _P)
+_PU64, _PU8 = C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint8))
+_sig("fls_aggregate_hashed", C.c_int, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(AggregateSpec), C.c_uint32,
+     C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(_P))
+_sig("fls_hash_result_ngroups", C.c_uint64, _P)
+_sig("fls_hash_result_first_rows", C.c_int, _P, _PU64)
+_sig("fls_hash_result_key", C.c_int, _P, C.c_uint32, _PU64, _PU8)
+_sig("fls_hash_result_aggregate", C.c_int, _P, C.c_uint32, _PU64, _PU64, _PU64, _PU8)
+_sig("fls_hash_result_stats", C.c_int, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double),
+     C.POINTER(C.c_double))
+_sig("fls_hash_result_free", None, _P)
 _sig("fls_topn", C.c_int, _P, C.POINTER(OrderKey), C.c_uint32, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32,
      C.POINTER(_P))
 _sig("fls_topn_pruned", C.c_int, _P, C.POINTER(OrderKey), C.c_uint32, C.c_uint32, C.c_uint32)
@@ -747,6 +757,74 @@ def _agg_value(v: AggregateValue):
     return x - (1 << 128) if x >> 127 else x
 
 
+MAX_HASH_GROUPS = 1 << 28         # kMaxHashGroups
+
+
+class HashGroups:
+    """The groups of Table.aggregate_hashed, as numpy arrays copied out of the
+    fls_hash_result, in unspecified order: first_row (uint64: the global row
+    index of each group's first selected row), key_values[q] (uint64: key q's
+    value sign- or zero-extended to 64 bits; view it as int64 for a signed
+    column) and key_null[q] (bool), and per aggregate a the arrays count[a],
+    lo[a], hi[a] (uint64) and kind[a] (uint8, AGGV_*) with
+    fls_aggregate_value's meaning.  key_signed[q] says how key q extends.
+    table_bytes is one pipeline's table; scan_ms, extract_ms (compaction and
+    D2H) and merge_ms are the call's phases on the host clock."""
+
+    def __init__(self, res, key_signed, naggs: int):
+        n = self.ngroups = int(_lib.fls_hash_result_ngroups(res))
+        self.key_signed = list(key_signed)
+
+        def arr(p, dtype):
+            return np.ctypeslib.as_array(p, shape=(n,)).view(dtype).copy() if n else np.zeros(0, dtype)
+        p64, p64b, p64c, p8 = (C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(),
+                               C.POINTER(C.c_uint8)())
+        _check(_lib.fls_hash_result_first_rows(res, C.byref(p64)))
+        self.first_row = arr(p64, np.uint64)
+        self.key_values, self.key_null = [], []
+        for q in range(len(self.key_signed)):
+            _check(_lib.fls_hash_result_key(res, q, C.byref(p64), C.byref(p8)))
+            self.key_values.append(arr(p64, np.uint64))
+            self.key_null.append(arr(p8, np.uint8).astype(bool))
+        self.count, self.lo, self.hi, self.kind = [], [], [], []
+        for a in range(naggs):
+            _check(_lib.fls_hash_result_aggregate(res, a, C.byref(p64), C.byref(p64b), C.byref(p64c), C.byref(p8)))
+            self.count.append(arr(p64, np.uint64))
+            self.lo.append(arr(p64b, np.uint64))
+            self.hi.append(arr(p64c, np.uint64))
+            self.kind.append(arr(p8, np.uint8))
+        tb, sm, em, mm = C.c_uint64(), C.c_double(), C.c_double(), C.c_double()
+        _check(_lib.fls_hash_result_stats(res, C.byref(tb), C.byref(sm), C.byref(em), C.byref(mm)))
+        self.table_bytes, self.scan_ms, self.extract_ms, self.merge_ms = tb.value, sm.value, em.value, mm.value
+
+    def __len__(self) -> int:
+        return self.ngroups
+
+    def to_list(self, ordered: bool = True) -> list:
+        """[(key_tuple, values)] in aggregate_grouped's shape: a key element an
+        int or None (NULL), values as aggregate() returns them.  ordered: by
+        each group's first row, which is aggregate_grouped's order."""
+        order = np.argsort(self.first_row, kind="stable") if ordered else np.arange(self.ngroups)
+        keys = []
+        for v, nul, sg in zip(self.key_values, self.key_null, self.key_signed):
+            vals = (v.view(np.int64) if sg else v).tolist()
+            keys.append([None if z else x for x, z in zip(vals, nul.tolist())])
+        cols = []
+        for cnt, lo, hi, kind in zip(self.count, self.lo, self.hi, self.kind):
+            dbl = lo.view(np.float64).tolist()
+            col = []
+            for k, l, h, d in zip(kind.tolist(), lo.tolist(), hi.tolist(), dbl):
+                if k == AGGV_NULL:
+                    col.append(None)
+                elif k == AGGV_DOUBLE:
+                    col.append(d)
+                else:
+                    x = (h << 64) | l
+                    col.append(x - (1 << 128) if x >> 127 else x)
+            cols.append(col)
+        return [(tuple(k[g] for k in keys), [c[g] for c in cols]) for g in order.tolist()]
+
+
 class Table:
     def __init__(self, h, conn):
         self.h, self.conn, self._keep = h, conn, None
@@ -1133,6 +1211,39 @@ class Table:
             return out
         finally:
             _lib.fls_group_result_free(res)
+
+    def aggregate_hashed(self, keys, aggs, max_groups: int, filt=None, rg_begin=0, rg_end=None) -> HashGroups:
+        """GROUP BY keys (1 to 4 integer-like columns of any cardinality up to
+        max_groups) of the aggregates aggregate() takes, except FLOAT / DOUBLE
+        sums, in a hash table in HBM (fls_aggregate_hashed): the call for
+        GROUP BY l_orderkey, which aggregate_grouped refuses.  Returns a
+        HashGroups of numpy arrays in unspecified order; its
+        to_list() is aggregate_grouped's list.  The packed key (per key the
+        bits of its zone maps' max - min over the range, plus a NULL bit)
+        holds at most 63 bits.  FlsError with code ERR_LIMIT when one
+        pipeline's row groups hold more than max_groups distinct keys among
+        the selected rows: call again with a larger max_groups (each pipeline
+        allocates the next power of two >= 2 * max_groups slots)."""
+        if rg_end is None:
+            rg_end = self.nrowgroups
+        karr = (C.c_uint32 * max(1, len(keys)))(*keys[:max(1, len(keys))])
+        arr, exprs = _agg_specs(aggs)
+        res = _P()
+        self.set_filter(filt)
+        try:
+            if exprs:
+                self.set_aggregate_exprs(exprs)
+            _check(_lib.fls_aggregate_hashed(self.h, karr, len(keys), arr, len(aggs), max_groups, rg_begin, rg_end,
+                                             C.byref(res)))
+        finally:
+            _check(_lib.fls_scan_filter(self.h, None, 0))
+            if exprs:
+                self.set_aggregate_exprs(None)
+        try:
+            signed = [self.column(k).type in (INT8, INT16, INT32, INT64, DATE, DECIMAL) for k in keys]
+            return HashGroups(res, signed, len(aggs))
+        finally:
+            _lib.fls_hash_result_free(res)
 
     # -- ORDER BY key LIMIT k selected on the GPU
     def topn_pruned(self, order_by: int, k: int, desc=False, nulls_first=False, rg_begin=0, rg_end=None) -> int:

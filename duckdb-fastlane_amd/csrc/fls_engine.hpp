@@ -5,6 +5,9 @@
 //                         pipeline (scan_setup, fill_batch, scan_acquire ...)
 //   fls_scan_agg.hip      fls_aggregate / fls_aggregate_grouped: checks,
 //                         per-batch enqueue, the host fold
+//   fls_scan_hashagg.hip  fls_aggregate_hashed: checks, the key layout, the
+//                         per-pipeline tables, per-batch enqueue, extraction
+//                         and the host merge
 //   fls_scan_topn.hip     fls_topn: checks, per-batch enqueue, the host merge
 //                         and the late materialisation
 //   fls_scan_keyset.hip   the key-set registry and fls_keyset_*
@@ -13,7 +16,7 @@
 //   fls_device_table.hip  the device-resident table (fls_device_*)
 //
 // The pushdown and device-table units depend on flsgpu.hip's scan pipeline and
-// launch helpers; flsgpu.hip depends on them only through the three enqueue_*
+// launch helpers; flsgpu.hip depends on them only through the four enqueue_*
 // functions fill_batch switches over, keyset_registry() and, for mapped GROUP
 // BY keys, enqueue_keymap, binding_may_match and keymap_registry().  Every function
 // and registry declared here is defined in exactly one unit.
@@ -47,6 +50,7 @@
 #include "fls_filter.hpp"
 #include "fls_format.hpp"
 #include "fls_groupagg.hpp"
+#include "fls_hashagg.hpp"
 #include "fls_keymap.hpp"
 #include "fls_keyset.hpp"
 #include "fls_pinned.hpp"
@@ -343,6 +347,9 @@ struct Slot {                       // one batch of row groups in flight
     DevBuf<uint8_t> d_gdesc;
     DevBuf<uint8_t> d_gvec;         // stage 1: the vectors' groups
     DevBuf<uint8_t> d_grg;          // stage 2: the row groups' groups
+    // hash aggregate batches (fls_aggregate_hashed)
+    PinBuf<uint8_t> h_hdesc;        // DevHashKey[kMaxKeys] + DevHashFields[kMaxAggs]
+    DevBuf<uint8_t> d_hdesc;
     // mapped keys of a grouped aggregate batch (fls_aggregate_key_bindings)
     PinBuf<DevMapTerm> h_mdesc;
     DevBuf<DevMapTerm> d_mdesc;
@@ -526,6 +533,22 @@ enum class Reduce {
     Aggregate,       // fls_aggregate: per-vector partial records (enqueue_aggregate)
     GroupAggregate,  // fls_aggregate_grouped: per-row-group tables of groups (enqueue_group_aggregate)
     TopN,            // fls_topn: per-row-group candidate lists (enqueue_topn)
+    HashAggregate,   // fls_aggregate_hashed: every batch into the pipeline's table in HBM (enqueue_hash_aggregate)
+};
+
+// The packed key and the tables of a hash aggregate (fls_scan_hashagg.hip):
+// key q's field is value - min[q] in bits[q] bits at shift[q], its NULL mark
+// bit null_bit[q].  The tables belong to the call, one per pipeline of the
+// scan (tables[g] for ScanCtx::devs[g]), allocated and zeroed before scan_start.
+struct HashPlan {
+    uint64_t min[kMaxKeys] = {}, span[kMaxKeys] = {};
+    uint32_t bits[kMaxKeys] = {}, shift[kMaxKeys] = {}, null_bit[kMaxKeys] = {};
+    uint32_t total = 0;                  // bits of the packed key (<= kHashKeyBits)
+    uint64_t cap = 0;                    // slots of each table
+    uint32_t nfields = 0;                // fields of a slot (fls_hashagg.hpp)
+    std::vector<DevHashFields> fields;   // per aggregate
+    std::vector<uint64_t *> tables;      // per pipeline, in HBM
+    bool combine = false;                // merge runs of equal keys in adjacent lanes before the atomics
 };
 
 // What a scan is asked to do (scan_setup).  The pointers are borrowed for the
@@ -539,11 +562,14 @@ struct ScanPlan {
     // options (dictionary codes, narrowing, deferred records); fls_materialize
     // and the scans the engine runs for itself deliver at full width
     bool delivering_scan = false;
-    const std::vector<HostAgg> *aggs = nullptr;     // Reduce::Aggregate / GroupAggregate
+    const std::vector<HostAgg> *aggs = nullptr;     // Reduce::Aggregate / GroupAggregate / HashAggregate
     // Reduce::GroupAggregate: the GROUP BY keys, a column each or
     // FLS_KEY_MAPPED | i for binding i of binds
     const std::vector<uint32_t> *keys = nullptr;
     const std::vector<HostBinding> *binds = nullptr;  // the mapped keys' bindings (NULL: none)
+    // Reduce::HashAggregate (max_groups != 0): keys are plain columns, hash their layout and tables
+    uint64_t max_groups = 0;
+    const HashPlan *hash = nullptr;
     const fls_order_key *order = nullptr;           // Reduce::TopN: the key and
     uint32_t k = 0;                                 // ... how many rows
     // exactly these row groups (ascending, inside the range) instead of
@@ -567,11 +593,17 @@ struct ScanCtx {
     // column (keymap_kernel).  With a binding the scan always has a mask.
     std::vector<HostBinding> binds;
     bool masked() const { return !terms.empty() || !binds.empty(); }
+    // hash aggregate scan (Reduce::HashAggregate): the key layout and the
+    // pipelines' tables, and the groups one table may hold
+    HashPlan hash;
+    uint64_t max_groups = 0;
     // top-N scan (Reduce::TopN): no column is delivered, each batch's
     // candidate lists ride in its HostBatch
     fls_order_key tkey = {};
     uint32_t tk = 0;
-    bool aggregating() const { return reduce == Reduce::Aggregate || reduce == Reduce::GroupAggregate; }
+    bool aggregating() const {
+        return reduce == Reduce::Aggregate || reduce == Reduce::GroupAggregate || reduce == Reduce::HashAggregate;
+    }
     bool dict_codes = false;        // deliver DICT string chunks as codes + dictionary
     bool narrow = false;            // deliver integer columns narrowed to their row groups' ranges
     bool defer_records = false;     // FSST-as-lengths records built by fls_scan_build_records, not scan_acquire
@@ -773,6 +805,20 @@ int rg_vec_table(const fls_table *t, const Slot &sl, uint32_t *tab, uint32_t &rg
 int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);        // fls_scan_agg.hip
 int enqueue_group_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);  // fls_scan_agg.hip
 int enqueue_topn(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);             // fls_scan_topn.hip
+int enqueue_hash_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);   // fls_scan_hashagg.hip
+
+// ---- what the aggregate calls share (fls_scan_agg.hip) ---------------------------
+
+// The argument checks of fls_aggregate, fls_aggregate_grouped and
+// fls_aggregate_hashed (`who`): the aggregates into ha, or FLS_ERR_ARG before
+// any device work.
+int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_spec *aggs, uint32_t n,
+                     uint32_t rg_begin, uint32_t rg_end, std::vector<HostAgg> &ha);
+// Is aggregate h a FLOAT / DOUBLE SUM, MIN or MAX?
+bool agg_is_float(const fls_table *t, const HostAgg &h);
+// The aggregates of a batch as the kernels see them (sl.h_adesc -> sl.d_adesc
+// on the slot's stream), over the slot's decoded columns and staged validity.
+int upload_agg_descs(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl);
 
 // ---- mapped GROUP BY keys (fls_scan_keymap.hip) ---------------------------------
 

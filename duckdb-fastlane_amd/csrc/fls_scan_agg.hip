@@ -14,7 +14,7 @@ FLS_ENGINE_BEGIN
 
 // The aggregates of a batch as the kernels see them (sl.h_adesc -> sl.d_adesc
 // on the slot's stream), over the slot's decoded columns and staged validity.
-static int upload_agg_descs(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl) {
+int upload_agg_descs(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl) {
     const std::vector<uint8_t> &need = sl.valid_staged;
     const uint32_t na = (uint32_t)s.aggs.size();
     HIP_TRY(sl.h_adesc.alloc(na));
@@ -215,8 +215,13 @@ double max_factor(const fls_table *t, uint32_t rg, uint32_t c, bool neg, int64_t
     return m == 0 ? 0.0 : std::nextafter((double)m, HUGE_VAL);
 }
 
-// The argument checks fls_aggregate and fls_aggregate_grouped (`who`) share:
-// the aggregates into ha, or FLS_ERR_ARG before any device work.
+}  // namespace
+
+FLS_ENGINE_BEGIN
+
+// The argument checks fls_aggregate, fls_aggregate_grouped and
+// fls_aggregate_hashed (`who`) share: the aggregates into ha, or FLS_ERR_ARG
+// before any device work.
 int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_spec *aggs, uint32_t n,
                      uint32_t rg_begin, uint32_t rg_end, std::vector<HostAgg> &ha) {
     if (n == 0 || n > kMaxAggs) return fail(FLS_ERR_ARG, "%s: %u aggregates (1 to %u per call)", who, n, kMaxAggs);
@@ -289,6 +294,14 @@ int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_sp
     return 0;
 }
 
+bool agg_is_float(const fls_table *t, const HostAgg &h) {
+    return h.fn >= AGG_SUM && h.fn != AGG_SUM_EXPR && type_is_float(t->meta.cols[h.col].type);
+}
+
+FLS_ENGINE_END
+
+namespace {
+
 // The running value of one aggregate (of one group) on the host.
 struct AggAcc {
     uint64_t count = 0;
@@ -297,10 +310,6 @@ struct AggAcc {
     uint64_t key = 0;
     explicit AggAcc(uint8_t fn = 0) : key(fn == AGG_MIN ? ~0ull : 0ull) {}
 };
-
-bool agg_is_float(const fls_table *t, const HostAgg &h) {
-    return h.fn >= AGG_SUM && h.fn != AGG_SUM_EXPR && type_is_float(t->meta.cols[h.col].type);
-}
 
 // The grouped fold's addition of a vector's partial binary64 sum onto the
 // running sum.  It differs from acc + x only in which NaN comes back when both

@@ -1209,7 +1209,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     if (p.filter) s.terms = *p.filter;
     // the one place that decides what kind of scan this is
     s.reduce = Reduce::None;
-    if (p.aggs) s.reduce = p.keys ? Reduce::GroupAggregate : Reduce::Aggregate;
+    if (p.aggs) s.reduce = p.hash ? Reduce::HashAggregate : p.keys ? Reduce::GroupAggregate : Reduce::Aggregate;
     else if (p.order && p.k) s.reduce = Reduce::TopN;
     // the delivery options: consumers' scans only (not materialize); a reducing scan delivers nothing
     const bool options = p.delivering_scan && s.reduce == Reduce::None;
@@ -1225,8 +1225,16 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     s.tk = 0;
     s.tkey = fls_order_key{};
     bool string_key = false;
+    s.hash = HashPlan();
+    s.max_groups = 0;
     switch (s.reduce) {
     case Reduce::None: break;
+    case Reduce::HashAggregate:
+        // the key columns (plain integer-like columns) and the operands are
+        // decoded, as a grouped aggregate scan's are
+        s.hash = *p.hash;
+        s.max_groups = p.max_groups;
+        [[fallthrough]];
     case Reduce::GroupAggregate:
         // the GROUP BY columns of a grouped aggregate scan are decoded too
         s.keys = *p.keys;
@@ -1847,6 +1855,7 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
         case Reduce::Aggregate: rc = enqueue_aggregate(t, s, d, sl, rows, lo); break;             // partial records
         case Reduce::GroupAggregate: rc = enqueue_group_aggregate(t, s, d, sl, rows, lo); break;  // tables of groups
         case Reduce::TopN: rc = enqueue_topn(t, s, d, sl, rows, lo); break;                       // candidate lists
+        case Reduce::HashAggregate: rc = enqueue_hash_aggregate(t, s, d, sl, rows, lo); break;    // into the pipeline's table
         }
         if (rc) return rc;
     }
@@ -2065,6 +2074,9 @@ static int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
         if (err & KERR_KEYMAP) return fail(FLS_ERR_FORMAT, "grouped aggregate: damaged key-map descriptor (flags 0x%x)", err);
         if (err & KERR_NARROW)
             return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a narrowed column (flags 0x%x)", err);
+        if (err & KERR_HASH_RANGE)
+            return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a hash aggregate's key column "
+                        "(flags 0x%x)", err);
         if (err & KERR_LDS_BASE) return fail(FLS_ERR_DEVICE, "FSST kernel: dynamic LDS not at address 0 (flags 0x%x)", err);
         // a grouped aggregate past its capacity: the kernels stopped before they wrote past a table
         if (err == KERR_GROUP_RG)
@@ -2075,6 +2087,12 @@ static int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
             return fail(FLS_ERR_LIMIT,
                         "grouped aggregate: more than %u distinct keys among the selected rows of one 1024-row vector "
                         "(kMaxVecGroups); fall back to a scan and group its rows (flags 0x%x)", kMaxVecGroups, err);
+        // a hash aggregate past its table: the kernel dropped the rows it had no group for
+        if (err == KERR_HASH_LIMIT)
+            return fail(FLS_ERR_LIMIT,
+                        "hash aggregate: more than max_groups = %llu distinct keys among the selected rows of one "
+                        "pipeline's row groups; call again with a larger max_groups (flags 0x%x)",
+                        (unsigned long long)s.max_groups, err);
         if (err) return fail(FLS_ERR_FORMAT, "corrupt chunk detected while decoding (flags 0x%x)", err);
         return 0;
     };

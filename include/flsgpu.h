@@ -51,7 +51,7 @@ typedef enum fls_status {
     FLS_ERR_STATE = -5,     /* call out of order (e.g. decode before upload) */
     FLS_ERR_NOMEM = -6,
     FLS_ERR_CONFIG = -7,    /* an FLS_* tuning variable names a kernel this build does not hold */
-    FLS_ERR_LIMIT = -8      /* a documented capacity was exceeded (fls_aggregate_grouped, fls_topn, fls_keyset_create) */
+    FLS_ERR_LIMIT = -8      /* a documented capacity was exceeded (fls_aggregate_grouped, fls_aggregate_hashed, fls_topn, fls_keyset_create) */
 } fls_status;
 
 typedef struct fls_connection fls_connection;
@@ -387,6 +387,72 @@ int fls_group_result_key(const fls_group_result *r, uint64_t group, uint32_t key
 /* the group's n values in the aggregates' order; NULL out of range */
 const fls_aggregate_value *fls_group_result_values(const fls_group_result *r, uint64_t group);
 void fls_group_result_free(fls_group_result *r);
+/* GROUP BY keys[0..nkeys) of any cardinality up to max_groups: a hash
+ * aggregate in HBM, for the keys fls_aggregate_grouped's 64 / 256 distinct-key
+ * limits refuse (GROUP BY l_orderkey, l_partkey, l_suppkey).  The filter set by
+ * fls_scan_filter (key sets included), the pruning, the decode, the resident
+ * image, the batch pipeline and the sharding over pipelines are the other
+ * aggregate calls'; only the reduction differs: every pipeline of the scan
+ * owns one open-addressing table in HBM for the length of the call -- the next
+ * power of two >= 2 * max_groups slots, one 8-byte array per field actually
+ * needed: the packed key, the first row, per aggregate its count and, for
+ * sums and MIN / MAX, lo and hi -- into which each batch inserts its selected
+ * rows with device-scope atomics (csrc/fls_hashagg.hip).  After the scan the
+ * occupied slots are compacted on the device, copied in one D2H per pipeline
+ * and merged by key on the host when there are several pipelines.
+ * Keys (1 to 4): INT*, UINT*, BOOLEAN, DATE, DECIMAL of at most 64 bits, in
+ * any encoding; the key is the decoded value, a NULL key a group of its own.
+ * The packed key holds at most 63 bits: per key the bits of max - min of its
+ * zone maps over [rg_begin, rg_end) before pruning (the type's width where a
+ * row group has no valid zone map; an all-NULL chunk adds nothing), plus one
+ * NULL bit.  l_orderkey at SF 10 takes 26 + 1 bits; a full-range INT64 key is
+ * refused.  A decoded value outside that range means a corrupt or foreign
+ * file: FLS_ERR_FORMAT.
+ * Aggregates: fls_aggregate's, with its argument checks and overflow bounds --
+ * COUNT(*), COUNT(col), integer SUM, SUM_PRODUCT, SUM_EXPR, MIN / MAX of
+ * integer and FLOAT / DOUBLE columns -- except SUM of a FLOAT / DOUBLE column:
+ * an atomic float sum depends on arrival order, and no call here returns a
+ * value that is not reproducible (fls_aggregate_grouped sums floats).
+ * Groups come in unspecified order; first_rows gives the caller a canonical
+ * one.  The set of (key, first row, values) is identical whatever the batch
+ * size, slot count or number of pipelines, and where fls_aggregate_grouped
+ * accepts the same arguments it equals that call's groups and values exactly.
+ * No row group to read (an empty range, everything pruned): zero groups, no
+ * device work, no table.
+ * FLS_ERR_ARG before any device work, naming "key q:": nkeys == 0 or > 4, a
+ * column out of range or listed twice, a VARCHAR key (a dictionary code means
+ * a string of one row group only), a mapped key (FLS_KEY_MAPPED), a FLOAT /
+ * DOUBLE / BLOB key, a packed key of more than 63 bits; naming "aggregate i:":
+ * everything fls_aggregate refuses and a FLOAT / DOUBLE SUM; max_groups
+ * outside 1 .. 2^28.
+ * FLS_ERR_LIMIT: more than max_groups distinct keys among the selected rows of
+ * one pipeline's row groups (the kernel checks before it writes; call again
+ * with a larger max_groups).  FLS_ERR_DEVICE, naming the bytes: a table that
+ * cannot be allocated.  The fls_table stays usable after either.
+ * *out is owned by the caller (fls_hash_result_free); the accessors return
+ * arrays of fls_hash_result_ngroups elements that live as long as the result:
+ * first_rows  per group the global row index (fls_rowgroup.first_row + row)
+ *             of its first selected row;
+ * key         key `key`'s decoded value, sign- or zero-extended to 64 bits by
+ *             column type (0 where is_null is 1);
+ * aggregate   count / lo / hi / kind with fls_aggregate_value's meaning: a
+ *             SUM / MIN / MAX with count 0 is FLS_AGGV_NULL;
+ * stats       the bytes of one pipeline's table and the call's phases on the
+ *             host clock: the scan, extraction + D2H, merge + unpacking (any
+ *             pointer may be NULL).
+ * Not in the reference. */
+typedef struct fls_hash_result fls_hash_result;
+int fls_aggregate_hashed(fls_table *t, const uint32_t *keys, uint32_t nkeys,
+                         const fls_aggregate_spec *aggs, uint32_t n, uint64_t max_groups,
+                         uint32_t rg_begin, uint32_t rg_end, fls_hash_result **out);
+uint64_t fls_hash_result_ngroups(const fls_hash_result *r);
+int fls_hash_result_first_rows(const fls_hash_result *r, const uint64_t **rows);
+int fls_hash_result_key(const fls_hash_result *r, uint32_t key, const uint64_t **values, const uint8_t **is_null);
+int fls_hash_result_aggregate(const fls_hash_result *r, uint32_t agg, const uint64_t **count,
+                              const uint64_t **lo, const uint64_t **hi, const uint8_t **kind);
+int fls_hash_result_stats(const fls_hash_result *r, uint64_t *table_bytes, double *scan_ms, double *extract_ms,
+                          double *merge_ms);
+void fls_hash_result_free(fls_hash_result *r);
 
 /* Key maps: GROUP BY an attribute of a joined dimension table.  A key map is
  * a function from 64-bit keys to 16-bit codes, built on the host from the
