@@ -143,6 +143,21 @@ class OrderKey(C.Structure):     # fls_order_key
 MAX_TOPN = 1024
 
 
+class GroupHaving(C.Structure):  # fls_group_having: aggregate[agg] <op> constant
+    _fields_ = [("agg", C.c_uint32), ("op", C.c_uint8), ("kind", C.c_uint8), ("pad", C.c_uint8 * 2),
+                ("lo", C.c_uint64), ("hi", C.c_uint64)]
+
+
+class GroupSelect(C.Structure):  # fls_group_select
+    _fields_ = [("having", C.POINTER(GroupHaving)), ("nhaving", C.c_uint32), ("order_agg", C.c_uint32),
+                ("desc", C.c_uint8), ("nulls_first", C.c_uint8), ("pad", C.c_uint8 * 2), ("limit", C.c_uint32)]
+
+
+GROUP_ORDER_NONE = 0xFFFFFFFF     # FLS_GROUP_ORDER_NONE
+MAX_GROUP_LIMIT = 1024            # kMaxGroupLimit
+MAX_HAVING = 8                    # kMaxHaving
+
+
 class DecodeStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("values", C.c_uint64), ("packed_bytes", C.c_uint64),
                 ("meta_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("launches", C.c_uint32),
@@ -222,6 +237,10 @@ _sig("fls_hash_result_aggregate", C.c_int, _P, C.c_uint32, _PU64, _PU64, _PU64, 
 _sig("fls_hash_result_stats", C.c_int, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double),
      C.POINTER(C.c_double))
 _sig("fls_hash_result_free", None, _P)
+_sig("fls_aggregate_hashed_select", C.c_int, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(AggregateSpec),
+     C.c_uint32, C.c_uint64, C.POINTER(GroupSelect), C.c_uint32, C.c_uint32, C.POINTER(_P))
+_sig("fls_hash_result_select_stats", C.c_int, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int),
+     C.POINTER(C.c_double))
 _sig("fls_topn", C.c_int, _P, C.POINTER(OrderKey), C.c_uint32, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32,
      C.POINTER(_P))
 _sig("fls_topn_pruned", C.c_int, _P, C.POINTER(OrderKey), C.c_uint32, C.c_uint32, C.c_uint32)
@@ -769,11 +788,16 @@ class HashGroups:
     lo[a], hi[a] (uint64) and kind[a] (uint8, AGGV_*) with
     fls_aggregate_value's meaning.  key_signed[q] says how key q extends.
     table_bytes is one pipeline's table; scan_ms, extract_ms (compaction and
-    D2H) and merge_ms are the call's phases on the host clock."""
+    D2H) and merge_ms are the call's phases on the host clock.  Of a call
+    with having / order_by / limit: groups_total (the groups formed),
+    groups_passed (after HAVING, before LIMIT), selected_on_device (the
+    selection ran on the GPU: one pipeline held the groups) and select_ms;
+    with an order_by or a limit the arrays are in result order."""
 
-    def __init__(self, res, key_signed, naggs: int):
+    def __init__(self, res, key_signed, naggs: int, in_result_order: bool = False):
         n = self.ngroups = int(_lib.fls_hash_result_ngroups(res))
         self.key_signed = list(key_signed)
+        self.in_result_order = in_result_order
 
         def arr(p, dtype):
             return np.ctypeslib.as_array(p, shape=(n,)).view(dtype).copy() if n else np.zeros(0, dtype)
@@ -796,6 +820,10 @@ class HashGroups:
         tb, sm, em, mm = C.c_uint64(), C.c_double(), C.c_double(), C.c_double()
         _check(_lib.fls_hash_result_stats(res, C.byref(tb), C.byref(sm), C.byref(em), C.byref(mm)))
         self.table_bytes, self.scan_ms, self.extract_ms, self.merge_ms = tb.value, sm.value, em.value, mm.value
+        gt, gp, od = C.c_uint64(), C.c_uint64(), C.c_int()
+        _check(_lib.fls_hash_result_select_stats(res, C.byref(gt), C.byref(gp), C.byref(od), C.byref(sm)))
+        self.groups_total, self.groups_passed = gt.value, gp.value
+        self.selected_on_device, self.select_ms = bool(od.value), sm.value
 
     def __len__(self) -> int:
         return self.ngroups
@@ -803,8 +831,10 @@ class HashGroups:
     def to_list(self, ordered: bool = True) -> list:
         """[(key_tuple, values)] in aggregate_grouped's shape: a key element an
         int or None (NULL), values as aggregate() returns them.  ordered: by
-        each group's first row, which is aggregate_grouped's order."""
-        order = np.argsort(self.first_row, kind="stable") if ordered else np.arange(self.ngroups)
+        each group's first row, which is aggregate_grouped's order; the
+        groups of a call with an order_by or a limit stay in result order."""
+        by_first = ordered and not self.in_result_order
+        order = np.argsort(self.first_row, kind="stable") if by_first else np.arange(self.ngroups)
         keys = []
         for v, nul, sg in zip(self.key_values, self.key_null, self.key_signed):
             vals = (v.view(np.int64) if sg else v).tolist()
@@ -1212,7 +1242,38 @@ class Table:
         finally:
             _lib.fls_group_result_free(res)
 
-    def aggregate_hashed(self, keys, aggs, max_groups: int, filt=None, rg_begin=0, rg_end=None) -> HashGroups:
+    @staticmethod
+    def _group_select(having, order_by, limit):
+        """the fls_group_select of aggregate_hashed's having / order_by / limit
+        (and the array it points into, which must outlive the call)"""
+        terms = (GroupHaving * max(1, len(having or ())))()
+        for j, (agg, op, value) in enumerate(having or ()):
+            if isinstance(op, str) and op not in ("=", "==", "!=", "<>", "<", "<=", ">", ">="):
+                raise ValueError(f"aggregate_hashed: having {j}: op {op!r} is not one of = != < <= > >=")
+            terms[j].agg, terms[j].op = agg, OPS[op] if isinstance(op, str) else op   # (an int: the code itself)
+            if isinstance(value, float):
+                terms[j].kind = AGGV_DOUBLE
+                terms[j].lo = int(np.array([value], dtype=np.float64).view(np.uint64)[0])
+            else:
+                x = int(value)
+                if not -(1 << 127) <= x < (1 << 127):
+                    raise ValueError(f"aggregate_hashed: having {j}: {x} is no 128-bit integer")
+                terms[j].kind = AGGV_INT
+                terms[j].lo, terms[j].hi = x & (2**64 - 1), (x >> 64) & (2**64 - 1)
+        sel = GroupSelect(having=terms, nhaving=len(having or ()), order_agg=GROUP_ORDER_NONE, limit=limit or 0)
+        if order_by is not None:
+            ob = tuple(order_by) if isinstance(order_by, (tuple, list)) else (order_by,)
+            if (not 1 <= len(ob) <= 3 or (len(ob) > 1 and ob[1] not in ("asc", "desc"))
+                    or (len(ob) > 2 and ob[2] != "nulls_first")):
+                raise ValueError(f"aggregate_hashed: order_by {order_by!r} is not agg_index, (agg_index, "
+                                 '"asc" | "desc") or (agg_index, "asc" | "desc", "nulls_first")')
+            sel.order_agg = ob[0]
+            sel.desc = int(len(ob) > 1 and ob[1] == "desc")
+            sel.nulls_first = int(len(ob) > 2)
+        return sel, terms
+
+    def aggregate_hashed(self, keys, aggs, max_groups: int, filt=None, rg_begin=0, rg_end=None, having=None,
+                         order_by=None, limit=None) -> HashGroups:
         """GROUP BY keys (1 to 4 integer-like columns of any cardinality up to
         max_groups) of the aggregates aggregate() takes, except FLOAT / DOUBLE
         sums, in a hash table in HBM (fls_aggregate_hashed): the call for
@@ -1223,25 +1284,43 @@ class Table:
         holds at most 63 bits.  FlsError with code ERR_LIMIT when one
         pipeline's row groups hold more than max_groups distinct keys among
         the selected rows: call again with a larger max_groups (each pipeline
-        allocates the next power of two >= 2 * max_groups slots)."""
+        allocates the next power of two >= 2 * max_groups slots).
+        having / order_by / limit choose among the groups on the GPU
+        (fls_aggregate_hashed_select), so that only the chosen ones come back:
+        having is a list of (agg_index, op, value), all of which must hold,
+        op one of "=", "!=", "<", "<=", ">", ">=", value an int of up to 128
+        bits, or a float against a FLOAT / DOUBLE MIN / MAX (a NULL aggregate
+        satisfies no term); order_by is agg_index, (agg_index, "desc" | "asc")
+        or (agg_index, "desc" | "asc", "nulls_first") and needs a limit of 1
+        to 1024; ties go to the smaller first row, NULLs last by default; a
+        limit alone gives the first groups by first row.  With an order_by or
+        a limit the HashGroups and its to_list() are in result order.  With
+        all three None the plain call is made."""
         if rg_end is None:
             rg_end = self.nrowgroups
         karr = (C.c_uint32 * max(1, len(keys)))(*keys[:max(1, len(keys))])
         arr, exprs = _agg_specs(aggs)
         res = _P()
+        select = having is not None or order_by is not None or limit is not None
+        if select:
+            sel, terms = self._group_select(having, order_by, limit)
         self.set_filter(filt)
         try:
             if exprs:
                 self.set_aggregate_exprs(exprs)
-            _check(_lib.fls_aggregate_hashed(self.h, karr, len(keys), arr, len(aggs), max_groups, rg_begin, rg_end,
-                                             C.byref(res)))
+            if select:
+                _check(_lib.fls_aggregate_hashed_select(self.h, karr, len(keys), arr, len(aggs), max_groups,
+                                                        C.byref(sel), rg_begin, rg_end, C.byref(res)))
+            else:
+                _check(_lib.fls_aggregate_hashed(self.h, karr, len(keys), arr, len(aggs), max_groups, rg_begin,
+                                                 rg_end, C.byref(res)))
         finally:
             _check(_lib.fls_scan_filter(self.h, None, 0))
             if exprs:
                 self.set_aggregate_exprs(None)
         try:
             signed = [self.column(k).type in (INT8, INT16, INT32, INT64, DATE, DECIMAL) for k in keys]
-            return HashGroups(res, signed, len(aggs))
+            return HashGroups(res, signed, len(aggs), in_result_order=order_by is not None or bool(limit))
         finally:
             _lib.fls_hash_result_free(res)
 

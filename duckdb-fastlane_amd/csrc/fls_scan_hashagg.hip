@@ -1,5 +1,6 @@
 // fls_scan_hashagg.hip -- the host half of the hash aggregate pushdown:
-// fls_aggregate_hashed (kernels: fls_hashagg.hip).
+// fls_aggregate_hashed and fls_aggregate_hashed_select (kernels: fls_hashagg.hip,
+// fls_hashsel.hip).
 //
 // Per call: the argument checks, the packed key's layout from the zone maps,
 // one table in HBM per pipeline (owned by the call, zeroed before the scan
@@ -9,7 +10,20 @@
 // Per batch (called by fill_batch for Reduce::HashAggregate): the descriptors
 // and the launch on the slot's stream; a batch leaves nothing to copy back but
 // the error word.
+//
+// The two entry points share hash_check, hash_scan and hash_unpack.  With a
+// selection (HAVING terms, ORDER BY one aggregate, LIMIT) and ONE pipeline
+// holding groups, the groups are chosen where they lie: group_select_kernel,
+// the top-k where an order or a limit is set, group_gather_kernel, and only the
+// chosen groups are copied and unpacked.  With SEVERAL pipelines holding
+// groups a key may straddle shards, so neither HAVING nor the order can be
+// decided per pipeline: everything is extracted and merged as in the plain
+// call, and the same selection then runs on the host with the kernels' own
+// comparators (fls_hashsel.hpp); the result is identical and
+// fls_hash_result_select_stats reports on_device = 0.  The plain call never
+// touches the selection's kernels.
 #include "fls_engine.hpp"
+#include "fls_hashsel.hpp"
 
 using namespace fls;
 using namespace fls::engine;
@@ -71,6 +85,10 @@ struct fls_hash_result {
     std::vector<Agg> aggs;
     uint64_t table_bytes = 0;  // of one pipeline's table
     double scan_ms = 0, extract_ms = 0, merge_ms = 0;
+    // the selection (fls_aggregate_hashed_select): groups formed, groups after HAVING and before LIMIT
+    uint64_t groups_total = 0, groups_passed = 0;
+    int on_device = 0;
+    double select_ms = 0;
 };
 
 namespace {
@@ -130,14 +148,34 @@ int hash_key_layout(const fls_table *t, const std::vector<uint32_t> &keys, uint3
     return 0;
 }
 
-}  // namespace
+// What the two entry points share of one call.
+struct HashCall {
+    fls_table *t = nullptr;
+    uint32_t nkeys = 0, n = 0, rg0 = 0, rg1 = 0;
+    uint64_t max_groups = 0;
+    std::vector<uint32_t> hk;
+    std::vector<HostAgg> ha;
+    HashPlan H;
+    std::vector<uint8_t> fop;               // per field of a slot: how the merge combines it (FieldOp)
+    std::vector<DevBuf<uint64_t>> tables;   // per pipeline; none without a row group to read
+    std::unique_ptr<fls_hash_result> res;
+};
 
-extern "C" {
-
-int fls_aggregate_hashed(fls_table *t, const uint32_t *keys, uint32_t nkeys, const fls_aggregate_spec *aggs, uint32_t n,
-                         uint64_t max_groups, uint32_t rg_begin, uint32_t rg_end, fls_hash_result **out) {
+// Part 1: the argument checks, the packed key's layout, the slots' fields and
+// an empty result.  No device work.
+int hash_check(fls_table *t, const uint32_t *keys, uint32_t nkeys, const fls_aggregate_spec *aggs, uint32_t n,
+               uint64_t max_groups, uint32_t rg_begin, uint32_t rg_end, fls_hash_result **out, HashCall &c) {
     if (!t || !out || (!keys && nkeys) || !aggs) return fail(FLS_ERR_ARG, "fls_aggregate_hashed: NULL argument");
     *out = nullptr;
+    c.t = t;
+    c.nkeys = nkeys;
+    c.n = n;
+    c.rg0 = rg_begin;
+    c.rg1 = rg_end;
+    c.max_groups = max_groups;
+    HashPlan &H = c.H;
+    std::vector<HostAgg> &ha = c.ha;
+    std::vector<uint8_t> &fop = c.fop;
     if (nkeys == 0 || nkeys > kMaxKeys)
         return fail(FLS_ERR_ARG, "fls_aggregate_hashed: %u keys (1 to %u per call)", nkeys, kMaxKeys);
     if (max_groups == 0 || max_groups > kMaxHashGroups)
@@ -145,7 +183,8 @@ int fls_aggregate_hashed(fls_table *t, const uint32_t *keys, uint32_t nkeys, con
                     (unsigned long long)kMaxHashGroups);
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
     if (int rc = check_rowgroup_range(t, rg_begin, rg_end, "")) return rc;
-    std::vector<uint32_t> hk(keys, keys + nkeys);
+    std::vector<uint32_t> &hk = c.hk;
+    hk.assign(keys, keys + nkeys);
     for (uint32_t q = 0; q < nkeys; ++q) {
         const uint32_t c = hk[q];
         if (c & FLS_KEY_MAPPED)
@@ -164,16 +203,14 @@ int fls_aggregate_hashed(fls_table *t, const uint32_t *keys, uint32_t nkeys, con
             return fail(FLS_ERR_ARG, "key %u: a DECIMAL wider than 64 bits (column %u) cannot be a hash aggregate's key",
                         q, c);
     }
-    HashPlan H;
     if (int rc = hash_key_layout(t, hk, rg_begin, rg_end, H)) return rc;
-    std::vector<HostAgg> ha;
     if (int rc = check_aggregates(t, "fls_aggregate_hashed", aggs, n, rg_begin, rg_end, ha)) return rc;
     for (uint32_t i = 0; i < n; ++i)
         if (ha[i].fn == AGG_SUM && agg_is_float(t, ha[i]))
             return fail(FLS_ERR_ARG, "aggregate %u: SUM of FLOAT / DOUBLE column %u is order-dependent under atomic "
                         "accumulation and is refused; fls_aggregate_grouped sums it reproducibly", i, ha[i].col);
     // the slots' fields: keys, first rows, then per aggregate what it needs
-    std::vector<uint8_t> fop = {F_KEY, F_MAX};
+    fop = {F_KEY, F_MAX};
     H.fields.assign(n, DevHashFields{0, 0, 0, 0});
     for (uint32_t i = 0; i < n; ++i) {
         const uint8_t fn = ha[i].fn;
@@ -194,18 +231,29 @@ int fls_aggregate_hashed(fls_table *t, const uint32_t *keys, uint32_t nkeys, con
         const char *e = getenv("FLS_HASHAGG_COMBINE");
         H.combine = e && *e ? atoi(e) != 0 : true;
     }
-    auto res = std::make_unique<fls_hash_result>();
-    res->key_values.resize(nkeys);
-    res->key_null.resize(nkeys);
-    res->aggs.resize(n);
+    c.res = std::make_unique<fls_hash_result>();
+    c.res->key_values.resize(nkeys);
+    c.res->key_null.resize(nkeys);
+    c.res->aggs.resize(n);
+    c.res->table_bytes = hash_table_words(H.cap, H.nfields) * 8;
+    return 0;
+}
+
+// Part 2: the tables, the reducing scan into them, and the drain of its streams.
+int hash_scan(HashCall &c) {
+    fls_table *t = c.t;
+    HashPlan &H = c.H;
+    const uint64_t max_groups = c.max_groups;
+    const uint32_t rg_begin = c.rg0, rg_end = c.rg1;
+    std::vector<DevBuf<uint64_t>> &tables = c.tables;
+    fls_hash_result *res = c.res.get();
     const uint64_t words = hash_table_words(H.cap, H.nfields);
-    res->table_bytes = words * 8;
     // Is there a row group to read?  (scan_setup prunes the same way; without
     // one the scan below does no device work and no table is needed)
     std::vector<uint32_t> rgs;
     select_rowgroups(t, t->filter, nullptr, 0, rg_begin, rg_end, rgs);
     const size_t G = t->devices.size();
-    std::vector<DevBuf<uint64_t>> tables(rgs.empty() ? 0 : G);
+    tables = std::vector<DevBuf<uint64_t>>(rgs.empty() ? 0 : G);
     for (size_t g = 0; g < tables.size(); ++g) {
         hipError_t e = hipSetDevice(t->devices[g]);
         if (e == hipSuccess) e = tables[g].alloc(t->devices[g], words);
@@ -222,8 +270,8 @@ int fls_aggregate_hashed(fls_table *t, const uint32_t *keys, uint32_t nkeys, con
     ScanPlan plan;
     plan.rg0 = rg_begin;
     plan.rg1 = rg_end;
-    plan.aggs = &ha;
-    plan.keys = &hk;
+    plan.aggs = &c.ha;
+    plan.keys = &c.hk;
     plan.max_groups = max_groups;
     plan.hash = &H;
     ScanCtx &s = t->scan;
@@ -235,22 +283,39 @@ int fls_aggregate_hashed(fls_table *t, const uint32_t *keys, uint32_t nkeys, con
         for (auto &d : s.devs)
             if (d) d->sync();
     res->scan_ms = ms_since(t0);
-    if (rc) return rc;
-    // per pipeline: the occupied slots, compacted on the device, in one D2H
-    t0 = Clock::now();
-    std::vector<std::vector<uint64_t>> raw(tables.size());
-    std::vector<uint64_t> ng(tables.size(), 0);
+    return rc;
+}
+
+// Pipeline g of the call's scan and the groups its table holds.
+int hash_pipeline(HashCall &c, size_t g, ScanDev *&dev, uint64_t &ngroups) {
+    fls_table *t = c.t;
+    ScanCtx &s = t->scan;
+    if (g >= s.devs.size() || !s.devs[g] || s.devs[g]->dev != t->devices[g])
+        return fail(FLS_ERR_STATE, "internal: hash aggregate pipeline %u not found", (uint32_t)g);
+    ScanDev &d = *s.devs[g];
+    HIP_TRY(hipSetDevice(d.dev));
+    uint64_t hdr = 0;
+    HIP_TRY(hipMemcpy(&hdr, c.tables[g].p, sizeof(hdr), hipMemcpyDeviceToHost));
+    if (hdr > c.max_groups)  // (the device flag fails the batch's acquire first)
+        return fail(FLS_ERR_LIMIT, "hash aggregate: more than max_groups = %llu distinct keys",
+                    (unsigned long long)c.max_groups);
+    dev = &d;
+    ngroups = hdr;
+    return 0;
+}
+
+// Per pipeline: the occupied slots, compacted on the device, in one D2H
+// (field-major: raw[g][f * ng[g] + i]).
+int hash_extract_all(HashCall &c, std::vector<std::vector<uint64_t>> &raw, std::vector<uint64_t> &ng) {
+    const HashPlan &H = c.H;
+    std::vector<DevBuf<uint64_t>> &tables = c.tables;
+    raw.assign(tables.size(), {});
+    ng.assign(tables.size(), 0);
     for (size_t g = 0; g < tables.size(); ++g) {
-        if (g >= s.devs.size() || !s.devs[g] || s.devs[g]->dev != t->devices[g])
-            return fail(FLS_ERR_STATE, "internal: hash aggregate pipeline %u not found", (uint32_t)g);
-        ScanDev &d = *s.devs[g];
-        HIP_TRY(hipSetDevice(d.dev));
+        ScanDev *dp = nullptr;
+        if (int rc = hash_pipeline(c, g, dp, ng[g])) return rc;
+        ScanDev &d = *dp;
         uint64_t hdr[2] = {0, 0};
-        HIP_TRY(hipMemcpy(hdr, tables[g].p, sizeof(hdr), hipMemcpyDeviceToHost));
-        if (hdr[0] > max_groups)  // (the device flag fails the batch's acquire first)
-            return fail(FLS_ERR_LIMIT, "hash aggregate: more than max_groups = %llu distinct keys",
-                        (unsigned long long)max_groups);
-        ng[g] = hdr[0];
         if (ng[g] == 0) continue;
         DevBuf<uint64_t> dense;
         if (dense.alloc(d.dev, ng[g] * H.nfields) != hipSuccess) {
@@ -267,19 +332,24 @@ int fls_aggregate_hashed(fls_table *t, const uint32_t *keys, uint32_t nkeys, con
             return fail(FLS_ERR_STATE, "internal: hash aggregate extracted %llu of %llu groups",
                         (unsigned long long)hdr[1], (unsigned long long)ng[g]);
     }
-    res->extract_ms = ms_since(t0);
-    t0 = Clock::now();
-    // the pipelines' groups by packed key: a key may straddle a shard boundary
+    return 0;
+}
+
+// The pipelines' groups by packed key -- a key may straddle a shard boundary --
+// as one field-major array F[f * mg + i]: a pipeline's own where only one
+// holds groups, else `merged`.
+void hash_merge(const HashCall &c, std::vector<std::vector<uint64_t>> &raw, const std::vector<uint64_t> &ng,
+                std::vector<uint64_t> &merged, const uint64_t *&F, uint64_t &mg) {
+    const std::vector<uint8_t> &fop = c.fop;
+    const uint32_t nf = c.H.nfields;
+    mg = 0;
+    F = nullptr;
     size_t with = 0, only = 0;
     for (size_t g = 0; g < raw.size(); ++g)
         if (ng[g]) {
             with++;
             only = g;
         }
-    const uint32_t nf = H.nfields;
-    std::vector<uint64_t> merged;   // field-major like a pipeline's: [f * mg + i]
-    uint64_t mg = 0;
-    const uint64_t *F = nullptr;
     if (with == 1) {
         F = raw[only].data();
         mg = ng[only];
@@ -322,9 +392,18 @@ int fls_aggregate_hashed(fls_table *t, const uint32_t *keys, uint32_t nkeys, con
             for (uint32_t f = 0; f < nf; ++f) merged[(uint64_t)f * mg + i] = rows[i * nf + f];
         F = merged.data();
     }
+}
+
+// Part 3: a field-major array of mg groups (F[f * mg + i]) into the result's
+// arrays, the fields as the caller sees them.
+void hash_unpack(HashCall &c, const uint64_t *F, uint64_t mg) {
+    const fls_table *t = c.t;
+    const HashPlan &H = c.H;
+    const std::vector<HostAgg> &ha = c.ha;
+    const uint32_t nkeys = c.nkeys, n = c.n;
+    fls_hash_result *res = c.res.get();
     static const uint64_t no_group = 0;
     if (!F) F = &no_group;  // (mg == 0: nothing is read)
-    // the fields as the caller sees them
     res->ngroups = mg;
     res->first_rows.resize(mg);
     for (uint64_t i = 0; i < mg; ++i) res->first_rows[i] = ~F[(uint64_t)kHashFieldFirst * mg + i];
@@ -382,8 +461,290 @@ int fls_aggregate_hashed(fls_table *t, const uint32_t *keys, uint32_t nkeys, con
             }
         }
     }
+}
+
+// ---- the selection among the groups (fls_hashsel.hpp)
+
+bool is_sum_fn(uint8_t fn) { return fn == AGG_SUM || fn == AGG_SUM_PRODUCT || fn == AGG_SUM_EXPR; }
+
+// Term `op` against a constant above (side > 0) or below every value the field can hold.
+uint8_t out_of_range_mode(uint8_t op, int side) {
+    if (op == FLS_CMP_EQ) return HV_NEVER;
+    if (op == FLS_CMP_NE) return HV_ALWAYS;
+    const bool less = op == FLS_CMP_LT || op == FLS_CMP_LE;
+    return (side > 0) == less ? HV_ALWAYS : HV_NEVER;
+}
+
+uint8_t mirrored(uint8_t op) {
+    switch (op) {
+    case FLS_CMP_LT: return FLS_CMP_GT;
+    case FLS_CMP_LE: return FLS_CMP_GE;
+    case FLS_CMP_GT: return FLS_CMP_LT;
+    case FLS_CMP_GE: return FLS_CMP_LE;
+    default: return op;
+    }
+}
+
+// The checks of a fls_group_select and its translation into the fields'
+// stored form.  k: the limit (0: none); active: anything is selected at all.
+int select_check(const HashCall &c, const fls_group_select *sel, DevGroupSelect &p, uint32_t &k, bool &active) {
+    const fls_table *t = c.t;
+    memset(&p, 0, sizeof(p));
+    k = 0;
+    active = false;
+    if (!sel) return 0;
+    if (sel->nhaving > kMaxHaving)
+        return fail(FLS_ERR_ARG, "having %u: %u terms (at most %u per call)", kMaxHaving, sel->nhaving, kMaxHaving);
+    if (sel->nhaving && !sel->having) return fail(FLS_ERR_ARG, "having 0: NULL terms");
+    for (uint32_t j = 0; j < sel->nhaving; ++j) {
+        const fls_group_having &h = sel->having[j];
+        if (h.agg >= c.n) return fail(FLS_ERR_ARG, "having %u: aggregate %u out of range (%u aggregates)", j, h.agg, c.n);
+        if (h.op > FLS_CMP_GE)
+            return fail(FLS_ERR_ARG, "having %u: op %u (FLS_CMP_EQ .. FLS_CMP_GE only)", j, (uint32_t)h.op);
+        const HostAgg &a = c.ha[h.agg];
+        const DevHashFields &fl = c.H.fields[h.agg];
+        const bool minmax = a.fn == AGG_MIN || a.fn == AGG_MAX;
+        const bool flt = minmax && agg_is_float(t, a);
+        if (h.kind != (flt ? FLS_AGGV_DOUBLE : FLS_AGGV_INT))
+            return fail(FLS_ERR_ARG, "having %u: a constant of kind %u against aggregate %u, whose values are of kind "
+                        "%s", j, (uint32_t)h.kind, h.agg, flt ? "FLS_AGGV_DOUBLE" : "FLS_AGGV_INT");
+        DevHaving &d = p.having[j];
+        d.op = h.op;
+        d.hi = kNoField;
+        const bool neg = (h.hi >> 63) != 0;
+        if (a.fn <= AGG_COUNT) {            // an unsigned 64-bit count, never NULL
+            d.val = fl.count;
+            d.null_cnt = kNoField;
+            d.mode = h.hi == 0 ? HV_U64 : out_of_range_mode(h.op, neg ? -1 : 1);
+            d.clo = h.lo;
+        } else if (is_sum_fn(a.fn)) {       // the 128-bit pair as it is
+            d.val = fl.lo;
+            d.hi = fl.hi;
+            d.null_cnt = fl.count;
+            d.mode = HV_S128;
+            d.clo = h.lo;
+            d.chi = h.hi;
+        } else {                            // MAX: the order key; MIN: its complement
+            d.val = fl.lo;
+            d.null_cnt = fl.count;
+            d.mode = HV_U64;
+            uint64_t key = 0;
+            if (flt) {
+                key = agg_key_float(as_double(h.lo));
+            } else if (type_is_signed(t->meta.cols[a.col].type)) {
+                if (h.hi != ((h.lo >> 63) ? ~0ull : 0ull)) d.mode = out_of_range_mode(h.op, neg ? -1 : 1);
+                key = agg_key_int((int64_t)h.lo);
+            } else {
+                if (h.hi != 0) d.mode = out_of_range_mode(h.op, neg ? -1 : 1);
+                key = h.lo;
+            }
+            d.clo = a.fn == AGG_MIN ? ~key : key;
+            if (a.fn == AGG_MIN) d.op = mirrored(h.op);
+        }
+    }
+    p.nhaving = sel->nhaving;
+    const bool ordered = sel->order_agg != FLS_GROUP_ORDER_NONE;
+    if (ordered && sel->order_agg >= c.n)
+        return fail(FLS_ERR_ARG, "order: aggregate %u out of range (%u aggregates)", sel->order_agg, c.n);
+    if (sel->limit > kMaxGroupLimit)
+        return fail(FLS_ERR_ARG, "order: limit %u (at most %u)", sel->limit, kMaxGroupLimit);
+    if (ordered && sel->limit == 0)
+        return fail(FLS_ERR_ARG, "order: an order needs a limit of 1 to %u (no call sorts all the groups)",
+                    kMaxGroupLimit);
+    p.oval = p.ohi = p.onull = kNoField;
+    p.oform = OF_NONE;
+    if (ordered) {
+        const HostAgg &a = c.ha[sel->order_agg];
+        const DevHashFields &fl = c.H.fields[sel->order_agg];
+        if (a.fn <= AGG_COUNT) {
+            p.oform = OF_U64;
+            p.oval = fl.count;
+        } else {
+            p.oform = is_sum_fn(a.fn) ? OF_S128 : a.fn == AGG_MIN ? OF_NOT64 : OF_U64;
+            p.oval = fl.lo;
+            p.ohi = is_sum_fn(a.fn) ? fl.hi : kNoField;
+            p.onull = fl.count;
+        }
+        p.desc = sel->desc ? 1 : 0;
+        p.nulls_first = sel->nulls_first ? 1 : 0;
+    }
+    k = sel->limit;
+    p.want_recs = (ordered || k) ? 1 : 0;
+    active = p.nhaving || ordered || k;
+    return 0;
+}
+
+template <class T>
+int select_alloc(DevBuf<T> &b, int dev, uint64_t count, const char *what) {
+    if (b.alloc(dev, count) == hipSuccess) return 0;
+    (void)hipGetLastError();
+    return fail(FLS_ERR_DEVICE, "hash aggregate: no buffer of %llu bytes for %s on GPU %d",
+                (unsigned long long)(count * sizeof(T)), what, dev);
+}
+
+// One pipeline holds the groups: select, top-k, gather on its stream; only
+// the chosen groups are copied (chosen[f * nout + i], in result order).
+int select_on_device(HashCall &c, size_t g, ScanDev &d, uint64_t ngroups, const DevGroupSelect &p, uint32_t k,
+                     std::vector<uint64_t> &chosen, uint64_t &nout, uint64_t &passed, double &select_ms) {
+    const HashPlan &H = c.H;
+    uint64_t *table = c.tables[g].p;
+    auto t0 = Clock::now();
+    HIP_TRY(hipSetDevice(d.dev));
+    HIP_TRY(hipMemsetAsync(table + kHashHdrSelected, 0, 8, d.stream));
+    DevBuf<uint32_t> slots;
+    DevBuf<GroupRec> recs, la, lb, best;
+    if (p.want_recs) {
+        if (int rc = select_alloc(recs, d.dev, ngroups, "the candidates")) return rc;
+    } else {
+        if (int rc = select_alloc(slots, d.dev, ngroups, "the selected slots")) return rc;
+    }
+    HIP_TRY(launch_group_select(p, table, H.cap, slots.p, recs.p, ngroups, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    HIP_TRY(hipMemcpy(&passed, table + kHashHdrSelected, 8, hipMemcpyDeviceToHost));
+    if (passed > ngroups)
+        return fail(FLS_ERR_STATE, "internal: hash aggregate selected %llu of %llu groups", (unsigned long long)passed,
+                    (unsigned long long)ngroups);
+    nout = passed;
+    if (p.want_recs && passed) {
+        nout = std::min<uint64_t>(passed, k);
+        const uint64_t lists = (passed + 1023) / 1024;
+        if (int rc = select_alloc(best, d.dev, nout, "the best groups")) return rc;
+        if (lists > 1) {
+            if (int rc = select_alloc(la, d.dev, lists * k, "the top-k lists")) return rc;
+            if (int rc = select_alloc(lb, d.dev, (lists + 1) / 2 * k, "the top-k lists")) return rc;
+        }
+        HIP_TRY(launch_group_topk(recs.p, passed, k, la.p, lb.p, best.p, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+    }
+    select_ms = ms_since(t0);
+    chosen.clear();
+    if (nout == 0) return 0;
+    DevBuf<uint64_t> dense;
+    if (int rc = select_alloc(dense, d.dev, nout * H.nfields, "the groups")) return rc;
+    HIP_TRY(launch_group_gather(table, H.cap, H.nfields, p.want_recs ? nullptr : slots.p, best.p, nout, dense.p,
+                                d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    chosen.resize(nout * H.nfields);
+    HIP_TRY(hipMemcpy(chosen.data(), dense.p, chosen.size() * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Several pipelines hold groups: the same selection over the merged groups
+// F[f * mg + i], with the kernels' own comparators (fls_hashsel.hpp).
+void select_on_host(const DevGroupSelect &p, uint32_t k, const uint64_t *F, uint64_t mg, uint32_t nf,
+                    std::vector<uint64_t> &chosen, uint64_t &nout, uint64_t &passed) {
+    std::vector<uint64_t> idx;
+    std::vector<GroupRec> recs;
+    for (uint64_t i = 0; i < mg; ++i) {
+        auto get = [&](uint32_t f) { return F[(uint64_t)f * mg + i]; };
+        if (!having_all(p, get)) continue;
+        idx.push_back(i);
+        if (!p.want_recs) continue;
+        GroupRec r;
+        order_key(p, get, r);
+        r.first = ~get(kHashFieldFirst);
+        r.slot = 0;
+        recs.push_back(r);
+    }
+    passed = idx.size();
+    nout = passed;
+    if (p.want_recs) {
+        nout = std::min<uint64_t>(passed, k);
+        std::vector<uint64_t> perm(passed);
+        for (uint64_t i = 0; i < passed; ++i) perm[i] = i;
+        std::partial_sort(perm.begin(), perm.begin() + nout, perm.end(),
+                          [&](uint64_t a, uint64_t b) { return rec_less(recs[a], recs[b]); });
+        std::vector<uint64_t> best(nout);
+        for (uint64_t i = 0; i < nout; ++i) best[i] = idx[perm[i]];
+        idx.swap(best);
+    }
+    chosen.resize(nout * nf);
+    for (uint32_t f = 0; f < nf; ++f)
+        for (uint64_t i = 0; i < nout; ++i) chosen[(uint64_t)f * nout + i] = F[(uint64_t)f * mg + idx[i]];
+}
+
+int hash_aggregate(fls_table *t, const uint32_t *keys, uint32_t nkeys, const fls_aggregate_spec *aggs, uint32_t n,
+                   uint64_t max_groups, const fls_group_select *sel, uint32_t rg_begin, uint32_t rg_end,
+                   fls_hash_result **out) {
+    HashCall c;
+    if (int rc = hash_check(t, keys, nkeys, aggs, n, max_groups, rg_begin, rg_end, out, c)) return rc;
+    DevGroupSelect p;
+    uint32_t k = 0;
+    bool active = false;
+    if (int rc = select_check(c, sel, p, k, active)) return rc;
+    if (int rc = hash_scan(c)) return rc;
+    fls_hash_result *res = c.res.get();
+    auto t0 = Clock::now();
+    std::vector<std::vector<uint64_t>> raw;
+    std::vector<uint64_t> ng, chosen;
+    uint64_t nout = 0;
+    if (active) {   // one pipeline holding groups decides on the device
+        std::vector<ScanDev *> devs(c.tables.size(), nullptr);
+        ng.assign(c.tables.size(), 0);
+        size_t with = 0, only = 0;
+        for (size_t g = 0; g < c.tables.size(); ++g) {
+            if (int rc = hash_pipeline(c, g, devs[g], ng[g])) return rc;
+            if (ng[g]) {
+                with++;
+                only = g;
+            }
+        }
+        if (with == 1) {
+            if (int rc = select_on_device(c, only, *devs[only], ng[only], p, k, chosen, nout, res->groups_passed,
+                                          res->select_ms))
+                return rc;
+            res->groups_total = ng[only];
+            res->on_device = 1;
+        }
+    }
+    if (!res->on_device)
+        if (int rc = hash_extract_all(c, raw, ng)) return rc;
+    res->extract_ms = ms_since(t0);
+    t0 = Clock::now();
+    if (res->on_device) {
+        hash_unpack(c, chosen.data(), nout);
+    } else {
+        std::vector<uint64_t> merged;
+        const uint64_t *F = nullptr;
+        uint64_t mg = 0;
+        hash_merge(c, raw, ng, merged, F, mg);
+        res->groups_total = res->groups_passed = mg;
+        if (active && mg) {   // a key may straddle shards: only the merged value decides
+            auto ts = Clock::now();
+            select_on_host(p, k, F, mg, c.H.nfields, chosen, nout, res->groups_passed);
+            res->select_ms = ms_since(ts);
+            F = chosen.data();
+            mg = nout;
+        }
+        hash_unpack(c, F, mg);
+    }
     res->merge_ms = ms_since(t0);
-    *out = res.release();
+    *out = c.res.release();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fls_aggregate_hashed(fls_table *t, const uint32_t *keys, uint32_t nkeys, const fls_aggregate_spec *aggs, uint32_t n,
+                         uint64_t max_groups, uint32_t rg_begin, uint32_t rg_end, fls_hash_result **out) {
+    return hash_aggregate(t, keys, nkeys, aggs, n, max_groups, nullptr, rg_begin, rg_end, out);
+}
+
+int fls_aggregate_hashed_select(fls_table *t, const uint32_t *keys, uint32_t nkeys, const fls_aggregate_spec *aggs,
+                                uint32_t n, uint64_t max_groups, const fls_group_select *sel, uint32_t rg_begin,
+                                uint32_t rg_end, fls_hash_result **out) {
+    return hash_aggregate(t, keys, nkeys, aggs, n, max_groups, sel, rg_begin, rg_end, out);
+}
+
+int fls_hash_result_select_stats(const fls_hash_result *r, uint64_t *groups_total, uint64_t *groups_passed,
+                                 int *on_device, double *select_ms) {
+    if (!r) return fail(FLS_ERR_ARG, "fls_hash_result_select_stats: NULL argument");
+    if (groups_total) *groups_total = r->groups_total;
+    if (groups_passed) *groups_passed = r->groups_passed;
+    if (on_device) *on_device = r->on_device;
+    if (select_ms) *select_ms = r->select_ms;
     return 0;
 }
 

@@ -453,6 +453,72 @@ int fls_hash_result_aggregate(const fls_hash_result *r, uint32_t agg, const uint
 int fls_hash_result_stats(const fls_hash_result *r, uint64_t *table_bytes, double *scan_ms, double *extract_ms,
                           double *merge_ms);
 void fls_hash_result_free(fls_hash_result *r);
+/* fls_aggregate_hashed that returns only the groups a query wants: HAVING
+ * (Q18: sum(l_quantity) > 300) and ORDER BY one aggregate LIMIT k (Q3: the ten
+ * largest revenues), chosen in HBM where the scan left the groups, so that
+ * only the chosen groups are compacted, copied and unpacked
+ * (csrc/fls_hashsel.hip).  Keys, aggregates, filter, pruning, max_groups,
+ * FLS_ERR_LIMIT and the "no row group to read" case are fls_aggregate_hashed's,
+ * with the same checks and messages; sel == NULL, or a sel with no term, no
+ * order and no limit, returns exactly what fls_aggregate_hashed returns.
+ * HAVING: a group passes when every one of the nhaving (0 .. 8) terms
+ * "aggregate[agg] op constant" holds.  An aggregate of kind FLS_AGGV_INT
+ * (counts, integer sums, integer MIN / MAX) compares as a signed 128-bit
+ * integer with the constant lo / hi (a UINT64 MIN / MAX zero-extended); a
+ * FLOAT / DOUBLE MIN / MAX compares with the binary64 constant in lo in the
+ * filter's float order: NaN equals NaN and sits above every number, -0 equals
+ * 0.  A NULL aggregate (SUM / MIN / MAX with count 0) satisfies no term,
+ * FLS_CMP_NE included.  The comparison runs on the fields as the table stores
+ * them; the constant is translated once, and one outside what the field can
+ * hold makes its term hold always or never.
+ * ORDER BY / LIMIT: the result order is (NULL placement, the aggregate's
+ * value, the group's first row); NULLs come last unless nulls_first, whether
+ * ascending or descending; NaN is the largest value.  First rows are distinct
+ * across groups, so no two groups compare equal and the list is unique.  With
+ * an order, limit must be 1 .. 1024 and the result holds the best
+ * min(limit, passed) groups in result order.  With FLS_GROUP_ORDER_NONE and
+ * limit > 0 it holds the first `limit` passing groups by first row.  With
+ * neither, the passing groups come in unspecified order.
+ * Everything returned is identical whatever the batch size, slot count or
+ * number of pipelines, and equals the plain call's groups with the same
+ * selection applied on the host.  The selection runs on the GPU when one
+ * pipeline holds the groups.  When several do, a key may straddle shards and
+ * only its merged value can decide: all groups are extracted and merged as in
+ * the plain call and the same selection, with the same comparators, runs on
+ * the host (on_device = 0).
+ * FLS_ERR_ARG before any device work, naming "having j:": nhaving > 8, an
+ * aggregate index >= n, an op outside FLS_CMP_EQ .. FLS_CMP_GE, a constant
+ * kind that is not the aggregate's; naming "order:": an aggregate index >= n,
+ * an order without a limit, a limit above 1024.  FLS_ERR_LIMIT,
+ * FLS_ERR_DEVICE and FLS_ERR_FORMAT as in the plain call; the fls_table stays
+ * usable after each.
+ * select_stats: groups_total the groups formed, groups_passed the groups after
+ * HAVING and before LIMIT, on_device whether the selection ran on the GPU,
+ * select_ms its time on the host clock (any pointer may be NULL); on a result
+ * of the plain call total = passed = ngroups and on_device = 0.
+ * Not in the reference. */
+typedef struct fls_group_having {   /* aggregate[agg] <op> constant */
+    uint32_t agg;                   /* index into aggs[] */
+    uint8_t  op;                    /* FLS_CMP_EQ .. FLS_CMP_GE only */
+    uint8_t  kind;                  /* FLS_AGGV_INT: lo/hi a 128-bit two's-complement constant;
+                                       FLS_AGGV_DOUBLE: binary64 bits in lo */
+    uint8_t  pad[2];
+    uint64_t lo, hi;
+} fls_group_having;
+#define FLS_GROUP_ORDER_NONE 0xFFFFFFFFu
+typedef struct fls_group_select {
+    const fls_group_having *having; /* conjunction of nhaving terms, 0 .. 8 */
+    uint32_t nhaving;
+    uint32_t order_agg;             /* index into aggs[], or FLS_GROUP_ORDER_NONE */
+    uint8_t  desc, nulls_first, pad[2];
+    uint32_t limit;                 /* 0 = no limit; else 1 .. 1024 */
+} fls_group_select;
+int fls_aggregate_hashed_select(fls_table *t, const uint32_t *keys, uint32_t nkeys,
+                                const fls_aggregate_spec *aggs, uint32_t n, uint64_t max_groups,
+                                const fls_group_select *sel,
+                                uint32_t rg_begin, uint32_t rg_end, fls_hash_result **out);
+int fls_hash_result_select_stats(const fls_hash_result *r, uint64_t *groups_total,
+                                 uint64_t *groups_passed, int *on_device, double *select_ms);
 
 /* Key maps: GROUP BY an attribute of a joined dimension table.  A key map is
  * a function from 64-bit keys to 16-bit codes, built on the host from the
