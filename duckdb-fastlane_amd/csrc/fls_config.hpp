@@ -7,7 +7,8 @@
 // for FLS_IDLE_PINNED_MB after the code moved to 1024).
 //
 // The other FLS_* variables in csrc/ are A/B-measurement and test hooks, not
-// deployment settings, and stay where they are read.
+// deployment settings: the decode launch's in one struct read once per decode
+// call (fls_tuning.hpp), the others where they are read.
 #pragma once
 #include <cstdint>
 #include <cstdlib>

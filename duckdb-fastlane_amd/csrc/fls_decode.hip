@@ -47,6 +47,7 @@
 #include "fls_alp.hpp"
 #include "fls_decode.hpp"
 #include "fls_format.hpp"
+#include "fls_tuning.hpp"
 #include "fls_unpack.hpp"
 
 #include "fls_decode_dev.hpp"
@@ -178,7 +179,7 @@ int decode_grid_size(uint32_t shmem_per_block) {
     const int cus = device_cus();
     int per_cu = occupancy(reinterpret_cast<const void *>(decode_kernel<false>), 64 * kWaves, shmem_per_block);
     // A/B knob: blocks per CU below what the occupancy query reports
-    if (const char *e = getenv("FLS_BLOCKS_PER_CU")) per_cu = std::min(per_cu, std::max(1, atoi(e)));
+    if (const int cap = blocks_per_cu_cap()) per_cu = std::min(per_cu, cap);
     return cus * std::max(1, per_cu);
 }
 

@@ -142,6 +142,7 @@ struct FsstLaunch {
     uint32_t *queue = nullptr;    // piece counter (overlapped launches); nullptr: contiguous ranges
     bool reset_queue = true;      // zero it first (false: drain a queue another launch started)
     int waves_per_cu = 0;         // grid: 0 = as many as fit, else at most this many per CU
+    uint32_t piece = 0;           // vectors per queue piece: 0 = by launch size (FLS_FSST_PIECE)
     int grid_cus = 0;             // grid: the CUs it may run on (a CU-masked stream); 0 = all
     int variant = kFsstDefault;   // code-parallel kernel variant (kFsst* bits; FLS_FSST_VARIANT)
     bool seg = false;             // the chunks carry segment tables (DevChunk.vbits bit 1): segmented kernel

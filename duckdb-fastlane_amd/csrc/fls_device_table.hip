@@ -1,6 +1,6 @@
 // fls_device_table.hip -- device-resident mode (fls_device_*): a table's row
 // groups uploaded verbatim to HBM, one part per GPU, and decoded there by one
-// launch per pass (launch_all, flsgpu.hip); the decoded columns stay on the
+// launch per pass (launch_all, fls_launch.hip); the decoded columns stay on the
 // device.  The benchmark's kernel roofline runs on this path.  Also the plain
 // device-memory helpers of the C ABI (fls_device_count / alloc / free / memcpy).
 #include "fls_engine.hpp"
@@ -308,8 +308,8 @@ int upload_part(fls_table *t, Resident &r) {
 int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask) {
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
     HIP_TRY(hipSetDevice(r.dev));
-    const int64_t policy = decode_policy();
-    if (mask != r.mask || !r.list_built || policy != r.policy) {
+    const DecodeTuning tuning = read_decode_tuning();
+    if (mask != r.mask || !r.list_built || tuning.list != r.list_key) {
         // (re)build the launch descriptor list: column-major task order, so
         // concurrent waves stream one column's consecutive row groups
         std::vector<DevChunk> chunks;
@@ -323,13 +323,14 @@ int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask) {
                 uint8_t *out = r.d_out[c].p + (t->meta.rgs[g].first_row - r.first_row) * out_bytes_of(t, c);
                 const uint64_t ho = r.heap_off[(size_t)(g - r.rg0) * ncols + c];
                 chunks.push_back(make_devchunk(t, g, c, r.img.p + (ch.off - r.base), dict, out, &bc,
-                                               r.d_heap[c].p ? r.d_heap[c].p + ho : nullptr,
+                                               tuning.launch.fsst_seg, r.d_heap[c].p ? r.d_heap[c].p + ho : nullptr,
                                                r.h_heap[c].p ? r.h_heap[c].p + ho : nullptr));
             }
         }
-        const int64_t lpol = launch_policy(policy, chunks, bc.geom);
+        r.list_key = tuning.list;
+        r.tuning = launch_policy(tuning, chunks, bc.geom);
         std::vector<DevChunk> dictwg;
-        r.nmain = order_for_launch(chunks, &r.fsst, lpol, &dictwg);
+        r.nmain = order_for_launch(chunks, &r.fsst, r.tuning, &dictwg);
         // one DictVec per vector of the chunks the dictionary-string grid takes,
         // from the host image's VecMeta arrays (validated when the file was read)
         std::vector<DictVec> dvecs;
@@ -349,10 +350,8 @@ int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask) {
             fprintf(stderr, "DEBUG: dictstr_decode_kernel takes %zu chunks (%zu vectors), %zu DICT VARCHAR chunks stay "
                             "on the main decode\n", dictwg.size(), dvecs.size(), kept);
         }
-        r.policy = policy;
-        r.lpolicy = lpol;
         const size_t k = chunks.size();
-        r.split = append_split(chunks, r.nmain, bc.geom, lpol);
+        r.split = append_split(chunks, r.nmain, bc.geom, r.tuning);
         HIP_TRY(hipStreamSynchronize(r.stream));
         HIP_TRY(r.d_chunks.alloc(r.dev, chunks.size()));
         HIP_TRY(hipMemcpy(r.d_chunks.p, chunks.data(), chunks.size() * sizeof(DevChunk), hipMemcpyHostToDevice));
@@ -380,13 +379,14 @@ int decode_part(fls_table *t, Resident &r, const std::vector<uint8_t> &mask) {
         HIP_TRY(hipEventCreateWithFlags(&r.side.fork, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&r.side.join, hipEventDisableTiming));
     }
+    r.tuning.launch = tuning.launch;
     if (r.fsst.total_vecs() > 0)
-        if (const int rc = fsst_config_check(r.lpolicy)) return rc;
+        if (const int rc = fsst_config_check(r.tuning)) return rc;
     hipEvent_t e0 = r.ev_pool[r.ev_used], e1 = r.ev_pool[r.ev_used + 1];
     r.ev_used += 2;
     HIP_TRY(hipEventRecord(e0, r.stream));
     HIP_TRY(launch_all(r.d_chunks.p, r.nmain, (uint32_t)r.h_chunks.size(), r.fsst, r.err.p, r.bytes.geom, r.stream,
-                       r.queue.p, r.lpolicy, r.split, &r.side, r.d_dictvecs.p, r.ndictvecs));
+                       r.queue.p, r.tuning, r.split, &r.side, r.d_dictvecs.p, r.ndictvecs));
     HIP_TRY(hipEventRecord(e1, r.stream));
     return 0;
 }

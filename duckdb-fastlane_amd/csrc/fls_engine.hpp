@@ -1,8 +1,11 @@
 // fls_engine.hpp -- the host engine's internal types and the functions its
 // units call across files.  Not part of the C ABI (include/flsgpu.h).
 //
-//   flsgpu.hip            connections, files, the launch policy and the scan
-//                         pipeline (scan_setup, fill_batch, scan_acquire ...)
+//   flsgpu.hip            connections, files and the scan pipeline
+//                         (scan_setup, fill_batch, scan_acquire ...)
+//   fls_launch.hip        the launch policy and the launches of one decode
+//                         (launch_policy, order_for_launch, launch_all), over
+//                         the hooks of fls_tuning.hpp
 //   fls_scan_agg.hip      fls_aggregate / fls_aggregate_grouped: checks,
 //                         per-batch enqueue, the host fold
 //   fls_scan_hashagg.hip  fls_aggregate_hashed: checks, the key layout, the
@@ -16,7 +19,7 @@
 //   fls_device_table.hip  the device-resident table (fls_device_*)
 //
 // The pushdown and device-table units depend on flsgpu.hip's scan pipeline and
-// launch helpers; flsgpu.hip depends on them only through the four enqueue_*
+// fls_launch.hip's launches; flsgpu.hip depends on them only through the four enqueue_*
 // functions fill_batch switches over, keyset_registry() and, for mapped GROUP
 // BY keys, enqueue_keymap, binding_may_match and keymap_registry().  Every function
 // and registry declared here is defined in exactly one unit.
@@ -57,6 +60,7 @@
 #include "fls_reader.hpp"
 #include "fls_resident.hpp"
 #include "fls_topn.hpp"
+#include "fls_tuning.hpp"
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -690,14 +694,14 @@ struct Resident {
     uint32_t nmain = 0;                // h_chunks[0, nmain) main kernel, the rest FSST
     DevBuf<DictVec> d_dictvecs;        // the dictionary-string grid's vectors (launch_dictstr), built with h_chunks
     uint32_t ndictvecs = 0;            // ... and how many (their chunks are not in h_chunks)
-    bool list_built = false;           // h_chunks / d_dictvecs describe the current mask, policy and outputs
-    void invalidate() {                // a new mask, policy or set of outputs: rebuild both at the next decode
+    bool list_built = false;           // h_chunks / d_dictvecs describe the current mask, list_key and outputs
+    void invalidate() {                // a new mask, list key or set of outputs: rebuild both at the next decode
         h_chunks.clear();
         ndictvecs = 0;
         list_built = false;
     }
-    int64_t policy = -1;               // decode_policy() h_chunks was ordered for
-    int64_t lpolicy = 0;                // ... and the launch policy it resolved to (launch_policy)
+    DecodeTuning::List list_key;       // the hooks h_chunks was ordered for (read_decode_tuning)
+    DecodeTuning tuning;               // ... resolved for its launch (launch_policy); .launch anew at every decode
     FsstCounts fsst;                   // FSST chunks of h_chunks
     SplitPlan split;                   // balanced split after h_chunks on the device (waves 0: none)
     ByteCount bytes;                   // algorithmic bytes of one launch
@@ -766,22 +770,23 @@ int check_rowgroup_range(const fls_table *t, uint32_t rg0, uint32_t rg1, const c
 int build_strtabs(const fls_table *t, int dev, uint32_t rg0, uint32_t rg1, DevBuf<StrT> &tab,
                   std::vector<uint64_t> &offs, std::vector<StrT> &host);
 DevChunk make_devchunk(const fls_table *t, uint32_t rg, uint32_t col, const uint8_t *d_chunk, const uint8_t *d_dict,
-                       uint8_t *d_out, ByteCount *bc, uint8_t *d_heap = nullptr, const uint8_t *h_heap = nullptr,
-                       uint32_t code_w = 0, const uint8_t *d_ident = nullptr);
+                       uint8_t *d_out, ByteCount *bc, bool fsst_seg, uint8_t *d_heap = nullptr,
+                       const uint8_t *h_heap = nullptr, uint32_t code_w = 0, const uint8_t *d_ident = nullptr);
 
-// ---- launch policy and launches (flsgpu.hip) ---------------------------------
+// ---- launch policy and launches (fls_launch.hip) -----------------------------
+// tn: the decode call's hooks (read_decode_tuning, fls_tuning.hpp), after
+// launch_policy with the distribution resolved for the launch.
 
 constexpr uint32_t kQueueWords = 1 + kFsstGroups;  // launch_all's d_queue
-int64_t decode_policy();
-int64_t launch_policy(int64_t policy, const std::vector<DevChunk> &v, DecodeGeom &geom);
-uint32_t order_for_launch(std::vector<DevChunk> &v, FsstCounts *fc, int64_t policy,
+DecodeTuning launch_policy(DecodeTuning tn, const std::vector<DevChunk> &v, DecodeGeom &geom);
+uint32_t order_for_launch(std::vector<DevChunk> &v, FsstCounts *fc, const DecodeTuning &tn,
                           std::vector<DevChunk> *dictwg = nullptr);
-SplitPlan append_split(std::vector<DevChunk> &list, uint32_t nmain, const DecodeGeom &geom, int64_t policy);
-int fsst_config_check(int64_t policy);
+SplitPlan append_split(std::vector<DevChunk> &list, uint32_t nmain, const DecodeGeom &geom, const DecodeTuning &tn);
+int fsst_config_check(const DecodeTuning &tn);
 hipError_t launch_all(const DevChunk *d_chunks, uint32_t nmain, uint32_t ntotal, const FsstCounts &fc,
-                      uint32_t *d_err, const DecodeGeom &geom, hipStream_t stream, uint32_t *d_queue, int64_t policy,
-                      SplitPlan plan, const SideStream *side = nullptr, const DictVec *d_dictvecs = nullptr,
-                      uint32_t ndictvecs = 0);
+                      uint32_t *d_err, const DecodeGeom &geom, hipStream_t stream, uint32_t *d_queue,
+                      const DecodeTuning &tn, SplitPlan plan, const SideStream *side = nullptr,
+                      const DictVec *d_dictvecs = nullptr, uint32_t ndictvecs = 0);
 
 // ---- the scan pipeline (flsgpu.hip) -------------------------------------------
 

@@ -1237,12 +1237,11 @@ hipError_t launch_kind(const DevChunk *d_chunks, uint32_t nchunks, uint32_t nvec
     int cus = device_cus(), per_cu = occupancy(reinterpret_cast<const void *>(kern), 64, shmem);
     if (how.grid_cus > 0) cus = std::min(cus, how.grid_cus);   // a CU-masked stream
     const int full = cus * std::max(1, per_cu);
-    int wpc = how.waves_per_cu;
-    if (const char *e = getenv("FLS_FSST_WPC"); e && wpc == 0) wpc = std::max(0, atoi(e));  // A/B knob (standalone launches)
+    const int wpc = how.waves_per_cu;
     const int grid = std::min<int>(wpc > 0 ? cus * std::min(wpc, per_cu) : full, (int)nvecs);
     // overlapped: pieces of ~1/4 of a wave's share of a full grid, <= 16 vectors
     uint32_t piece = std::max<uint32_t>(1, std::min<uint32_t>(16, nvecs / (4u * (uint32_t)full)));
-    if (const char *e = getenv("FLS_FSST_PIECE")) piece = (uint32_t)std::max(1, std::min(64, atoi(e)));  // A/B knob
+    if (how.piece) piece = how.piece;  // A/B knob
     if (how.queue && how.reset_queue) {
         const hipError_t e = hipMemsetAsync(how.queue, 0, sizeof(uint32_t), stream);
         if (e != hipSuccess) return e;

@@ -7,12 +7,12 @@
 //   * streaming scan: row groups sharded contiguously over the connection's
 //     GPUs (no collectives: row groups are independent); per
 //     GPU a two-slot pipeline H2D(compressed batch) -> decode -> D2H(pinned)
-//     runs ahead of the consumer (DuckDB's scan thread);
-//   * the launch policy every decode goes through (order_for_launch,
-//     launch_all), a scan's batches and a device-resident table alike.
+//     runs ahead of the consumer (DuckDB's scan thread).
 //
 // The rest of the engine is in units of its own, over the types and
-// declarations of fls_engine.hpp: what a scan does with a batch instead of
+// declarations of fls_engine.hpp: the launch policy every decode goes through
+// (order_for_launch, launch_all), a scan's batches and a device-resident table
+// alike, in fls_launch.hip, what a scan does with a batch instead of
 // delivering it (ScanCtx::reduce) in fls_scan_agg.hip and fls_scan_topn.hip,
 // key sets in fls_scan_keyset.hip, key maps and the mapped GROUP BY keys'
 // probe in fls_scan_keymap.hip, and the device-resident mode (a shard of
@@ -379,9 +379,11 @@ int build_strtabs(const fls_table *t, int dev, uint32_t rg0, uint32_t rg1, DevBu
 // Describe chunk (rg, col) located at d_chunk_base (device) for the kernel.
 // code_w (1 or 2): a DICT string chunk delivered as its codes, gathered from
 // the identity table d_ident instead of the string_t dictionary
+// fsst_seg (DecodeTuning::Launch::fsst_seg): FSST chunks with segment tables
+// for the segmented kernel
 DevChunk make_devchunk(const fls_table *t, uint32_t rg, uint32_t col, const uint8_t *d_chunk, const uint8_t *d_dict,
-                       uint8_t *d_out, ByteCount *bc, uint8_t *d_heap, const uint8_t *h_heap, uint32_t code_w,
-                       const uint8_t *d_ident) {
+                       uint8_t *d_out, ByteCount *bc, bool fsst_seg, uint8_t *d_heap, const uint8_t *h_heap,
+                       uint32_t code_w, const uint8_t *d_ident) {
     const ChunkRef &ch = t->meta.rgs[rg].chunks[col];
     const ChunkHeader &h = ch.hdr;
     DevChunk d;
@@ -429,11 +431,10 @@ DevChunk make_devchunk(const fls_table *t, uint32_t rg, uint32_t col, const uint
         // the code-parallel one, an A/B knob)
         // and symbols of at most 7 bytes (the segmented kernel stages each
         // symbol with its length in the top byte)
-        const char *sg = getenv("FLS_FSST_SEG");
         bool short_syms = true;
         const uint8_t *lens = t->img + ch.off + h.aux_off + 8 * 256;
         for (uint32_t k = 0; k < h.dict_count && k < 255; ++k) short_syms &= lens[k] <= 7;
-        const bool seg = chunk_seg_codes(h) == kFsstSegCodes && short_syms && !(sg && atoi(sg) == 0);
+        const bool seg = chunk_seg_codes(h) == kFsstSegCodes && short_syms && fsst_seg;
         d.vbits = (sp ? 1 : 0) | (seg ? 2 : 0);
         return d;  // separate kernels, fixed LDS layouts
     }
@@ -463,492 +464,6 @@ DevChunk make_devchunk(const fls_table *t, uint32_t rg, uint32_t col, const uint
 static bool col_selected(const std::vector<uint8_t> &mask, uint32_t c) { return mask.empty() || mask[c]; }
 
 bool is_fsst(const fls_table *t, uint32_t rg, uint32_t c) { return t->meta.rgs[rg].chunks[c].hdr.enc == ENC_FSST; }
-
-// Decode work distribution (A/B knob FLS_DECODE_POLICY, read per call so both
-// arms run on the same buffers): 0 = work queue, largest chunks first
-// (default); bit 0 = static grid-stride split; bit 1 = keep column order.
-// bit 2 = full-width register prefetch for every chunk (descriptor max_w = T).
-// bit 3 = FSST chunks with segment tables on the code-parallel kernel
-// (FLS_FSST_SEG=0) instead of the segmented one.
-// bit 4 = FSST rounds of 16 compressed bytes per lane instead of 8.
-// bit 5 = balanced static split of vectors over the resident waves, chunks in
-// file (row-group-major) order (balanced_split).  bit 6 = work queue even for
-// small launches (launch_policy).  bit 7 = FSST chunks whose strings are all
-// <= 255 bytes on the string-parallel kernel (default: every FSST chunk on the
-// code-parallel kernel; same-buffer A/B profiles/r1/abenv_fsst_cp.txt).
-enum : int {
-    POLICY_STATIC = 1, POLICY_NO_LPT = 2, POLICY_FULL_PREFETCH = 4, POLICY_FSST_NOSEG = 8, POLICY_FSST16 = 16,
-    POLICY_BALANCED = 32, POLICY_QUEUE = 64, POLICY_FSST_SP = 128
-};
-// Balanced-split knobs, folded into the policy word (so a change rebuilds the
-// cached launch list): FLS_STATIC_PCT = % of the bytes split statically
-// (bits 8-15, default 100), FLS_TAIL_PIECES = tail pieces per wave for the
-// rest (bits 16-23, default 2), FLS_BLOCKS_PER_CU (bits 24-30, 0 = unset).
-// Guided tail defaults (FLS_GUIDED_MIN_VECS / FLS_GUIDED_FACTOR, guided_split)
-constexpr int kGuidedMinVecs = 0, kGuidedFactor = 2;
-// The dictionary-string grid (fls_dictstr.hip): FLS_DICT_WG = 0 keeps every
-// chunk on the main decode, 1 (default) moves the eligible DICT VARCHAR
-// chunks of a table decode to their own grid when they hold at least
-// FLS_DICT_WG_MIN_VECS_PER_CU vectors per CU, 2 moves them whatever the size.
-// Below the threshold the second launch's drain outweighs the write rate
-// (lineitem_full, full step, grid forced against off: +3.9 % at 11 vectors per
-// CU, +1.4 % at 23, -1.2 % at 46, -1.5 % at 92, -4.2 % at 183;
-// profiles/r7/abenv_dictwg_small.txt).  FLS_DICT_WG_STREAMS: the grid's write
-// streams (order_for_launch).
-struct DictWgCfg {
-    int mode = 1;
-    uint32_t min_vecs_per_cu = 64;
-    uint32_t streams = 4;
-};
-static DictWgCfg dict_wg_cfg() {
-    DictWgCfg c;
-    if (const char *e = getenv("FLS_DICT_WG")) c.mode = std::min(2, std::max(0, atoi(e)));
-    if (const char *e = getenv("FLS_DICT_WG_MIN_VECS_PER_CU")) c.min_vecs_per_cu = (uint32_t)std::min(255, std::max(0, atoi(e)));
-    if (const char *e = getenv("FLS_DICT_WG_STREAMS")) c.streams = (uint32_t)std::min(31, std::max(1, atoi(e)));
-    return c;
-}
-int64_t decode_policy() {
-    const char *e = getenv("FLS_DECODE_POLICY");
-    const char *sp = getenv("FLS_STATIC_PCT");
-    const char *tp = getenv("FLS_TAIL_PIECES");
-    const int pct = sp ? std::min(100, std::max(0, atoi(sp))) : 100;
-    const int pieces = tp ? std::min(255, std::max(1, atoi(tp))) : 2;
-    // FLS_BLOCKS_PER_CU (decode_grid_size) only enters the grid when the
-    // launch list is rebuilt: fold it in so a change rebuilds it
-    const char *bp = getenv("FLS_BLOCKS_PER_CU");
-    const int bpc = bp ? std::min(127, std::max(0, atoi(bp))) : 0;
-    // FLS_FSST_SEG=0 (make_devchunk: FSST chunks with segment tables go to the
-    // code-parallel kernel) changes the descriptors: fold it in too
-    const char *sg = getenv("FLS_FSST_SEG");
-    const int noseg = sg && atoi(sg) == 0 ? POLICY_FSST_NOSEG : 0;
-    // guided tail (guided_split): FLS_GUIDED_MIN_VECS = smallest piece in
-    // vectors (bits 32-39, 0 = whole chunks only), FLS_GUIDED_FACTOR = pieces
-    // per wave of the remaining work (bits 40-47)
-    const char *gm = getenv("FLS_GUIDED_MIN_VECS");
-    const char *gf = getenv("FLS_GUIDED_FACTOR");
-    const int64_t gmin = gm ? std::min(64, std::max(0, atoi(gm))) : kGuidedMinVecs;
-    const int64_t gfac = gf ? std::min(255, std::max(1, atoi(gf))) : kGuidedFactor;
-    // the dictionary-string grid (FLS_DICT_WG, bits 48-49) and its size
-    // threshold (FLS_DICT_WG_MIN_VECS_PER_CU, bits 50-57) move chunks between
-    // the two launch lists, its write streams (FLS_DICT_WG_STREAMS, bits
-    // 58-62) order its own
-    const DictWgCfg dw = dict_wg_cfg();
-    return (int64_t)(((e ? (atoi(e) & 0xFF) : 0) | noseg) | pct << 8 | pieces << 16 | bpc << 24) | gmin << 32 |
-           gfac << 40 | (int64_t)dw.mode << 48 | (int64_t)dw.min_vecs_per_cu << 50 | (int64_t)dw.streams << 58;
-}
-
-// Policy for one launch: the default (no distribution bits) switches to the
-// balanced split when the launch has fewer main-kernel chunks than resident
-// waves (the scan pipeline's 8-row-group batches: ~120 chunks for ~4,096
-// waves), where whole-chunk work items would leave most waves idle.  Large
-// launches keep the work queue: same-buffer A/B on SF100 lineitem, c3 and c4
-// found the split no faster than the queue (profiles/r1/abenv_bal_*.txt).
-int64_t launch_policy(int64_t policy, const std::vector<DevChunk> &v, DecodeGeom &geom) {
-    if (policy & (POLICY_STATIC | POLICY_BALANCED | POLICY_QUEUE)) return policy;
-    size_t nmain = 0;
-    for (const DevChunk &d : v) nmain += d.enc != ENC_FSST;
-    if (geom.grid <= 0) geom.grid = decode_grid_size(4 * (geom.p_bytes + geom.v_bytes));
-    return nmain < decode_waves(geom) ? (policy | POLICY_BALANCED) : policy;
-}
-
-// FSST chunks go last (their own kernels: string-parallel ones first, then
-// code-parallel ones, each group numbering its vectors through vec_base);
-// returns how many lead (main kernel) and the FSST counts
-// dictwg (a table decode, decode_part): the chunks the dictionary-string grid
-// takes (dictstr_eligible, FLS_DICT_WG) leave v for it, in the order its
-// workgroups are laid out in: ascending output address, as S interleaved
-// streams (below).
-uint32_t order_for_launch(std::vector<DevChunk> &v, FsstCounts *fc, int64_t policy,
-                          std::vector<DevChunk> *dictwg) {
-    if (dictwg) {
-        dictwg->clear();
-        const int mode = (int)((policy >> 48) & 3);
-        uint64_t vecs = 0;
-        for (const DevChunk &d : v)
-            if (dictstr_eligible(d)) vecs += d.nvec;
-        const uint64_t need = mode == 2 ? 1 : (uint64_t)((policy >> 50) & 0xFF) * (uint64_t)device_cus();
-        if (mode > 0 && vecs > 0 && vecs >= need && vecs <= UINT32_MAX) {
-            auto rest = std::stable_partition(v.begin(), v.end(), [](const DevChunk &d) { return !dictstr_eligible(d); });
-            dictwg->assign(rest, v.end());
-            v.erase(rest, v.end());
-            std::stable_sort(dictwg->begin(), dictwg->end(),
-                             [](const DevChunk &a, const DevChunk &b) { return a.out < b.out; });
-            // S write streams (FLS_DICT_WG_STREAMS): the sorted list cut into
-            // S runs of as many chunks, taken round-robin, so S regions fill
-            // at once, each in ascending address.  lineitem_full SF100, the
-            // four string columns: S = 1 / 2 / 4 / 8 -> 6.90 / 5.96 / 5.72 /
-            // 5.74 ms (S = 4: one stream per column); one ascending sequence
-            // over several buffers is no faster than the main decode there
-            // (6.87 ms).  c4: 2.56 / 2.50 / 2.50 / 2.51 ms
-            // (profiles/r7/abenv_dictwg_streams_*.txt)
-            const size_t n = dictwg->size(), S = std::min<size_t>(std::max<size_t>(1, (size_t)((policy >> 58) & 31)), n);
-            if (S > 1) {
-                std::vector<DevChunk> il;
-                il.reserve(n);
-                for (size_t i = 0; il.size() < n; ++i)
-                    for (size_t s = 0; s < S; ++s)
-                        if (s * n / S + i < (s + 1) * n / S) il.push_back((*dictwg)[s * n / S + i]);
-                dictwg->swap(il);
-            }
-        }
-    }
-    auto mid = std::stable_partition(v.begin(), v.end(), [](const DevChunk &d) { return d.enc != ENC_FSST; });
-    std::stable_sort(mid, v.end(), [](const DevChunk &a, const DevChunk &b) {
-        return fsst_group(a.vbits) < fsst_group(b.vbits);
-    });
-    if (policy & POLICY_FULL_PREFETCH)
-        for (auto it = v.begin(); it != mid; ++it) it->max_w = it->T;
-    if (policy & POLICY_BALANCED) {
-        // file order = row-group-major: every wave's range mixes all columns
-        // (paths that run slower per byte are spread over the waves)
-        std::stable_sort(v.begin(), mid, [](const DevChunk &a, const DevChunk &b) { return a.chunk < b.chunk; });
-    } else if (!(policy & (POLICY_STATIC | POLICY_NO_LPT))) {
-        // largest output first: the work queue then ends the launch on small chunks
-        std::stable_sort(v.begin(), mid, [](const DevChunk &a, const DevChunk &b) {
-            return (uint64_t)a.nvec * a.ob > (uint64_t)b.nvec * b.ob;
-        });
-    }
-    *fc = FsstCounts();
-    for (auto it = mid; it != v.end(); ++it) {
-        const int g = fsst_group(it->vbits);
-        it->vec_base = fc->vecs[g];
-        fc->vecs[g] += it->nvec;
-        fc->n[g]++;
-    }
-    return (uint32_t)(mid - v.begin());
-}
-
-// Append the balanced split of the main chunks to the descriptor list (as
-// extra DevChunk slots, so it uploads with it); plan.waves == 0 when the
-// policy does not split.
-SplitPlan append_split(std::vector<DevChunk> &list, uint32_t nmain, const DecodeGeom &geom, int64_t policy) {
-    if (nmain == 0) return SplitPlan();
-    std::vector<uint32_t> pos;
-    SplitPlan plan;
-    if (policy & POLICY_BALANCED)
-        plan = balanced_split(list.data(), nmain, decode_waves(geom), (policy >> 8) & 0xFF, (policy >> 16) & 0xFF, pos);
-    else if (!(policy & (POLICY_STATIC | POLICY_NO_LPT)) && ((policy >> 32) & 0xFF))
-        plan = guided_split(list.data(), nmain, decode_waves(geom), (uint32_t)((policy >> 40) & 0xFF),
-                            (uint32_t)((policy >> 32) & 0xFF), pos);
-    else
-        return SplitPlan();
-    const size_t k = list.size();
-    list.resize(k + (pos.size() * 4 + sizeof(DevChunk) - 1) / sizeof(DevChunk));
-    memcpy(list.data() + k, pos.data(), pos.size() * 4);
-    return plan;
-}
-
-// Overlap split (launch_all): blocks per CU of the narrow main decode grid
-// and FSST waves per CU of the narrow FSST grid; knobs FLS_OVERLAP_DECODE_BPC /
-// FLS_OVERLAP_FSST_WPC (0 FSST waves = no overlap).
-// Overlap vs one-after-the-other at the per-GPU shares of 1/2/4/8-GPU runs
-// (same-buffer A/B on lineitem_full, profiles/r2/abenv_overlap_scales.txt,
-// abenv_sf12p5.txt, abenv_minvecs.txt, abenv_overlap_grid.txt,
-// abenv_overlap_prio.txt): overlapped is faster at SF25 (5.90 vs 6.26 ms),
-// SF50 (12.0 vs 12.9) and SF100 (23.1 vs 26.0, 23.9 vs 26.4); at SF12.5 (286
-// FSST vectors per CU, the per-GPU share of an 8-GPU run) serial was faster on
-// three boxes of four (3.41 vs 3.46, 3.11 vs 3.18, 3.36 vs 3.45 ms; 3.16 vs
-// 3.09 on the fourth).  So launches with fewer than 400 FSST vectors per CU
-// ran serially (FLS_OVERLAP_MIN_VECS_PER_CU).  With round 3's faster FSST
-// kernel serial also wins at SF25 (572 vectors per CU: 6.41 vs 6.51 ms) and
-// at SF12.5 against every split tried (3.22 vs 3.34-3.45 ms;
-// profiles/r3/abenv_sf25_split_r3zl.txt, abenv_sf12_split_r3zl.txt), so the
-// threshold is 800; SF50 (1,144 vectors per CU) and SF100 (2,288) stay
-// overlapped: 11.17 vs 11.82 and 22.14 vs 23.80 ms (abenv_sf50_split_r3zm.txt,
-// abenv_sf100_split_r3zm.txt).  The main kernel's wave issue
-// priority while overlapped (FLS_OVERLAP_DECODE_PRIO, s_setprio 1-3) measured
-// within 0.1 % of the default.
-struct OverlapSplit {
-    // 12 FSST waves per CU beside 1 decode block: 1.6-2 % faster than 16 at
-    // SF100 and SF12.5 (profiles/r2/abenv_v12.txt)
-    int decode_bpc = 1, fsst_wpc = 12;
-    uint32_t min_vecs_per_cu = 800;
-    int decode_prio = 0;  // FLS_OVERLAP_DECODE_PRIO: s_setprio of the main kernel's waves while overlapped
-    // FLS_OVERLAP_CU_SPLIT = m in 1..31: the main decode starts on the CUs whose
-    // index mod 32 is < m, FSST on the others, each kind alone on its CUs
-    // (0 = the co-resident split above)
-    int cu_split = 0;
-    // FLS_OVERLAP_GUIDED=1: the overlapped decode grids drain the guided plan's
-    // items (whole chunks, then pieces) instead of whole chunks
-    bool guided = false;
-};
-static OverlapSplit overlap_split() {
-    OverlapSplit o;
-    if (const char *e = getenv("FLS_OVERLAP_CU_SPLIT")) o.cu_split = std::min(31, std::max(0, atoi(e)));
-    if (const char *e = getenv("FLS_OVERLAP_DECODE_BPC")) o.decode_bpc = std::max(1, atoi(e));
-    if (const char *e = getenv("FLS_OVERLAP_FSST_WPC")) o.fsst_wpc = std::max(0, atoi(e));
-    if (const char *e = getenv("FLS_OVERLAP_MIN_VECS_PER_CU")) o.min_vecs_per_cu = (uint32_t)std::max(0, atoi(e));
-    if (const char *e = getenv("FLS_OVERLAP_DECODE_PRIO")) o.decode_prio = std::min(3, std::max(0, atoi(e)));
-    if (const char *e = getenv("FLS_OVERLAP_GUIDED")) o.guided = atoi(e) != 0;
-    return o;
-}
-
-// d_queue[0] = main decode work queue, [1 + g] = FSST piece counter of kernel
-// group g (FsstCounts).
-//
-// Without a side stream (scan batches) the FSST kernels follow the main one
-// on its stream.  With one (a table decode), the FSST kernels (VALU-bound)
-// overlap the main decode kernel (HBM-bound):
-//   main stream: narrow decode grid (decode_bpc blocks per CU), then a full
-//                FSST grid;
-//   side stream: narrow FSST grid (fsst_wpc waves per CU), then a full decode
-//                grid.
-// Every grid of a kind drains one shared queue (decode chunks / FSST pieces),
-// so no work is done twice, and whichever kind runs out first, its stream
-// follows with a full grid of the other kind onto the freed wave slots.  The
-// split holds whichever kernel the hardware dispatches first.
-// Measured on lineitem_full SF100 (same-buffer A/B, profiles/r1/abenv_overlap.txt):
-// 26.7 ms serial -> 24.3 ms at 1 decode block + 12..20 FSST waves per CU
-// (2 blocks + 8..12 waves: 24.7 ms).  The kernel trace shows the overlap phase
-// moving ~4.9 TB/s together, below the 5.6 TB/s of the main kernel alone: the
-// two compete for the CUs' LDS and issue slots as well as for HBM.
-// The FSST kernels a launch with this policy and FLS_FSST_VARIANT would run
-// must be in this build: the product library holds each kernel's default only
-// (fls_fsst.hip), the experiment library every variant (make lab).  A stale
-// tuning variable fails the decode with FLS_ERR_CONFIG instead of running a
-// kernel it did not ask for.
-int fsst_config_check(int64_t policy) {
-    int variant = kFsstDefault;
-    const char *fv = getenv("FLS_FSST_VARIANT");
-    if (fv) {
-        char *end = nullptr;
-        const long v = strtol(fv, &end, 10);
-        if (end == fv || *end != 0 || v < 0 || v > 0x7FFFFFFF)
-            return fail(FLS_ERR_CONFIG, "FLS_FSST_VARIANT=%s is not a variant number", fv);
-        variant = (int)v;
-    }
-    if (const char *fx = getenv("FLS_FUSED_X")) {  // the fused kernel's FSST-part bits (experiments)
-        char *end = nullptr;
-        const long x = strtol(fx, &end, 10);
-        if (end == fx || *end != 0 || x < 0 || x > 0x7FFFFFFF || !fused_x_built((int)x))
-            return fail(FLS_ERR_CONFIG,
-                        "FLS_FUSED_X=%s is not in this build: the product library holds the default fused kernel "
-                        "only; experiments need FLS_LIB=libflsgpu_lab.so (make lab) -- unset FLS_FUSED_X",
-                        fx);
-    }
-    const int bpl = (policy & POLICY_FSST16) ? 16 : 8;
-    if (!fsst_variant_built(variant, true, bpl) || !fsst_variant_built(variant, false, bpl))
-        return fail(FLS_ERR_CONFIG,
-                    "FSST kernel variant %d (%d bytes per lane) is not in this build: the product library holds the "
-                    "default kernels only; experiments need FLS_LIB=libflsgpu_lab.so (make lab)%s",
-                    variant, bpl, fv ? " -- unset FLS_FSST_VARIANT" : "");
-    return 0;
-}
-
-// Fused launch knobs (launch_all -> launch_fused): the default for a table
-// decode whose FSST chunks are of one segmented kind; FLS_FUSED=0 turns it
-// off (serial or overlapped kernels), FLS_FUSED=1 forces it even without FSST
-// chunks (the main decode alone in the fused kernel: 2 % slower, A/B only),
-// FLS_FUSED_FSST16 = waves of every 16 that start on FSST, FLS_FUSED_PIECE =
-// FSST vectors per queue item, FLS_FUSED_WPC = waves per CU (0: as many as
-// fit), FLS_FUSED_STATIC_PCT = % of the FSST vectors the FSST-first waves
-// split statically before the queue, FLS_FUSED_MIN_VECS_PER_CU = the FSST
-// vectors per CU below which the launch stays serial.
-struct FusedCfg {
-    // 0 off; 1 (default) launches with main chunks and FSST chunks of one
-    // segmented kind; 2 (FLS_FUSED=1) also launches with only one of the two
-    int mode = 1;
-    uint32_t min_vecs_per_cu = 0;
-    bool per16_set = false;  // FLS_FUSED_FSST16 given (else by launch size, launch_all)
-    bool variant = false;    // a non-default FLS_FSST_VARIANT: no fused launch
-    FusedLaunch how;
-};
-static FusedCfg fused_cfg() {
-    FusedCfg f;
-    if (const char *e = getenv("FLS_FUSED")) f.mode = std::min(2, std::max(0, atoi(e) == 1 ? 2 : atoi(e)));
-    if (const char *e = getenv("FLS_FUSED_FSST16")) {
-        f.how.fsst_per16 = (uint32_t)std::min(16, std::max(0, atoi(e)));
-        f.per16_set = true;
-    }
-    if (const char *e = getenv("FLS_FUSED_PIECE")) f.how.piece = (uint32_t)std::min(64, std::max(1, atoi(e)));
-    if (const char *e = getenv("FLS_FUSED_WPC")) f.how.waves_per_cu = std::max(0, atoi(e));
-    if (const char *e = getenv("FLS_FUSED_STATIC_PCT")) f.how.fsst_static_pct = (uint32_t)std::min(100, std::max(0, atoi(e)));
-    if (const char *e = getenv("FLS_FUSED_STATIC_FIRST")) f.how.static_first = atoi(e) != 0;
-    if (const char *e = getenv("FLS_FUSED_HALVING")) f.how.halving = atoi(e) != 0;
-    if (const char *e = getenv("FLS_FUSED_TAIL")) f.how.tail_chunks = (uint32_t)std::max(0, atoi(e));
-    if (const char *e = getenv("FLS_FUSED_TAIL_SPLIT")) f.how.tail_split = (uint32_t)std::min(64, std::max(1, atoi(e)));
-    if (const char *e = getenv("FLS_FUSED_X")) f.how.x = atoi(e);
-    if (const char *e = getenv("FLS_FUSED_MIN_VECS_PER_CU")) f.min_vecs_per_cu = (uint32_t)std::max(0, atoi(e));
-    // an FSST kernel variant A/B (FLS_FSST_VARIANT, experiment library) runs
-    // the standalone FSST kernels: the fused kernel holds only the default's
-    // FSST part, so fusing would measure the default instead
-    if (const char *e = getenv("FLS_FSST_VARIANT"))
-        if (atoi(e) != kFsstDefault) f.variant = true;
-    return f;
-}
-
-// CU-partitioned overlap: the main decode (HBM-bound) and the FSST kernels
-// (VALU / LDS-bound) each start alone on their own CU set instead of sharing
-// every CU's LDS and issue slots (the co-resident split lost to running them
-// one after the other at the 8-GPU share, profiles/r3/abenv_sf12_split_r3zl.txt):
-//   stream A (CUs with index mod 32 < m): full decode grid, then FSST;
-//   stream B (the other CUs):             full FSST grid, then decode.
-// Both kinds drain shared queues, so whichever set finishes its kind first
-// joins the other.  A mask that takes m of every 32 CU indices gives each XCD
-// the same share whether the mask's bits run XCD by XCD or round-robin over
-// the XCDs (m a multiple of 8).
-template <class LaunchGroup>
-static hipError_t launch_cu_split(const DevChunk *d_chunks, uint32_t nmain, const FsstCounts &fc, uint32_t *d_err,
-                           const DecodeGeom &geom, hipStream_t stream, uint32_t *d_queue, SideStream *side,
-                           const OverlapSplit &ov, int cus, const FsstLaunch (&how)[kFsstGroups],
-                           LaunchGroup &launch_group) {
-    const int m = ov.cu_split;
-    uint32_t mask_a[8] = {}, mask_b[8] = {};
-    int na = 0, nb = 0;
-    for (int i = 0; i < std::min(cus, 256); ++i) {
-        if (i % 32 < m) {
-            mask_a[i / 32] |= 1u << (i % 32);
-            ++na;
-        } else {
-            mask_b[i / 32] |= 1u << (i % 32);
-            ++nb;
-        }
-    }
-    if (na == 0 || nb == 0) return hipErrorInvalidValue;
-    if (side->cu_m != m) {
-        side->release_cu();
-        hipError_t e = hipExtStreamCreateWithCUMask(&side->cu_a, 8, mask_a);
-        if (e == hipSuccess) e = hipExtStreamCreateWithCUMask(&side->cu_b, 8, mask_b);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&side->join_a, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&side->join_b, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            side->release_cu();
-            return e;
-        }
-        side->cu_m = m;
-    }
-    const uint32_t shmem = 4 * (geom.p_bytes + geom.v_bytes);
-    const int bpc = std::max(1, (geom.grid > 0 ? geom.grid : decode_grid_size(shmem)) / std::max(1, cus));
-    DecodeGeom ga = geom, gb = geom;
-    ga.grid = na * bpc;
-    gb.grid = nb * bpc;
-    FsstLaunch ha[kFsstGroups], hb[kFsstGroups];
-    for (int g = 0; g < kFsstGroups; ++g) {
-        ha[g] = hb[g] = how[g];
-        ha[g].queue = hb[g].queue = d_queue + 1 + g;
-        ha[g].reset_queue = hb[g].reset_queue = false;
-        ha[g].grid_cus = na;
-        hb[g].grid_cus = nb;
-    }
-    hipError_t e = hipMemsetAsync(d_queue, 0, kQueueWords * sizeof(uint32_t), stream);
-    if (e == hipSuccess) e = hipEventRecord(side->fork, stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(side->cu_a, side->fork, 0);
-    if (e == hipSuccess) e = hipStreamWaitEvent(side->cu_b, side->fork, 0);
-    if (e == hipSuccess)
-        e = launch_decode(d_chunks, nmain, d_err, ga, side->cu_a, d_queue, nullptr, SplitPlan(), true, ov.decode_prio);
-    for (int g = 0; g < kFsstGroups && e == hipSuccess; ++g) e = launch_group(g, side->cu_b, hb[g]);
-    if (e == hipSuccess)
-        e = launch_decode(d_chunks, nmain, d_err, gb, side->cu_b, d_queue, nullptr, SplitPlan(), true, ov.decode_prio);
-    for (int g = 0; g < kFsstGroups && e == hipSuccess; ++g) e = launch_group(g, side->cu_a, ha[g]);
-    if (e == hipSuccess) e = hipEventRecord(side->join_a, side->cu_a);
-    if (e == hipSuccess) e = hipEventRecord(side->join_b, side->cu_b);
-    if (e == hipSuccess) e = hipStreamWaitEvent(stream, side->join_a, 0);
-    if (e == hipSuccess) e = hipStreamWaitEvent(stream, side->join_b, 0);
-    return e;
-}
-
-hipError_t launch_all(const DevChunk *d_chunks, uint32_t nmain, uint32_t ntotal, const FsstCounts &fc,
-                      uint32_t *d_err, const DecodeGeom &geom, hipStream_t stream, uint32_t *d_queue, int64_t policy,
-                      SplitPlan plan, const SideStream *side, const DictVec *d_dictvecs, uint32_t ndictvecs) {
-    // the dictionary-string grid first, on the same stream: its chunks are not
-    // in d_chunks, and a launch may consist of it alone
-    if (ndictvecs) {
-        const hipError_t de = launch_dictstr(d_dictvecs, ndictvecs, d_err, stream);
-        if (de != hipSuccess || ntotal == 0) return de;
-    }
-    // a guided plan only orders the serial launch: the overlapped and
-    // CU-split launches drain whole chunks from a queue several grids share
-    const uint32_t *d_split = plan.waves ? reinterpret_cast<const uint32_t *>(d_chunks + ntotal) : nullptr;
-    const bool balanced = d_split && !plan.guided;
-    const bool sp = (policy & POLICY_FSST_SP) != 0;
-    const OverlapSplit ov = overlap_split();
-    FsstLaunch how[kFsstGroups];
-    for (int g = 0; g < kFsstGroups; ++g) {
-        how[g].bytes_per_lane = (policy & POLICY_FSST16) ? 16 : 8;
-        if (const char *fv = getenv("FLS_FSST_VARIANT")) how[g].variant = atoi(fv);  // fsst_config_check'ed
-        how[g].small = g == 0 || g == 2;
-        how[g].seg = g < 2;
-        if (const char *sc = getenv("FLS_FSST_SEG_CAP")) how[g].seg_cap = atoi(sc);
-    }
-    auto launch_group = [&](int g, hipStream_t st, const FsstLaunch &h) -> hipError_t {
-        const DevChunk *dc = d_chunks + nmain + fc.first(g);
-        if (g == 2 && sp && !h.queue) return launch_fsst_sp(dc, fc.n[g], fc.vecs[g], d_err, st);
-        return launch_fsst(dc, fc.n[g], fc.vecs[g], d_err, st, h);
-    };
-    const int cus = device_cus();
-    const uint64_t fsst_vecs = fc.total_vecs();
-    if (ov.cu_split > 0 && side && side->stream && nmain > 0 && fsst_vecs > 0 && !balanced && !sp &&
-        !(policy & POLICY_STATIC))
-        return launch_cu_split(d_chunks, nmain, fc, d_err, geom, stream, d_queue, const_cast<SideStream *>(side),
-                               ov, cus, how, launch_group);
-    // fused: one kernel pulling main chunks and FSST pieces from two queues
-    // (launch_fused), when every FSST chunk is of one segmented kind
-    {
-        const FusedCfg fz = fused_cfg();
-        int g1 = -1, ng = 0;
-        for (int g = 0; g < kFsstGroups; ++g)
-            if (fc.n[g]) {
-                g1 = g;
-                ++ng;
-            }
-        if (fz.mode > 0 && !fz.variant && ((ng == 1 && nmain > 0) || fz.mode == 2) && ng <= 1 && g1 < 2 && !balanced && !sp &&
-            !(policy & POLICY_STATIC) &&
-            fsst_vecs >= (uint64_t)fz.min_vecs_per_cu * (uint64_t)cus) {
-            const int g = std::max(0, g1);  // (no FSST chunks: the main decode alone, in the fused kernel)
-            // waves starting on FSST: 6 of 16 for large launches (SF100:
-            // 21.79 ms against 21.93 with 5), 5 below 1,000 FSST vectors per
-            // CU (SF12.5: 3.115 against 3.133 ms with 6; profiles/r5/)
-            FusedLaunch how = fz.how;
-            // With the DICT VARCHAR chunks on their own grid the main queue
-            // holds about half the bytes and the FSST part needs more of the
-            // waves: 8 of 16 (SF100: 20.57 ms against 20.91 with 6 and 20.71
-            // with 9; SF12.5: 2.704 against 2.820 with 5 and 2.714 with 6,
-            // while without the grid 7 and 8 lose to 6;
-            // profiles/r7/abenv_dictwg_fsst16_*.txt)
-            if (!fz.per16_set) how.fsst_per16 = ndictvecs ? 8u : fsst_vecs < 1000ull * (uint64_t)cus ? 5u : 6u;
-            return launch_fused(d_chunks, nmain, d_chunks + nmain + fc.first(g), fc.n[g], fc.vecs[g], g == 0, d_err,
-                                geom, stream, d_queue, how);
-        }
-    }
-    const bool overlap = side && side->stream && ov.fsst_wpc > 0 && nmain > 0 && fsst_vecs > 0 &&
-                         fsst_vecs >= (uint64_t)ov.min_vecs_per_cu * (uint64_t)cus && !balanced && !sp &&
-                         !(policy & POLICY_STATIC);
-    hipError_t e = hipSuccess;
-    if (overlap) {
-        DecodeGeom narrow = geom;
-        const uint32_t shmem = 4 * (geom.p_bytes + geom.v_bytes);
-        narrow.grid = std::min(geom.grid > 0 ? geom.grid : decode_grid_size(shmem), cus * ov.decode_bpc);
-        e = hipMemsetAsync(d_queue, 0, kQueueWords * sizeof(uint32_t), stream);
-        if (e == hipSuccess) e = hipEventRecord(side->fork, stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(side->stream, side->fork, 0);
-        FsstLaunch narrow_how[kFsstGroups];
-        for (int g = 0; g < kFsstGroups; ++g) {
-            how[g].queue = d_queue + 1 + g;
-            how[g].reset_queue = false;
-            narrow_how[g] = how[g];
-            narrow_how[g].waves_per_cu = ov.fsst_wpc;
-        }
-        // main stream: narrow decode, then full FSST
-        // (a guided plan: both decode grids drain its items from the shared queue)
-        const uint32_t *gs = d_split && plan.guided && ov.guided ? d_split : nullptr;
-        const SplitPlan gp = gs ? plan : SplitPlan();
-        if (e == hipSuccess)
-            e = launch_decode(d_chunks, nmain, d_err, narrow, stream, d_queue, gs, gp, true, ov.decode_prio);
-        // side stream: narrow FSST, then full decode
-        for (int g = 0; g < kFsstGroups && e == hipSuccess; ++g) e = launch_group(g, side->stream, narrow_how[g]);
-        if (e == hipSuccess)
-            e = launch_decode(d_chunks, nmain, d_err, geom, side->stream, d_queue, gs, gp, true, ov.decode_prio);
-        for (int g = 0; g < kFsstGroups && e == hipSuccess; ++g) e = launch_group(g, stream, how[g]);
-        if (e == hipSuccess) e = hipEventRecord(side->join, side->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(stream, side->join, 0);
-        return e;
-    }
-    e = launch_decode(d_chunks, nmain, d_err, geom, stream, (policy & POLICY_STATIC) ? nullptr : d_queue, d_split, plan);
-    // FSST groups in order; chunks whose strings are all <= 255 bytes without
-    // segment tables go to the string-parallel kernel under POLICY_FSST_SP
-    for (int g = 0; g < kFsstGroups && e == hipSuccess; ++g) e = launch_group(g, stream, how[g]);
-    return e;
-}
 
 FLS_ENGINE_END
 
@@ -1771,6 +1286,7 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     std::vector<DevChunk> list;
     ByteCount bc;
     ProfTimer plist(PROF_FILL_LIST);
+    const DecodeTuning tuning = read_decode_tuning();
     for (uint32_t c = 0; c < ncols; ++c) {
         if (!col_selected(s.dmask, c)) continue;
         for (uint32_t r = sl.rg0; r < sl.rg0 + sl.nrg; ++r) {
@@ -1779,17 +1295,17 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
             const uint8_t *dict = so == UINT64_MAX ? nullptr : (const uint8_t *)(d.strtab.p + so);
             uint8_t *out = sl.d_out[c].p + (t->meta.rgs[r].first_row - t->meta.rgs[sl.rg0].first_row) * dob[c];
             const uint64_t ho = hoff[(size_t)(r - sl.rg0) * ncols + c];
-            list.push_back(make_devchunk(t, r, c, sl.in_dev + (ch.off - lo), dict, out, &bc,
+            list.push_back(make_devchunk(t, r, c, sl.in_dev + (ch.off - lo), dict, out, &bc, tuning.launch.fsst_seg,
                                          sl.heap_bytes[c] ? sl.d_heap[c].p + ho : nullptr,
                                          sl.heap_bytes[c] ? hb.h_heap[c].p + ho : nullptr, code_w[c], d.ident.p));
         }
     }
     plist.stop();
     FsstCounts fsst;
-    const int64_t policy = launch_policy(decode_policy(), list, bc.geom);
-    const uint32_t nmain = order_for_launch(list, &fsst, policy);
+    const DecodeTuning tn = launch_policy(tuning, list, bc.geom);
+    const uint32_t nmain = order_for_launch(list, &fsst, tn);
     const size_t k = list.size();
-    const SplitPlan plan = append_split(list, nmain, bc.geom, policy);
+    const SplitPlan plan = append_split(list, nmain, bc.geom, tn);
     pdesc.stop();
     const size_t kk = list.size();
     HIP_TRY(sl.h_chunks.alloc(kk));
@@ -1804,13 +1320,12 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     HIP_TRY(hipMemcpyAsync(sl.d_chunks.p, sl.h_chunks.p, kk * sizeof(DevChunk), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(sl.queue.alloc(d.dev, kQueueWords));
     // (only batches with FSST work: a stale FLS_FSST_VARIANT must not fail
-    // integer-only scans, nor cost every refill an environment parse)
+    // integer-only scans)
     if (fsst.total_vecs() > 0)
-        if (const int rc = fsst_config_check(policy)) return rc;
+        if (const int rc = fsst_config_check(tn)) return rc;
     // (an aggregate scan of counts without a filter decodes no column)
     if (kk || !s.aggregating())
-        HIP_TRY(launch_all(sl.d_chunks.p, nmain, (uint32_t)k, fsst, d.err.p, bc.geom, sl.stream, sl.queue.p, policy,
-                           plan));
+        HIP_TRY(launch_all(sl.d_chunks.p, nmain, (uint32_t)k, fsst, d.err.p, bc.geom, sl.stream, sl.queue.p, tn, plan));
     const uint64_t rows = t->meta.rgs[sl.rg0 + sl.nrg - 1].first_row + t->meta.rgs[sl.rg0 + sl.nrg - 1].nrows -
                           t->meta.rgs[sl.rg0].first_row;
     // 2b. narrowed columns: value - base into their narrow copies

@@ -4,7 +4,8 @@ byte work -> exact equality, no tolerance."""
 import numpy as np
 import pytest
 
-from helpers import INT_TYPE, SIGNED, UNSIGNED, assert_column_equal, gpu_decode_all, width_sweep_values
+from helpers import (INT_TYPE, SIGNED, UNSIGNED, assert_column_equal, fsst_text, gpu_decode_all,
+                     width_sweep_values)
 
 pytestmark = pytest.mark.gpu
 
@@ -274,3 +275,55 @@ def test_work_distribution_policies(fl, ref, gpu, monkeypatch, env):
                           ("d", fl.INT32, (a % 7).astype(np.int32), fl.ENC_DICT)])
     _check_image(fl, ref, img)
     _check_image(fl, ref, img, [1, 2])
+
+
+# The decode hooks are read at every decode call (csrc/fls_tuning.hpp): a change
+# between two decodes of one resident table takes effect at the next decode,
+# and the cached descriptor list is rebuilt when one of the hooks that key it
+# changed.  Every step states its whole environment; each differs from the one
+# before in a keyed hook, so each must rebuild the list (the FLS_DEBUG line of
+# the rebuild) and decode bit-exactly.
+TUNING_STEPS = [
+    {},
+    {"FLS_DICT_WG": "2"},
+    {"FLS_DICT_WG": "0"},
+    {"FLS_DECODE_POLICY": "32"},
+    {"FLS_DECODE_POLICY": "1"},
+    {"FLS_DECODE_POLICY": "64", "FLS_GUIDED_MIN_VECS": "1"},
+    {"FLS_FUSED": "0"},
+    {"FLS_FUSED": "0", "FLS_FSST_SEG": "0"},
+    {},
+]
+
+
+def test_tuning_change_between_decodes(fl, ref, gpu, monkeypatch, capfd):
+    rng = np.random.default_rng(2048)
+    n = 5 * 2048 + 77   # a ragged last row group
+    a = rng.integers(-50, 50, n).astype(np.int32)
+    b = np.cumsum(rng.integers(0, 4, n)).astype(np.int64)
+    s = [["N", "O", "DELIVER IN PERSON"][i] for i in rng.integers(0, 3, n)]
+    f = [x[:29] for x in fsst_text(n, rng)]
+    img = fl.write_image([("a", fl.INT32, a, fl.ENC_FFOR), ("b", fl.INT64, b, fl.ENC_DELTA),
+                          ("r", fl.INT16, (b // 100).astype(np.int16), fl.ENC_RLE),
+                          ("s", fl.VARCHAR, s, fl.ENC_DICT), ("f", fl.VARCHAR, f, fl.ENC_FSST)], rowgroup=2048)
+    rf = ref.RefFile(img)
+    t = fl.Connection().read_image(img)
+    t.device_upload()
+    names = sorted({k for env in TUNING_STEPS for k in env})
+    monkeypatch.setenv("FLS_DEBUG", "1")
+    for step, env in enumerate(TUNING_STEPS, 1):
+        for k in names:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        capfd.readouterr()
+        t.device_decode()
+        t.device_sync()
+        err = capfd.readouterr().err
+        for c in range(t.ncols):
+            assert_column_equal(fl, rf, c, t.device_copy_out(c), img.ptr)
+        assert "DEBUG: dictstr_decode_kernel takes " in err, (step, err)   # the list was rebuilt
+        if step == 2:
+            assert "dictstr_decode_kernel takes 6 chunks" in err and "dictstr_decode_kernel:" in err, err
+        if step == 3:
+            assert "dictstr_decode_kernel takes 0 chunks" in err and "dictstr_decode_kernel:" not in err, err
