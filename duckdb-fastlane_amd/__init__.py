@@ -71,8 +71,29 @@ class Predicate(C.Structure):
 EQ, NE, LT, LE, GT, GE, IS_NULL, IS_NOT_NULL = range(8)
 OPS = {"=": EQ, "==": EQ, "!=": NE, "<>": NE, "<": LT, "<=": LE, ">": GT, ">=": GE,
        "is_null": IS_NULL, "is_not_null": IS_NOT_NULL, "false": 8,
-       "in_set": 9, "not_in_set": 10}
+       "in_set": 9, "not_in_set": 10, "like": 11, "not_like": 12}
 IN_SET, NOT_IN_SET = 9, 10
+LIKE, NOT_LIKE = 11, 12
+MAX_PATTERN_TERMS, MAX_PATTERN_TOKENS = 8, 256   # kMaxPatTerms, kMaxPatTokens
+
+
+def _pat_bytes(x, what):
+    if isinstance(x, str):
+        return x.encode()
+    if isinstance(x, (bytes, bytearray, memoryview)):
+        return bytes(x)
+    raise TypeError(f"{what}: str or bytes expected, got {type(x).__name__}")
+
+
+def like_escape(literal, escape=b"\\") -> bytes:
+    """literal with `%`, `_` and the escape byte escaped: a LIKE pattern (under
+    ESCAPE escape) that matches exactly the literal's bytes"""
+    lit, e = _pat_bytes(literal, "like_escape"), _pat_bytes(escape, "like_escape")
+    return b"".join(e + bytes([b]) if b in (0x25, 0x5F, e[0]) else bytes([b]) for b in lit)
+
+
+# (col, sugar, literal) -> the LIKE pattern around the escaped literal, ESCAPE '\'
+_LIKE_SUGAR = {"starts_with": (b"", b"%"), "ends_with": (b"%", b""), "contains": (b"%", b"%")}
 # fls_keyset_form
 KEYSET_AUTO, KEYSET_BITMAP, KEYSET_HASH = 0, 1, 2
 MAX_KEYSET_KEYS = 1 << 28          # kMaxKeysetKeys
@@ -1010,18 +1031,47 @@ class Table:
         """filt: list of (col, op, value[, clause]); op a fls_cmp or one of OPS;
         value int (integers, DATE days, DECIMAL scaled), float (FLOAT/DOUBLE) or
         str/bytes (VARCHAR), or a KeySet for "in_set" / "not_in_set" (a clause
-        of its own).  Terms without a clause get their own clause."""
+        of its own).  Terms without a clause get their own clause.
+        String patterns on a VARCHAR column (DuckDB's LIKE: `%` any bytes, `_`
+        one character, case-sensitive; a clause of their own, a NULL row
+        satisfies neither): (col, "like" / "not_like", pattern) or
+        (col, "like", (pattern, escape)) with pattern str or bytes and escape
+        one byte; a None pattern selects no row.  (col, "starts_with" /
+        "ends_with" / "contains", literal) build the LIKE pattern around the
+        literal, its `%`, `_` and `\\` escaped with `\\`."""
         sch = self.schema()
         arr = (Predicate * max(1, len(filt)))()
         keep = []
         for i, term in enumerate(filt):
             col, op, val = term[:3]
+            if isinstance(op, str) and op in _LIKE_SUGAR and val is not None:
+                pre, post = _LIKE_SUGAR[op]
+                op, val = "like", (pre + like_escape(val) + post, b"\\")
+            elif isinstance(op, str) and op in _LIKE_SUGAR:
+                op = "like"
             p = arr[i]
             p.col = col
             p.clause = term[3] if len(term) > 3 else 1000000 + i
             p.op = OPS[op] if isinstance(op, str) else op
             ty = sch[col][1] if 0 <= col < len(sch) else None
-            if p.op in (IN_SET, NOT_IN_SET):
+            if p.op in (LIKE, NOT_LIKE):
+                pat, esc = val if isinstance(val, tuple) else (val, None)
+                if pat is None:
+                    p.op = OPS["false"]   # a NULL pattern: no row
+                    continue
+                if ty not in STRING_TYPES:
+                    continue              # the engine refuses the term by name
+                b = _pat_bytes(pat, "like pattern")
+                if esc is not None:
+                    e = _pat_bytes(esc, "like escape")
+                    if len(e) != 1 or e == b"\0":
+                        raise ValueError(f"like: the escape {esc!r} is not one non-NUL byte")
+                    p.value = e[0]
+                buf = C.create_string_buffer(b, len(b) + 1)
+                keep.append(buf)
+                p.str = C.cast(buf, C.c_char_p)
+                p.str_len = len(b)
+            elif p.op in (IN_SET, NOT_IN_SET):
                 p.value = (val.h or 0) if isinstance(val, KeySet) else int(val)   # the set's handle
                 keep.append(val)
             elif val is None or ty is None:

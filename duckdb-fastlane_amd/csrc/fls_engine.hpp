@@ -59,6 +59,7 @@
 #include "fls_pinned.hpp"
 #include "fls_reader.hpp"
 #include "fls_resident.hpp"
+#include "fls_strmatch.hpp"
 #include "fls_topn.hpp"
 #include "fls_tuning.hpp"
 
@@ -337,6 +338,8 @@ struct Slot {                       // one batch of row groups in flight
     DevBuf<uint8_t> d_fdesc;
     PinBuf<DevSetTerm> h_sdesc;     // the filter's key-set terms
     DevBuf<DevSetTerm> d_sdesc;
+    PinBuf<uint8_t> h_pdesc;        // the filter's pattern terms: DevPatTerm[] + their tokens
+    DevBuf<uint8_t> d_pdesc;
     std::vector<DevBuf<uint64_t>> d_valid;  // per filtered / aggregated column with a NULL: batch validity words
     std::vector<uint8_t> valid_staged;      // per column: d_valid[c] holds this batch's words (stage_validity)
     std::vector<DevBuf<uint8_t>> d_narrow;  // per narrowed column: its narrowed copy
@@ -516,8 +519,10 @@ struct HostTerm {
     uint64_t value = 0;             // comparison domain: int64 / uint64 / double bits
     std::string str;
     std::shared_ptr<KeySet> set;    // OP_IN_SET / OP_NOT_IN_SET
+    std::shared_ptr<const CompiledPattern> pat;  // OP_LIKE / OP_NOT_LIKE
 };
 inline bool is_set_op(uint8_t op) { return op == OP_IN_SET || op == OP_NOT_IN_SET; }
+inline bool is_pat_op(uint8_t op) { return op == OP_LIKE || op == OP_NOT_LIKE; }
 
 // One aggregate of fls_aggregate, host side.
 struct HostAgg {

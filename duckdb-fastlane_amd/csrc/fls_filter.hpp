@@ -20,6 +20,10 @@
 // set`, fls_keyset.hpp): such a term is a clause of its own, pruned against
 // the zone maps by the set's sorted keys and evaluated by a kernel of its own
 // (fls_keyset.hip) that narrows the mask the filter kernel wrote.
+// A string pattern term (`column LIKE pattern` / `NOT LIKE`, fls_strmatch.hpp)
+// has the same shape: a clause of its own, pruned against the DICT
+// dictionaries by the shared matcher and evaluated by strmatch_kernel
+// (fls_strmatch.hip), which narrows the same mask after the key sets.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,7 +42,10 @@ enum FilterOp : uint8_t {
     OP_FALSE = 8,  // no row (col <op> NULL)
     // key-set membership (fls_keyset.hpp): a clause of its own, evaluated by
     // keyset_kernel after filter_kernel, never by eval_term
-    OP_IN_SET = 9, OP_NOT_IN_SET = 10
+    OP_IN_SET = 9, OP_NOT_IN_SET = 10,
+    // string patterns (fls_strmatch.hpp): a clause of its own, evaluated by
+    // strmatch_kernel after keyset_kernel, never by eval_term
+    OP_LIKE = 11, OP_NOT_LIKE = 12
 };
 
 __host__ __device__ inline bool op_holds(uint8_t op, int c) {
@@ -150,6 +157,34 @@ enum : uint32_t { KERR_KEYSET = 512 };
 // nrows rows (fls_keyset.hip).
 hipError_t launch_keyset(const DevSetTerm *d_terms, uint32_t nterms, uint32_t nrows, uint64_t *d_mask,
                          uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
+
+// One pattern term (OP_LIKE / OP_NOT_LIKE) as strmatch_kernel sees it, rebuilt
+// per scan batch; the tokens (fls_strmatch.hpp) follow the descriptors in one
+// buffer.  A row stays selected when its string is valid and matches (negate:
+// valid and does not match).
+struct DevPatTerm {           // 96 B
+    const uint8_t *col;       // decoded string_t column of the batch in HBM (row 0 of the batch)
+    const uint64_t *valid;    // as DevTerm::valid
+    StrRange heap;            // as DevTerm::heap
+    StrRange image;           // as DevTerm::image
+    const uint16_t *tok;      // the compiled pattern in HBM
+    uint32_t ntok;
+    uint32_t min_len;         // a shorter string cannot match
+    uint32_t prefix;          // the literal prefix's first prefix_len bytes, as a record's inline prefix word holds them
+    uint8_t prefix_len;       // 0..4
+    uint8_t negate;           // NOT LIKE
+    uint8_t exact;            // no wildcard: a string longer than ntok cannot match
+    uint8_t pad[9];
+};
+static_assert(sizeof(DevPatTerm) == 96 && sizeof(DevPatTerm) % 32 == 0, "DevPatTerm is 96 B");
+// a pattern descriptor no sound pattern produces (ntok > 256, a token above
+// 257, an inline prefix length above 4, tokens past the staged LDS)
+enum : uint32_t { KERR_PATTERN = 8192 };
+// Narrows the mask and recomputes the counts launch_filter / launch_keyset
+// wrote for the same nrows rows (fls_strmatch.hip).  total_tokens: the sum of
+// the terms' ntok, which sizes the launch's LDS.
+hipError_t launch_strmatch(const DevPatTerm *d_terms, uint32_t nterms, uint32_t total_tokens, uint32_t nrows,
+                           uint64_t *d_mask, uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
 
 // Narrowed delivery (fls_scan_narrow): an integer column of a batch whose
 // values, per row group, lie in [base, base + 2^(8 nw)) crosses PCIe as the

@@ -507,6 +507,19 @@ static bool term_may_match(const fls_table *t, uint32_t rg, const HostTerm &h) {
         if (r.zones.empty() || !(r.zones[h.col].flags & ZM_VALID)) return true;
         return keyset_any_in_range(h.set->img, r.zones[h.col].min, r.zones[h.col].max);
     }
+    if (is_pat_op(h.op)) {
+        // exact on a DICT chunk: some dictionary string matches (NOT LIKE: some does not)
+        if (ch.hdr.enc != ENC_DICT) return true;  // FSST: no statistics
+        const uint8_t *aux = t->img + ch.off + ch.hdr.aux_off;
+        const bool want = h.op == OP_LIKE;
+        for (uint32_t i = 0; i < ch.hdr.dict_count; ++i) {
+            const uint8_t *p;
+            uint32_t len;
+            dict_string(aux, ch.hdr.dict_count, i, p, len);
+            if (like_match(p, len, h.pat->tok.data(), (uint32_t)h.pat->tok.size()) == want) return true;
+        }
+        return false;
+    }
     if (h.kind == FK_STR) {
         if (ch.hdr.enc != ENC_DICT) return true;  // FSST: no statistics
         const uint8_t *aux = t->img + ch.off + ch.hdr.aux_off;
@@ -733,7 +746,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     s.defer_records = options && t->defer_records;
     s.dmask = s.mask;
     for (auto &h : s.terms)
-        if (h.op < OP_IS_NULL || is_set_op(h.op)) s.dmask[h.col] = 1;
+        if (h.op < OP_IS_NULL || is_set_op(h.op) || is_pat_op(h.op)) s.dmask[h.col] = 1;
     s.aggs.clear();
     s.keys.clear();
     s.binds.clear();
@@ -957,10 +970,11 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
     if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
     const std::vector<uint8_t> &need = sl.valid_staged;
     // key-set terms (each a clause of its own) go to keyset_kernel, the rest
-    // to filter_kernel, which with no term left writes the row < nrows mask
-    std::vector<const HostTerm *> ord, sets;
-    for (auto &h : s.terms) (is_set_op(h.op) ? sets : ord).push_back(&h);
-    const size_t nt = ord.size(), no = outs.size(), ns = sets.size();
+    // to filter_kernel, which with no term left writes the row < nrows mask;
+    // pattern terms (a clause each too) go to strmatch_kernel after both
+    std::vector<const HostTerm *> ord, sets, pats;
+    for (auto &h : s.terms) (is_set_op(h.op) ? sets : is_pat_op(h.op) ? pats : ord).push_back(&h);
+    const size_t nt = ord.size(), no = outs.size(), ns = sets.size(), np = pats.size();
     size_t str_bytes = 0;
     for (auto *h : ord) str_bytes += (h->str.size() + 15) & ~size_t(15);
     const size_t bytes = nt * sizeof(DevTerm) + no * sizeof(DevOut) + str_bytes;
@@ -990,6 +1004,40 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
         ds.ob = (uint8_t)out_bytes_of(t, h.col);
         ds.sign = ki.is_signed ? 1 : 0;
         ds.negate = h.op == OP_NOT_IN_SET ? 1 : 0;
+    }
+    // pattern descriptors, then each term's tokens (16-byte aligned)
+    size_t pat_bytes = np * sizeof(DevPatTerm), total_tokens = 0;
+    for (auto *h : pats) pat_bytes += (h->pat->tok.size() * sizeof(uint16_t) + 15) & ~size_t(15);
+    if (np) {
+        HIP_TRY(sl.h_pdesc.alloc(pat_bytes));
+        HIP_TRY(sl.d_pdesc.alloc(d.dev, pat_bytes));
+    }
+    for (size_t i = 0, po = np * sizeof(DevPatTerm); i < np; ++i) {
+        const HostTerm &h = *pats[i];
+        const CompiledPattern &cp = *h.pat;
+        DevPatTerm dp;
+        memset(&dp, 0, sizeof(dp));
+        dp.col = sl.d_out[h.col].p;
+        dp.valid = need[h.col] ? sl.d_valid[h.col].p : nullptr;
+        if (sl.heap_bytes[h.col]) {  // FSST rows (as a string term's ranges below)
+            dp.heap.host_lo = (uint64_t)(uintptr_t)sl.hb->h_heap[h.col].p;
+            dp.heap.host_hi = dp.heap.host_lo + sl.heap_bytes[h.col];
+            dp.heap.dev_delta = (int64_t)((uintptr_t)sl.d_heap[h.col].p - (uintptr_t)sl.hb->h_heap[h.col].p);
+        }
+        dp.image.host_lo = (uint64_t)(uintptr_t)(t->img + in_lo);
+        dp.image.host_hi = dp.image.host_lo + in_len;
+        dp.image.dev_delta = (int64_t)((uintptr_t)sl.in_dev - (uintptr_t)(t->img + in_lo));
+        dp.tok = (const uint16_t *)(sl.d_pdesc.p + po);
+        dp.ntok = (uint32_t)cp.tok.size();
+        dp.min_len = cp.min_len;
+        dp.prefix_len = (uint8_t)std::min<size_t>(4, cp.prefix.size());
+        memcpy(&dp.prefix, cp.prefix.data(), dp.prefix_len);
+        dp.negate = h.op == OP_NOT_LIKE ? 1 : 0;
+        dp.exact = cp.exact ? 1 : 0;
+        memcpy(sl.h_pdesc.p + i * sizeof(DevPatTerm), &dp, sizeof(dp));
+        if (!cp.tok.empty()) memcpy(sl.h_pdesc.p + po, cp.tok.data(), cp.tok.size() * sizeof(uint16_t));
+        po += (cp.tok.size() * sizeof(uint16_t) + 15) & ~size_t(15);
+        total_tokens += cp.tok.size();
     }
     for (size_t i = 0; i < nt; ++i) {
         const HostTerm &h = *ord[i];
@@ -1032,6 +1080,11 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
         HIP_TRY(hipMemcpyAsync(sl.d_sdesc.p, sl.h_sdesc.p, ns * sizeof(DevSetTerm), hipMemcpyHostToDevice, sl.stream));
         HIP_TRY(launch_keyset(sl.d_sdesc.p, (uint32_t)ns, (uint32_t)rows, sl.d_mask.p, sl.d_counts.p, d.err.p,
                               sl.stream));
+    }
+    if (np) {
+        HIP_TRY(hipMemcpyAsync(sl.d_pdesc.p, sl.h_pdesc.p, pat_bytes, hipMemcpyHostToDevice, sl.stream));
+        HIP_TRY(launch_strmatch((const DevPatTerm *)sl.d_pdesc.p, (uint32_t)np, (uint32_t)total_tokens, (uint32_t)rows,
+                                sl.d_mask.p, sl.d_counts.p, d.err.p, sl.stream));
     }
     if (!s.binds.empty())  // mapped GROUP BY keys: their codes, and the inner ones' narrowing of the mask
         if (int rc = enqueue_keymap(t, s, d, sl, rows)) return rc;
@@ -1586,6 +1639,7 @@ static int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
         const uint32_t err = *(volatile const uint32_t *)hb->h_err.p;
         if (err & KERR_FILTER_STR) return fail(FLS_ERR_FORMAT, "filter: string outside its batch heap (flags 0x%x)", err);
         if (err & KERR_KEYSET) return fail(FLS_ERR_FORMAT, "filter: damaged key-set descriptor (flags 0x%x)", err);
+        if (err & KERR_PATTERN) return fail(FLS_ERR_FORMAT, "filter: damaged pattern descriptor (flags 0x%x)", err);
         if (err & KERR_KEYMAP) return fail(FLS_ERR_FORMAT, "grouped aggregate: damaged key-map descriptor (flags 0x%x)", err);
         if (err & KERR_NARROW)
             return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a narrowed column (flags 0x%x)", err);
@@ -1757,7 +1811,7 @@ static int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std:
     if (n && !p) return fail(FLS_ERR_ARG, "fls_scan_filter: NULL predicates");
     for (uint32_t i = 0; i < n; ++i) {
         if (p[i].col >= t->meta.cols.size()) return fail(FLS_ERR_ARG, "filter column %u out of range", p[i].col);
-        if (p[i].op > FLS_CMP_NOT_IN_SET) return fail(FLS_ERR_ARG, "filter operator %u unknown", p[i].op);
+        if (p[i].op > FLS_CMP_NOT_LIKE) return fail(FLS_ERR_ARG, "filter operator %u unknown", p[i].op);
         HostTerm h;
         h.col = p[i].col;
         h.clause = p[i].clause;
@@ -1784,6 +1838,31 @@ static int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std:
                     return fail(FLS_ERR_ARG, "filter term %u: a key-set term shares clause %u with term %u (a set "
                                 "term is a clause of its own)", i, p[i].clause, j);
             h.kind = type_is_signed(ty) ? FK_INT : FK_UINT;
+        } else if (is_pat_op(h.op)) {
+            if (ty != TY_VARCHAR)
+                return fail(FLS_ERR_ARG, "filter term %u: filter operator %u unknown for column %u: LIKE needs a "
+                            "VARCHAR column", i, h.op, h.col);
+            if (p[i].str_len && !p[i].str) return fail(FLS_ERR_ARG, "filter term %u: NULL pattern string", i);
+            if (p[i].value > 255)
+                return fail(FLS_ERR_ARG, "filter term %u: escape 0x%llx is not a byte (0: none)", i,
+                            (unsigned long long)p[i].value);
+            for (uint32_t j = 0; j < n; ++j)
+                if (j != i && p[j].clause == p[i].clause)
+                    return fail(FLS_ERR_ARG, "filter term %u: a pattern term shares clause %u with term %u (a pattern "
+                                "term is a clause of its own)", i, p[i].clause, j);
+            uint32_t npat = 0;
+            for (uint32_t j = 0; j <= i; ++j) npat += p[j].op == FLS_CMP_LIKE || p[j].op == FLS_CMP_NOT_LIKE;
+            if (npat > kMaxPatTerms)
+                return fail(FLS_ERR_ARG, "filter term %u: more than %u pattern terms in one filter", i, kMaxPatTerms);
+            // the compiler stops at token kMaxPatTokens + 1: an oversized pattern is refused after bounded work
+            auto cp = std::make_shared<CompiledPattern>();
+            const int rc = pattern_compile((const uint8_t *)p[i].str, (size_t)p[i].str_len, (uint32_t)p[i].value, *cp);
+            if (rc == PAT_TRAILING_ESCAPE)
+                return fail(FLS_ERR_ARG, "filter term %u: the pattern ends in its escape byte", i);
+            if (rc == PAT_TOO_LONG)
+                return fail(FLS_ERR_ARG, "filter term %u: the pattern compiles to more than %u tokens", i, kMaxPatTokens);
+            h.pat = std::move(cp);
+            h.kind = FK_STR;
         } else if (type_is_string(ty)) {
             h.kind = FK_STR;
             if (p[i].str_len && !p[i].str) return fail(FLS_ERR_ARG, "filter on column %u: NULL string", h.col);

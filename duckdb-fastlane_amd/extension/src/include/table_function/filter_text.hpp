@@ -14,8 +14,11 @@
 //           integer-like column the list becomes one key-set term
 //           (fls_keyset_create, FLS_CMP_IN_SET / FLS_CMP_NOT_IN_SET), on
 //           VARCHAR / FLOAT / DOUBLE EQ terms of one clause (NOT IN: NE terms,
-//           a clause each); NULL in the list follows SQL.  No OR, no other
-//           parentheses.
+//           a clause each); NULL in the list follows SQL.
+//           `column [NOT] LIKE 'pattern' [ESCAPE 'c']` on a VARCHAR column is
+//           one pattern term (FLS_CMP_LIKE / FLS_CMP_NOT_LIKE: `%` any bytes,
+//           `_` one character, case-sensitive; c one byte; LIKE NULL matches
+//           no row).  No OR, no other parentheses.
 //
 // Everything unparsable, unknown or ill-typed is a BinderException that starts
 // with the calling function's name (`who`) and quotes the offending text.
@@ -355,6 +358,52 @@ inline void ParseInList(const Schema &sch, int c, bool negate, Lexer &lex, const
     preds.push_back(p);
 }
 
+// `column [NOT] LIKE 'pattern' [ESCAPE 'c']`, the lexer past LIKE: one pattern
+// term (FLS_CMP_LIKE / FLS_CMP_NOT_LIKE, the escape byte in `value`), a clause
+// of its own.  LIKE NULL matches no row (FLS_CMP_FALSE).
+inline void ParseLike(const Schema &sch, int c, bool negate, Lexer &lex, const string &filter, uint32_t &clause,
+                      std::vector<fls_predicate> &preds, std::deque<string> &strs) {
+    const string &who = lex.who;
+    const string what = negate ? "NOT LIKE" : "LIKE";
+    if (sch.cols[c].type != FLS_VARCHAR)
+        throw BinderException(who + ": " + what + " needs a VARCHAR column, \"" + sch.names[c] + "\" is " +
+                              sch.types[c].ToString() + " in filter \"" + filter + "\"");
+    fls_predicate p;
+    memset(&p, 0, sizeof(p));
+    p.col = (uint32_t)c;
+    p.clause = clause++;
+    Token pat = lex.Next();
+    if (pat.kind == Token::WORD && StringUtil::Lower(pat.text) == "null") {
+        p.op = FLS_CMP_FALSE;
+        preds.push_back(p);
+        return;
+    }
+    if (pat.kind != Token::STRING)
+        throw BinderException(who + ": a quoted pattern is expected after " + what + ", found \"" + pat.text +
+                              "\" in filter \"" + filter + "\"");
+    p.op = negate ? FLS_CMP_NOT_LIKE : FLS_CMP_LIKE;
+    const size_t after = lex.pos;  // ESCAPE is optional: look one token ahead
+    Token t = lex.Next();
+    if (t.kind == Token::WORD && StringUtil::Lower(t.text) == "escape") {
+        Token e = lex.Next();
+        if (e.kind != Token::STRING || e.text.size() != 1 || e.text[0] == '\0')
+            throw BinderException(who + ": ESCAPE needs a string of one byte, found \"" +
+                                  (e.kind == Token::STRING ? "'" + e.text + "'" : e.text) + "\" in filter \"" + filter +
+                                  "\"");
+        p.value = (uint8_t)e.text[0];
+        for (size_t i = 0; i < pat.text.size(); ++i)
+            if ((uint8_t)pat.text[i] == p.value && ++i >= pat.text.size())
+                throw BinderException(who + ": the pattern \"'" + pat.text + "'\" ends in its escape byte \"" + e.text +
+                                      "\" in filter \"" + filter + "\"");
+    } else {
+        lex.pos = after;
+    }
+    strs.push_back(pat.text);
+    p.str = strs.back().data();
+    p.str_len = strs.back().size();
+    preds.push_back(p);
+}
+
 inline void ParseFilter(const Schema &sch, const string &filter, std::vector<fls_predicate> &preds,
                         std::deque<string> &strs, const string &who = "fastlanes_aggregate",
                         fls_connection *conn = nullptr, KeySets *sets = nullptr) {
@@ -372,14 +421,19 @@ inline void ParseFilter(const Schema &sch, const string &filter, std::vector<fls
         p.col = (uint32_t)c;
         Token op = lex.Next();
         bool in_list = op.kind == Token::WORD && StringUtil::Lower(op.text) == "in", negate = false;
+        bool like = op.kind == Token::WORD && StringUtil::Lower(op.text) == "like";
         if (op.kind == Token::WORD && StringUtil::Lower(op.text) == "not") {
             Token t = lex.Next();
-            if (t.kind != Token::WORD || StringUtil::Lower(t.text) != "in")
-                throw BinderException(who + ": NOT IN is expected after \"" + col.text + "\" in filter \"" + filter + "\"");
-            in_list = negate = true;
+            const string low = t.kind == Token::WORD ? StringUtil::Lower(t.text) : "";
+            if (low != "in" && low != "like")
+                throw BinderException(who + ": NOT IN or NOT LIKE is expected after \"" + col.text + "\" in filter \"" +
+                                      filter + "\"");
+            negate = true;
+            (low == "in" ? in_list : like) = true;
         }
-        if (in_list) {
-            ParseInList(sch, c, negate, lex, filter, clause, preds, strs, conn, sets);
+        if (in_list || like) {
+            if (like) ParseLike(sch, c, negate, lex, filter, clause, preds, strs);
+            else ParseInList(sch, c, negate, lex, filter, clause, preds, strs, conn, sets);
             Token next = lex.Next();
             if (next.kind == Token::END) return;
             if (next.kind != Token::WORD || StringUtil::Lower(next.text) != "and")

@@ -109,12 +109,30 @@ typedef struct fls_rowgroup {
  * zero-extended to 64 bits, is in the set; NOT_IN_SET for a valid row whose
  * value is not; a NULL row satisfies neither.  A set term is a clause of its
  * own, AND-ed with the rest (the semi-join / anti-join restriction of a fact
- * table by a filtered dimension's keys). */
+ * table by a filtered dimension's keys).
+ * FLS_CMP_LIKE / FLS_CMP_NOT_LIKE match a VARCHAR column against a pattern
+ * (DuckDB's LIKE): `str` / `str_len` carry the pattern, `value` is 0 for no
+ * escape byte, else the escape byte (1..255).  The pattern is a byte string:
+ * `%` matches any sequence of bytes, the empty one included; `_` matches one
+ * character, that is one byte and every directly following continuation byte
+ * ((b & 0xC0) == 0x80) -- which defines the result on ill-formed UTF-8 too: a
+ * stray continuation byte the match position stands on is a character of its
+ * own; every other byte matches itself, case-sensitively and bytewise; the
+ * whole string must be consumed.  The escape byte followed by any byte x
+ * matches x literally (so `%`, `_` and the escape byte itself can be matched);
+ * a pattern ending in a lone escape byte is FLS_ERR_ARG.  A NULL row
+ * satisfies neither LIKE nor NOT LIKE; a NULL pattern is FLS_CMP_FALSE.  A
+ * BLOB or non-string column is FLS_ERR_ARG.  A pattern term is a clause of
+ * its own, AND-ed with the rest; at most 8 pattern terms per filter and 256
+ * tokens per pattern (a literal byte, `_`, or a run of `%` is one token),
+ * more of either is FLS_ERR_ARG.  Pruning is exact on dictionary-encoded
+ * chunks (the pattern is run on each dictionary string). */
 typedef enum fls_cmp {
     FLS_CMP_EQ = 0, FLS_CMP_NE = 1, FLS_CMP_LT = 2, FLS_CMP_LE = 3, FLS_CMP_GT = 4, FLS_CMP_GE = 5,
     FLS_CMP_IS_NULL = 6, FLS_CMP_IS_NOT_NULL = 7,
     FLS_CMP_FALSE = 8,            /* holds for no row (a comparison with a NULL constant) */
-    FLS_CMP_IN_SET = 9, FLS_CMP_NOT_IN_SET = 10
+    FLS_CMP_IN_SET = 9, FLS_CMP_NOT_IN_SET = 10,
+    FLS_CMP_LIKE = 11, FLS_CMP_NOT_LIKE = 12
 } fls_cmp;
 typedef struct fls_predicate {
     uint32_t col;                 /* table column */
@@ -125,8 +143,9 @@ typedef struct fls_predicate {
                                      signed ints / DATE days / DECIMAL scaled as
                                      int64, unsigned as uint64, FLOAT as IEEE
                                      binary32 bits (low 32), DOUBLE binary64 bits;
-                                     IN_SET / NOT_IN_SET: the fls_keyset handle */
-    const char *str;              /* VARCHAR constant (copied) */
+                                     IN_SET / NOT_IN_SET: the fls_keyset handle;
+                                     LIKE / NOT_LIKE: the escape byte, 0 for none */
+    const char *str;              /* VARCHAR constant or LIKE pattern (copied) */
     uint64_t str_len;
 } fls_predicate;
 
