@@ -71,10 +71,23 @@ class Predicate(C.Structure):
 EQ, NE, LT, LE, GT, GE, IS_NULL, IS_NOT_NULL = range(8)
 OPS = {"=": EQ, "==": EQ, "!=": NE, "<>": NE, "<": LT, "<=": LE, ">": GT, ">=": GE,
        "is_null": IS_NULL, "is_not_null": IS_NOT_NULL, "false": 8,
-       "in_set": 9, "not_in_set": 10, "like": 11, "not_like": 12}
+       "in_set": 9, "not_in_set": 10, "like": 11, "not_like": 12,
+       "col=": 13, "col!=": 14, "col<": 15, "col<=": 16, "col>": 17, "col>=": 18}
 IN_SET, NOT_IN_SET = 9, 10
 LIKE, NOT_LIKE = 11, 12
 MAX_PATTERN_TERMS, MAX_PATTERN_TOKENS = 8, 256   # kMaxPatTerms, kMaxPatTokens
+COL_EQ, COL_NE, COL_LT, COL_LE, COL_GT, COL_GE = range(13, 19)
+
+
+class Col:
+    """the right-hand side of a column-to-column filter term: (a, "<", Col(b))
+    holds for the rows where both columns are valid and a < b"""
+
+    def __init__(self, index: int):
+        self.index = int(index)
+
+    def __repr__(self):
+        return f"Col({self.index})"
 
 
 def _pat_bytes(x, what):
@@ -1038,7 +1051,12 @@ class Table:
         (col, "like", (pattern, escape)) with pattern str or bytes and escape
         one byte; a None pattern selects no row.  (col, "starts_with" /
         "ends_with" / "contains", literal) build the LIKE pattern around the
-        literal, its `%`, `_` and `\\` escaped with `\\`."""
+        literal, its `%`, `_` and `\\` escaped with `\\`.
+        Two columns of the same row: (a, op, Col(b)) with op one of `=`, `!=`,
+        `<`, `<=`, `>`, `>=` (or (a, "col<", b) with the index itself): both
+        values valid and a op b; a clause of its own; two signed or two
+        unsigned integer columns of any widths, two DATE, two DECIMAL of one
+        scale, or FLOAT / DOUBLE in any mix."""
         sch = self.schema()
         arr = (Predicate * max(1, len(filt)))()
         keep = []
@@ -1054,7 +1072,14 @@ class Table:
             p.clause = term[3] if len(term) > 3 else 1000000 + i
             p.op = OPS[op] if isinstance(op, str) else op
             ty = sch[col][1] if 0 <= col < len(sch) else None
-            if p.op in (LIKE, NOT_LIKE):
+            if isinstance(val, Col):
+                if p.op > GE:
+                    raise TypeError(f"filter term {i}: operator {op!r} takes no column on its right")
+                p.op += COL_EQ
+                val = val.index
+            if COL_EQ <= p.op <= COL_GE:
+                p.value = int(val) & 0xFFFFFFFFFFFFFFFF   # the right column's index, no literal conversion
+            elif p.op in (LIKE, NOT_LIKE):
                 pat, esc = val if isinstance(val, tuple) else (val, None)
                 if pat is None:
                     p.op = OPS["false"]   # a NULL pattern: no row

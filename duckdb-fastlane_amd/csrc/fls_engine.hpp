@@ -338,6 +338,8 @@ struct Slot {                       // one batch of row groups in flight
     DevBuf<uint8_t> d_fdesc;
     PinBuf<DevSetTerm> h_sdesc;     // the filter's key-set terms
     DevBuf<DevSetTerm> d_sdesc;
+    PinBuf<DevColTerm> h_cdesc;     // the filter's column-to-column terms
+    DevBuf<DevColTerm> d_cdesc;
     PinBuf<uint8_t> h_pdesc;        // the filter's pattern terms: DevPatTerm[] + their tokens
     DevBuf<uint8_t> d_pdesc;
     std::vector<DevBuf<uint64_t>> d_valid;  // per filtered / aggregated column with a NULL: batch validity words
@@ -515,6 +517,7 @@ struct HostBinding {
 // One term of a pushed-down filter (fls_scan_filter), host side.
 struct HostTerm {
     uint32_t col = 0, clause = 0;
+    uint32_t col2 = 0;              // OP_COL_EQ .. OP_COL_GE: the right column
     uint8_t op = 0, kind = 0;
     uint64_t value = 0;             // comparison domain: int64 / uint64 / double bits
     std::string str;
@@ -523,6 +526,7 @@ struct HostTerm {
 };
 inline bool is_set_op(uint8_t op) { return op == OP_IN_SET || op == OP_NOT_IN_SET; }
 inline bool is_pat_op(uint8_t op) { return op == OP_LIKE || op == OP_NOT_LIKE; }
+inline bool is_col_op(uint8_t op) { return op >= OP_COL_EQ && op <= OP_COL_GE; }
 
 // One aggregate of fls_aggregate, host side.
 struct HostAgg {

@@ -24,6 +24,11 @@
 // has the same shape: a clause of its own, pruned against the DICT
 // dictionaries by the shared matcher and evaluated by strmatch_kernel
 // (fls_strmatch.hip), which narrows the same mask after the key sets.
+// A column term (`column op column` of the same row, OP_COL_EQ .. OP_COL_GE)
+// is a clause of its own as well: pruned by comparing the two zone maps and
+// evaluated by colcmp_kernel (fls_colcmp.hip), which narrows the mask right
+// after filter_kernel -- two coalesced loads and a compare are cheaper than a
+// probe or a string match, so the later kernels skip the words it empties.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,7 +50,10 @@ enum FilterOp : uint8_t {
     OP_IN_SET = 9, OP_NOT_IN_SET = 10,
     // string patterns (fls_strmatch.hpp): a clause of its own, evaluated by
     // strmatch_kernel after keyset_kernel, never by eval_term
-    OP_LIKE = 11, OP_NOT_LIKE = 12
+    OP_LIKE = 11, OP_NOT_LIKE = 12,
+    // column against column: op - OP_COL_EQ is OP_EQ .. OP_GE; a clause of its
+    // own, evaluated by colcmp_kernel after filter_kernel, never by eval_term
+    OP_COL_EQ = 13, OP_COL_NE = 14, OP_COL_LT = 15, OP_COL_LE = 16, OP_COL_GT = 17, OP_COL_GE = 18
 };
 
 __host__ __device__ inline bool op_holds(uint8_t op, int c) {
@@ -156,6 +164,29 @@ enum : uint32_t { KERR_KEYSET = 512 };
 // Narrows the mask and recomputes the counts launch_filter wrote for the same
 // nrows rows (fls_keyset.hip).
 hipError_t launch_keyset(const DevSetTerm *d_terms, uint32_t nterms, uint32_t nrows, uint64_t *d_mask,
+                         uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
+
+// One column term (OP_COL_EQ .. OP_COL_GE) as colcmp_kernel sees it, rebuilt
+// per scan batch.  A row stays selected when both values are valid and
+// `a op b` holds: op_holds(op, cmp_int | cmp_uint | cmp_float) over the values
+// sign- (FK_INT) or zero-extended to 64 bits, a binary32 widened to binary64.
+struct DevColTerm {           // 48 B
+    const uint8_t *a, *b;     // the decoded left / right column of the batch in HBM (row 0 of the batch)
+    const uint64_t *va, *vb;  // as DevTerm::valid, per side
+    uint8_t oba, obb;         // bytes per decoded value: 1, 2, 4 or 8
+    uint8_t kind;             // FK_INT / FK_UINT / FK_FLOAT, of both sides
+    uint8_t op;               // OP_EQ .. OP_GE
+    uint8_t f32a, f32b;       // FK_FLOAT: the side holds binary32 values (ob 4), else binary64 (ob 8)
+    uint8_t pad[10];
+};
+static_assert(sizeof(DevColTerm) == 48, "DevColTerm is 48 B");
+// a column-comparison descriptor no sound term produces (a width outside
+// {1, 2, 4, 8}, a kind above FK_FLOAT, an op above OP_GE, binary32 flagged on
+// an integer kind, a float side whose width does not fit its flag)
+enum : uint32_t { KERR_COLCMP = 16384 };
+// Narrows the mask and recomputes the counts launch_filter wrote for the same
+// nrows rows (fls_colcmp.hip).
+hipError_t launch_colcmp(const DevColTerm *d_terms, uint32_t nterms, uint32_t nrows, uint64_t *d_mask,
                          uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
 
 // One pattern term (OP_LIKE / OP_NOT_LIKE) as strmatch_kernel sees it, rebuilt

@@ -507,6 +507,35 @@ static bool term_may_match(const fls_table *t, uint32_t rg, const HostTerm &h) {
         if (r.zones.empty() || !(r.zones[h.col].flags & ZM_VALID)) return true;
         return keyset_any_in_range(h.set->img, r.zones[h.col].min, r.zones[h.col].max);
     }
+    if (is_col_op(h.op)) {
+        // the two zone maps compared in the term's order; conservative
+        if (r.zones.empty()) return true;
+        const ZoneMap &za = r.zones[h.col], &zb = r.zones[h.col2];
+        if (zb.flags & ZM_ALL_NULL) return false;  // no row valid on both sides
+        if (!(za.flags & ZM_VALID) || !(zb.flags & ZM_VALID)) return true;
+        uint64_t alo = za.min, ahi = za.max, blo = zb.min, bhi = zb.max;
+        if (h.kind == FK_FLOAT) {  // the substitution the constant terms make below
+            uint64_t nan;
+            const double d = __builtin_nan("");
+            memcpy(&nan, &d, 8);
+            if (za.flags & ZM_ALL_NAN) alo = nan;
+            if (za.flags & ZM_HAS_NAN) ahi = nan;
+            if (zb.flags & ZM_ALL_NAN) blo = nan;
+            if (zb.flags & ZM_HAS_NAN) bhi = nan;
+        }
+        auto cmp = [&](uint64_t x, uint64_t y) {
+            return h.kind == FK_INT ? cmp_int((int64_t)x, (int64_t)y)
+                                    : h.kind == FK_UINT ? cmp_uint(x, y) : cmp_float(as_double(x), as_double(y));
+        };
+        switch (h.op - OP_COL_EQ) {
+        case OP_EQ: return cmp(alo, bhi) <= 0 && cmp(blo, ahi) <= 0;  // the ranges intersect
+        case OP_NE: return !(cmp(alo, ahi) == 0 && cmp(blo, bhi) == 0 && cmp(alo, blo) == 0);  // not one single value
+        case OP_LT: return cmp(alo, bhi) < 0;
+        case OP_LE: return cmp(alo, bhi) <= 0;
+        case OP_GT: return cmp(ahi, blo) > 0;
+        default: return cmp(ahi, blo) >= 0;  // OP_GE
+        }
+    }
     if (is_pat_op(h.op)) {
         // exact on a DICT chunk: some dictionary string matches (NOT LIKE: some does not)
         if (ch.hdr.enc != ENC_DICT) return true;  // FSST: no statistics
@@ -747,6 +776,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     s.dmask = s.mask;
     for (auto &h : s.terms)
         if (h.op < OP_IS_NULL || is_set_op(h.op) || is_pat_op(h.op)) s.dmask[h.col] = 1;
+        else if (is_col_op(h.op)) s.dmask[h.col] = s.dmask[h.col2] = 1;
     s.aggs.clear();
     s.keys.clear();
     s.binds.clear();
@@ -902,7 +932,10 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
     sl.d_valid.resize(ncols);
     std::vector<uint8_t> &need = sl.valid_staged;
     need.assign(ncols, 0);
-    for (auto &h : s.terms) need[h.col] = 1;
+    for (auto &h : s.terms) {
+        need[h.col] = 1;
+        if (is_col_op(h.op)) need[h.col2] = 1;
+    }
     for (auto &a : s.aggs) {
         if (a.fn == AGG_SUM_EXPR) {
             for (uint32_t i = 0; i < a.nf; ++i) need[a.fcol[i]] = 1;
@@ -971,10 +1004,15 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
     const std::vector<uint8_t> &need = sl.valid_staged;
     // key-set terms (each a clause of its own) go to keyset_kernel, the rest
     // to filter_kernel, which with no term left writes the row < nrows mask;
-    // pattern terms (a clause each too) go to strmatch_kernel after both
-    std::vector<const HostTerm *> ord, sets, pats;
-    for (auto &h : s.terms) (is_set_op(h.op) ? sets : is_pat_op(h.op) ? pats : ord).push_back(&h);
-    const size_t nt = ord.size(), no = outs.size(), ns = sets.size(), np = pats.size();
+    // pattern terms (a clause each too) go to strmatch_kernel after both.
+    // Column terms (a clause each as well) go to colcmp_kernel, which runs
+    // before the key sets: two coalesced loads and a compare are cheaper than
+    // a probe or a string match, and the later kernels skip the words it
+    // empties (all clauses are AND-ed, so the order changes no result).
+    std::vector<const HostTerm *> ord, sets, pats, ccs;
+    for (auto &h : s.terms)
+        (is_set_op(h.op) ? sets : is_pat_op(h.op) ? pats : is_col_op(h.op) ? ccs : ord).push_back(&h);
+    const size_t nt = ord.size(), no = outs.size(), ns = sets.size(), np = pats.size(), nc = ccs.size();
     size_t str_bytes = 0;
     for (auto *h : ord) str_bytes += (h->str.size() + 15) & ~size_t(15);
     const size_t bytes = nt * sizeof(DevTerm) + no * sizeof(DevOut) + str_bytes;
@@ -1004,6 +1042,26 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
         ds.ob = (uint8_t)out_bytes_of(t, h.col);
         ds.sign = ki.is_signed ? 1 : 0;
         ds.negate = h.op == OP_NOT_IN_SET ? 1 : 0;
+    }
+    // column terms: the full decoded values of both sides (never a narrowed copy)
+    if (nc) {
+        HIP_TRY(sl.h_cdesc.alloc(nc));
+        HIP_TRY(sl.d_cdesc.alloc(d.dev, nc));
+    }
+    for (size_t i = 0; i < nc; ++i) {
+        const HostTerm &h = *ccs[i];
+        DevColTerm &dc = sl.h_cdesc.p[i];
+        memset(&dc, 0, sizeof(dc));
+        dc.a = sl.d_out[h.col].p;
+        dc.b = sl.d_out[h.col2].p;
+        dc.va = need[h.col] ? sl.d_valid[h.col].p : nullptr;
+        dc.vb = need[h.col2] ? sl.d_valid[h.col2].p : nullptr;
+        dc.oba = (uint8_t)out_bytes_of(t, h.col);
+        dc.obb = (uint8_t)out_bytes_of(t, h.col2);
+        dc.kind = h.kind;
+        dc.op = (uint8_t)(h.op - OP_COL_EQ);
+        dc.f32a = t->meta.cols[h.col].type == TY_FLOAT ? 1 : 0;
+        dc.f32b = t->meta.cols[h.col2].type == TY_FLOAT ? 1 : 0;
     }
     // pattern descriptors, then each term's tokens (16-byte aligned)
     size_t pat_bytes = np * sizeof(DevPatTerm), total_tokens = 0;
@@ -1076,6 +1134,11 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
     HIP_TRY(sl.d_counts.alloc(d.dev, hb.nvec));
     HIP_TRY(launch_filter((const DevTerm *)sl.d_fdesc.p, (uint32_t)nt, (uint32_t)rows, sl.d_mask.p, sl.d_counts.p,
                           d.err.p, sl.stream));
+    if (nc) {
+        HIP_TRY(hipMemcpyAsync(sl.d_cdesc.p, sl.h_cdesc.p, nc * sizeof(DevColTerm), hipMemcpyHostToDevice, sl.stream));
+        HIP_TRY(launch_colcmp(sl.d_cdesc.p, (uint32_t)nc, (uint32_t)rows, sl.d_mask.p, sl.d_counts.p, d.err.p,
+                              sl.stream));
+    }
     if (ns) {
         HIP_TRY(hipMemcpyAsync(sl.d_sdesc.p, sl.h_sdesc.p, ns * sizeof(DevSetTerm), hipMemcpyHostToDevice, sl.stream));
         HIP_TRY(launch_keyset(sl.d_sdesc.p, (uint32_t)ns, (uint32_t)rows, sl.d_mask.p, sl.d_counts.p, d.err.p,
@@ -1213,7 +1276,10 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     // whatever is delivered: its key within a row group is the code
     // (fls_aggregate_grouped has checked the chunks).
     std::vector<uint8_t> code_w(ncols, 0), in_term(ncols, 0), is_key(ncols, 0);
-    for (auto &h : s.terms) in_term[h.col] = 1;
+    for (auto &h : s.terms) {
+        in_term[h.col] = 1;
+        if (is_col_op(h.op)) in_term[h.col2] = 1;
+    }
     for (uint32_t c : s.keys)
         if (!(c & FLS_KEY_MAPPED)) is_key[c] = 1;
     for (uint32_t c = 0; c < ncols; ++c) {
@@ -1640,6 +1706,8 @@ static int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
         if (err & KERR_FILTER_STR) return fail(FLS_ERR_FORMAT, "filter: string outside its batch heap (flags 0x%x)", err);
         if (err & KERR_KEYSET) return fail(FLS_ERR_FORMAT, "filter: damaged key-set descriptor (flags 0x%x)", err);
         if (err & KERR_PATTERN) return fail(FLS_ERR_FORMAT, "filter: damaged pattern descriptor (flags 0x%x)", err);
+        if (err & KERR_COLCMP)
+            return fail(FLS_ERR_FORMAT, "filter: damaged column-comparison descriptor (flags 0x%x)", err);
         if (err & KERR_KEYMAP) return fail(FLS_ERR_FORMAT, "grouped aggregate: damaged key-map descriptor (flags 0x%x)", err);
         if (err & KERR_NARROW)
             return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a narrowed column (flags 0x%x)", err);
@@ -1811,7 +1879,7 @@ static int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std:
     if (n && !p) return fail(FLS_ERR_ARG, "fls_scan_filter: NULL predicates");
     for (uint32_t i = 0; i < n; ++i) {
         if (p[i].col >= t->meta.cols.size()) return fail(FLS_ERR_ARG, "filter column %u out of range", p[i].col);
-        if (p[i].op > FLS_CMP_NOT_LIKE) return fail(FLS_ERR_ARG, "filter operator %u unknown", p[i].op);
+        if (p[i].op > FLS_CMP_COL_GE) return fail(FLS_ERR_ARG, "filter operator %u unknown", p[i].op);
         HostTerm h;
         h.col = p[i].col;
         h.clause = p[i].clause;
@@ -1838,6 +1906,40 @@ static int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std:
                     return fail(FLS_ERR_ARG, "filter term %u: a key-set term shares clause %u with term %u (a set "
                                 "term is a clause of its own)", i, p[i].clause, j);
             h.kind = type_is_signed(ty) ? FK_INT : FK_UINT;
+        } else if (is_col_op(h.op)) {
+            // `column op column`: value is the right column; both sides in one comparison domain
+            if (p[i].value >= t->meta.cols.size())
+                return fail(FLS_ERR_ARG, "filter term %u: right column %llu out of range (left column %u, %zu columns)",
+                            i, (unsigned long long)p[i].value, h.col, t->meta.cols.size());
+            h.col2 = (uint32_t)p[i].value;
+            const ColumnMeta &ca = t->meta.cols[h.col], &cb = t->meta.cols[h.col2];
+            const uint8_t tb = cb.type;
+            if (type_is_string(ty) || type_is_string(tb) || !type_valid(ty) || !type_valid(tb))
+                return fail(FLS_ERR_ARG, "filter term %u: a column comparison cannot read a VARCHAR / BLOB column "
+                            "(columns %u and %u)", i, h.col, h.col2);
+            if (type_is_float(ty) != type_is_float(tb))
+                return fail(FLS_ERR_ARG, "filter term %u: an integer-like column against a FLOAT / DOUBLE column "
+                            "(columns %u and %u)", i, h.col, h.col2);
+            if ((ty == TY_DATE) != (tb == TY_DATE))
+                return fail(FLS_ERR_ARG, "filter term %u: a DATE column against a non-DATE column (columns %u and %u)",
+                            i, h.col, h.col2);
+            if ((ty == TY_DECIMAL) != (tb == TY_DECIMAL))
+                return fail(FLS_ERR_ARG, "filter term %u: a DECIMAL column against a non-DECIMAL column (columns %u "
+                            "and %u)", i, h.col, h.col2);
+            if (ty == TY_DECIMAL && (ca.width > 18 || cb.width > 18))
+                return fail(FLS_ERR_ARG, "filter term %u: a column comparison cannot read a DECIMAL wider than 64 bits "
+                            "(columns %u and %u)", i, h.col, h.col2);
+            if (ty == TY_DECIMAL && ca.scale != cb.scale)
+                return fail(FLS_ERR_ARG, "filter term %u: DECIMALs of different scale, %u and %u (columns %u and %u)",
+                            i, (uint32_t)ca.scale, (uint32_t)cb.scale, h.col, h.col2);
+            if (!type_is_float(ty) && type_is_signed(ty) != type_is_signed(tb))
+                return fail(FLS_ERR_ARG, "filter term %u: a signed column against an unsigned column (columns %u and "
+                            "%u)", i, h.col, h.col2);
+            for (uint32_t j = 0; j < n; ++j)
+                if (j != i && p[j].clause == p[i].clause)
+                    return fail(FLS_ERR_ARG, "filter term %u: a column term shares clause %u with term %u (a column "
+                                "term is a clause of its own; columns %u and %u)", i, p[i].clause, j, h.col, h.col2);
+            h.kind = col_kind(t, h.col);
         } else if (is_pat_op(h.op)) {
             if (ty != TY_VARCHAR)
                 return fail(FLS_ERR_ARG, "filter term %u: filter operator %u unknown for column %u: LIKE needs a "

@@ -18,7 +18,12 @@
 //           `column [NOT] LIKE 'pattern' [ESCAPE 'c']` on a VARCHAR column is
 //           one pattern term (FLS_CMP_LIKE / FLS_CMP_NOT_LIKE: `%` any bytes,
 //           `_` one character, case-sensitive; c one byte; LIKE NULL matches
-//           no row).  No OR, no other parentheses.
+//           no row).  `column op column` compares two columns of the same
+//           row (FLS_CMP_COL_EQ .. FLS_CMP_COL_GE): the right side is a
+//           column when it is an identifier the schema resolves and neither
+//           NULL nor the start of a typed literal (DATE '...'); a word that
+//           names no column is read as a literal as before (nan, inf, true).
+//           No OR, no other parentheses.
 //
 // Everything unparsable, unknown or ill-typed is a BinderException that starts
 // with the calling function's name (`who`) and quotes the offending text.
@@ -404,6 +409,26 @@ inline void ParseLike(const Schema &sch, int c, bool negate, Lexer &lex, const s
     preds.push_back(p);
 }
 
+// `column op column`: the pairs the engine compares (include/flsgpu.h) -- two
+// signed or two unsigned integer columns of any widths, two DATE, two DECIMAL
+// of at most 64 bits and one scale, FLOAT / DOUBLE in any mix.
+inline void CheckColumnPair(const Schema &sch, int a, int b, const string &who, const string &filter) {
+    const fls_column_info &ca = sch.cols[a], &cb = sch.cols[b];
+    auto is_unsigned = [](uint8_t t) { return (t >= FLS_UINT8 && t <= FLS_UINT64) || t == FLS_BOOLEAN; };
+    const char *why = nullptr;
+    if (IsString(ca.type) || IsString(cb.type)) why = "strings are compared with constants only";
+    else if (IsFloat(ca.type) != IsFloat(cb.type)) why = "an integer-like column against a float";
+    else if ((ca.type == FLS_DATE) != (cb.type == FLS_DATE)) why = "a DATE column against a non-DATE column";
+    else if ((ca.type == FLS_DECIMAL) != (cb.type == FLS_DECIMAL)) why = "a DECIMAL column against a non-DECIMAL column";
+    else if (ca.type == FLS_DECIMAL && (ca.width > 18 || cb.width > 18)) why = "a DECIMAL wider than 64 bits";
+    else if (ca.type == FLS_DECIMAL && ca.scale != cb.scale) why = "DECIMALs of different scale";
+    else if (!IsFloat(ca.type) && is_unsigned(ca.type) != is_unsigned(cb.type)) why = "a signed column against an unsigned column";
+    if (why)
+        throw BinderException(who + ": cannot compare " + sch.types[a].ToString() + " column \"" + sch.names[a] +
+                              "\" with " + sch.types[b].ToString() + " column \"" + sch.names[b] + "\" (" + why +
+                              ") in filter \"" + filter + "\"");
+}
+
 inline void ParseFilter(const Schema &sch, const string &filter, std::vector<fls_predicate> &preds,
                         std::deque<string> &strs, const string &who = "fastlanes_aggregate",
                         fls_connection *conn = nullptr, KeySets *sets = nullptr) {
@@ -460,7 +485,35 @@ inline void ParseFilter(const Schema &sch, const string &filter, std::vector<fls
                    : op.text == "<="                     ? FLS_CMP_LE
                    : op.text == ">"                      ? FLS_CMP_GT
                                                          : FLS_CMP_GE;
-            SetLiteral(sch, c, lex, lex.Next(), filter, p, strs);
+            // the right side: a column when it is an identifier the schema resolves and
+            // neither NULL nor the start of a typed literal (DATE '...'); else a literal
+            Token rhs = lex.Next();
+            const string low = rhs.kind == Token::WORD ? StringUtil::Lower(rhs.text) : "";
+            bool typed = false;
+            if (low == "date") {
+                const size_t after = lex.pos;
+                typed = lex.Next().kind == Token::STRING;
+                lex.pos = after;
+            }
+            const bool word = rhs.kind == Token::WORD && low != "null" && !typed;
+            const int c2 = word ? sch.Find(rhs.text) : -1;
+            if (c2 >= 0) {
+                CheckColumnPair(sch, c, c2, who, filter);
+                p.op = (uint8_t)(FLS_CMP_COL_EQ + p.op);
+                p.value = (uint64_t)c2;
+            } else if (word && low != "date") {
+                // a word that names no column is still a literal where it was one before (nan, inf,
+                // infinity on a FLOAT / DOUBLE column, true / false on a BOOLEAN one); only a word
+                // the literal parser refuses as well is reported as an unknown column
+                try {
+                    SetLiteral(sch, c, lex, rhs, filter, p, strs);
+                } catch (const BinderException &) {
+                    throw BinderException(who + ": column \"" + rhs.text + "\" on the right of \"" + col.text + " " +
+                                          op.text + "\" in filter \"" + filter + "\" not found");
+                }
+            } else {
+                SetLiteral(sch, c, lex, rhs, filter, p, strs);
+            }
         } else {
             throw BinderException(who + ": a comparison or IS [NOT] NULL is expected after \"" + col.text +
                                   "\" in filter \"" + filter + "\"");

@@ -126,13 +126,37 @@ typedef struct fls_rowgroup {
  * its own, AND-ed with the rest; at most 8 pattern terms per filter and 256
  * tokens per pattern (a literal byte, `_`, or a run of `%` is one token),
  * more of either is FLS_ERR_ARG.  Pruning is exact on dictionary-encoded
- * chunks (the pattern is run on each dictionary string). */
+ * chunks (the pattern is run on each dictionary string).
+ * FLS_CMP_COL_EQ .. FLS_CMP_COL_GE compare two columns of the same row:
+ * `op - FLS_CMP_COL_EQ` is the ordinary comparison FLS_CMP_EQ .. FLS_CMP_GE,
+ * `col` the left column, `value` the index of the right column; `str` and
+ * `str_len` are ignored.  The term holds for a row when both values are valid
+ * and `left op right` holds in the order the constant terms use; a NULL on
+ * either side satisfies no operator, `!=` included.  Integers are sign- or
+ * zero-extended to 64 bits, so the two widths may differ (INT8 against
+ * INT64).  FLOAT and DOUBLE compare as binary64, a FLOAT widened exactly:
+ * NaN equals NaN and sits above every number, -0 equals 0.  Accepted pairs:
+ * two signed integer columns; two unsigned integer columns (BOOLEAN
+ * included); two DATE columns; two DECIMAL columns of at most 64 bits with
+ * equal scale; two of FLOAT / DOUBLE in any mix.  The same column on both
+ * sides is legal: `a = a` selects the valid rows, `a < a` none.  FLS_ERR_ARG,
+ * naming the term and both columns, before any device work: a right column
+ * out of range; VARCHAR / BLOB on either side; signed against unsigned; an
+ * integer-like column against a float; DATE against a non-DATE; DECIMAL
+ * against a non-DECIMAL, DECIMALs of different scale or one wider than 64
+ * bits; a column term that shares its clause with another term (it is a
+ * clause of its own, AND-ed with the rest).  A row group is pruned when
+ * either side is all NULL or when the two zone maps exclude the comparison
+ * (min(a) < max(b) for `<`, intersecting ranges for `=`, ...); a missing zone
+ * map on either side keeps it. */
 typedef enum fls_cmp {
     FLS_CMP_EQ = 0, FLS_CMP_NE = 1, FLS_CMP_LT = 2, FLS_CMP_LE = 3, FLS_CMP_GT = 4, FLS_CMP_GE = 5,
     FLS_CMP_IS_NULL = 6, FLS_CMP_IS_NOT_NULL = 7,
     FLS_CMP_FALSE = 8,            /* holds for no row (a comparison with a NULL constant) */
     FLS_CMP_IN_SET = 9, FLS_CMP_NOT_IN_SET = 10,
-    FLS_CMP_LIKE = 11, FLS_CMP_NOT_LIKE = 12
+    FLS_CMP_LIKE = 11, FLS_CMP_NOT_LIKE = 12,
+    FLS_CMP_COL_EQ = 13, FLS_CMP_COL_NE = 14, FLS_CMP_COL_LT = 15, FLS_CMP_COL_LE = 16, FLS_CMP_COL_GT = 17,
+    FLS_CMP_COL_GE = 18           /* column against column: value is the right column's index */
 } fls_cmp;
 typedef struct fls_predicate {
     uint32_t col;                 /* table column */
@@ -144,7 +168,8 @@ typedef struct fls_predicate {
                                      int64, unsigned as uint64, FLOAT as IEEE
                                      binary32 bits (low 32), DOUBLE binary64 bits;
                                      IN_SET / NOT_IN_SET: the fls_keyset handle;
-                                     LIKE / NOT_LIKE: the escape byte, 0 for none */
+                                     LIKE / NOT_LIKE: the escape byte, 0 for none;
+                                     COL_EQ .. COL_GE: the right column's index */
     const char *str;              /* VARCHAR constant or LIKE pattern (copied) */
     uint64_t str_len;
 } fls_predicate;
