@@ -89,6 +89,12 @@ class Col:
     def __repr__(self):
         return f"Col({self.index})"
 
+    def __eq__(self, other):
+        return isinstance(other, Col) and other.index == self.index
+
+    def __hash__(self):
+        return hash(("Col", self.index))
+
 
 def _pat_bytes(x, what):
     if isinstance(x, str):
@@ -144,7 +150,30 @@ AGGV_NULL, AGGV_INT, AGGV_DOUBLE = 0, 1, 2
 
 class AggregateSpec(C.Structure):
     _fields_ = [("fn", C.c_uint8), ("pad", C.c_uint8 * 3), ("col", C.c_uint32), ("col2", C.c_uint32),
-                ("pad2", C.c_uint32)]
+                ("cond", C.c_uint32)]   # 0: none, i: condition i - 1 (fls_aggregate_conditions)
+
+
+class AggCondition(C.Structure):   # fls_agg_condition: preds[first .. first + n)
+    _fields_ = [("first", C.c_uint32), ("n", C.c_uint32)]
+
+
+MAX_AGG_CONDITIONS = 8             # kMaxConds
+
+
+class When:
+    """agg FILTER (WHERE filt): any aggregate tuple of aggregate() under a
+    condition of its own, filt as scan_filtered takes it.  The aggregate
+    counts a row when the call's filter selects it, filt holds there and its
+    operands are valid there; filt prunes nothing and makes or removes no
+    group.  Accepted anywhere in the aggs of aggregate(), aggregate_grouped()
+    and aggregate_hashed()."""
+
+    def __init__(self, agg, filt):
+        self.agg = tuple(agg)
+        self.filt = [tuple(term) for term in filt]
+
+    def __repr__(self):
+        return f"When({self.agg!r}, {self.filt!r})"
 
 
 class AggFactor(C.Structure):   # fls_agg_factor: k + sign * column
@@ -255,6 +284,7 @@ _sig("fls_aggregate_key_bindings", C.c_int, _P, C.POINTER(KeyBinding), C.c_uint3
 _sig("fls_aggregate", C.c_int, _P, C.POINTER(AggregateSpec), C.c_uint32, C.c_uint32, C.c_uint32,
      C.POINTER(AggregateValue))
 _sig("fls_aggregate_exprs", C.c_int, _P, C.POINTER(AggExpr), C.c_uint32)
+_sig("fls_aggregate_conditions", C.c_int, _P, C.POINTER(Predicate), C.c_uint32, C.POINTER(AggCondition), C.c_uint32)
 _sig("fls_aggregate_grouped", C.c_int, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(AggregateSpec), C.c_uint32,
      C.c_uint32, C.c_uint32, C.POINTER(_P))
 _sig("fls_group_result_ngroups", C.c_uint64, _P)
@@ -780,12 +810,19 @@ def _agg_exprs(exprs) -> C.Array:
 
 
 def _agg_specs(aggs):
-    """fls_aggregate_spec[] of aggregate()'s tuples, and the factor lists of
-    its ("sum_expr", [...]) items in the order their specs index them; a first
-    element that is an int is passed through as the function code"""
+    """fls_aggregate_spec[] of aggregate()'s tuples, the factor lists of its
+    ("sum_expr", [...]) items in the order their specs index them, and the
+    distinct conditions of its When items in the order their specs' cond - 1
+    index them (equal conditions share one); a first element that is an int is
+    passed through as the function code"""
     arr = (AggregateSpec * max(1, len(aggs)))()
-    exprs = []
+    exprs, conds = [], []
     for i, a in enumerate(aggs[:len(arr)]):
+        if isinstance(a, When):
+            if a.filt not in conds:
+                conds.append(a.filt)
+            arr[i].cond = conds.index(a.filt) + 1
+            a = a.agg
         fn = a[0]
         if fn == "sum_expr":
             arr[i].fn = AGG_FNS[fn]
@@ -797,7 +834,7 @@ def _agg_specs(aggs):
         arr[i].fn = fn
         arr[i].col = a[1] if len(a) > 1 else 0
         arr[i].col2 = a[2] if len(a) > 2 else 0
-    return arr, exprs
+    return arr, exprs, conds
 
 
 def _agg_value(v: AggregateValue):
@@ -1219,6 +1256,23 @@ class Table:
         exprs = exprs or []
         _check(_lib.fls_aggregate_exprs(self.h, _agg_exprs(exprs) if exprs else None, len(exprs)))
 
+    def set_aggregate_conditions(self, conds):
+        """fls_aggregate_conditions: the condition list an aggregate spec's
+        cond = i + 1 indexes in the following aggregate calls (what When sets
+        and clears per call); each condition a filter as scan_filtered takes
+        it, at most 8.  [] or None clears."""
+        conds = conds or []
+        parts = [self._preds(c) for c in conds]
+        preds = (Predicate * max(1, sum(n for _, n, _ in parts)))()
+        ranges = (AggCondition * max(1, len(conds)))()
+        k = 0
+        for i, (arr, n, _keep) in enumerate(parts):
+            ranges[i].first, ranges[i].n = k, n
+            for j in range(n):
+                preds[k + j] = arr[j]   # (the strings stay alive in parts until the call has copied them)
+            k += n
+        _check(_lib.fls_aggregate_conditions(self.h, preds if k else None, k, ranges if conds else None, len(conds)))
+
     def aggregate_raw(self, aggs, rg_begin=0, rg_end=None) -> list[AggregateValue]:
         """fls_aggregate under the filter currently set (set_filter): the raw
         fls_aggregate_value records.  aggs as for aggregate(); a first element
@@ -1227,15 +1281,19 @@ class Table:
         items replace that list for the call and clear it afterwards."""
         if rg_end is None:
             rg_end = self.nrowgroups
-        arr, exprs = _agg_specs(aggs)
+        arr, exprs, conds = _agg_specs(aggs)
         out = (AggregateValue * max(1, len(aggs)))()
-        if exprs:
-            self.set_aggregate_exprs(exprs)
         try:
+            if exprs:
+                self.set_aggregate_exprs(exprs)
+            if conds:
+                self.set_aggregate_conditions(conds)
             _check(_lib.fls_aggregate(self.h, arr, len(aggs), rg_begin, rg_end, out))
         finally:
             if exprs:
                 self.set_aggregate_exprs(None)
+            if conds:
+                self.set_aggregate_conditions(None)
         return list(out)[:len(aggs)]
 
     def aggregate(self, aggs, filt=None, rg_begin=0, rg_end=None) -> list:
@@ -1244,7 +1302,9 @@ class Table:
         ("min", col), ("max", col), ("sum_product", a, b),
         ("sum_expr", [(k, sign, col), ...]) [the exact integer sum of the
         product of 1 to 3 factors k + sign * col, sign +1 or -1, k in the
-        column's physical unit]; filt as scan_filtered takes it.  Returns per aggregate an int (counts, integer
+        column's physical unit], or When(agg, cond) [agg FILTER (WHERE cond):
+        any of these over the rows of the call's filter where cond, a filter of
+        its own, holds too]; filt as scan_filtered takes it.  Returns per aggregate an int (counts, integer
         sums at full 128-bit precision, integer MIN / MAX), a float (FLOAT /
         DOUBLE sums, MIN, MAX) or None (SUM / MIN / MAX over no row)."""
         self.set_filter(filt)
@@ -1281,12 +1341,14 @@ class Table:
             else:
                 raw.append(k)
         karr = (C.c_uint32 * max(1, len(raw)))(*raw[:max(1, len(raw))])
-        arr, exprs = _agg_specs(aggs)
+        arr, exprs, conds = _agg_specs(aggs)
         res = _P()
         self.set_filter(filt)
         try:
             if exprs:
                 self.set_aggregate_exprs(exprs)
+            if conds:
+                self.set_aggregate_conditions(conds)
             if binds:
                 self.set_key_bindings(binds)
             _check(_lib.fls_aggregate_grouped(self.h, karr, len(keys), arr, len(aggs), rg_begin, rg_end,
@@ -1295,6 +1357,8 @@ class Table:
             _check(_lib.fls_scan_filter(self.h, None, 0))
             if exprs:
                 self.set_aggregate_exprs(None)
+            if conds:
+                self.set_aggregate_conditions(None)
             if binds:
                 self.set_key_bindings(None)
         try:
@@ -1374,7 +1438,7 @@ class Table:
         if rg_end is None:
             rg_end = self.nrowgroups
         karr = (C.c_uint32 * max(1, len(keys)))(*keys[:max(1, len(keys))])
-        arr, exprs = _agg_specs(aggs)
+        arr, exprs, conds = _agg_specs(aggs)
         res = _P()
         select = having is not None or order_by is not None or limit is not None
         if select:
@@ -1383,6 +1447,8 @@ class Table:
         try:
             if exprs:
                 self.set_aggregate_exprs(exprs)
+            if conds:
+                self.set_aggregate_conditions(conds)
             if select:
                 _check(_lib.fls_aggregate_hashed_select(self.h, karr, len(keys), arr, len(aggs), max_groups,
                                                         C.byref(sel), rg_begin, rg_end, C.byref(res)))
@@ -1393,6 +1459,8 @@ class Table:
             _check(_lib.fls_scan_filter(self.h, None, 0))
             if exprs:
                 self.set_aggregate_exprs(None)
+            if conds:
+                self.set_aggregate_conditions(None)
         try:
             signed = [self.column(k).type in (INT8, INT16, INT32, INT64, DATE, DECIMAL) for k in keys]
             return HashGroups(res, signed, len(aggs), in_result_order=order_by is not None or bool(limit))

@@ -48,6 +48,7 @@ __global__ __launch_bounds__(256) void aggregate_kernel(const DevAgg *__restrict
                 const uint64_t base = (uint64_t)v * 1024 + 64 * word;
                 m[k] = base >= nrows ? 0ull : (nrows - base >= 64 ? ~0ull : (1ull << (nrows - base)) - 1);
                 if (mask) m[k] &= mask[(size_t)v * 16 + word];
+                if (g.cond) m[k] &= g.cond[(size_t)v * 16 + word];
                 for (uint32_t i = 0; i < g.nf; ++i)
                     if (g.f[i].valid) m[k] &= g.f[i].valid[(size_t)v * 16 + word];
                 cnt += (uint64_t)__popcll(m[k]);
@@ -62,6 +63,7 @@ __global__ __launch_bounds__(256) void aggregate_kernel(const DevAgg *__restrict
                 // rows of this word below nrows: no row past the batch is ever selected
                 uint64_t m = base >= nrows ? 0ull : (nrows - base >= 64 ? ~0ull : (1ull << (nrows - base)) - 1);
                 if (mask) m &= mask[(size_t)v * 16 + word];
+                if (g.cond) m &= g.cond[(size_t)v * 16 + word];
                 if (fn != AGG_COUNT_STAR) {
                     if (g.valid) m &= g.valid[(size_t)v * 16 + word];
                     if (fn == AGG_SUM_PRODUCT && g.valid2) m &= g.valid2[(size_t)v * 16 + word];

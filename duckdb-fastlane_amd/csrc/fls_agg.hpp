@@ -6,8 +6,9 @@
 // One launch per batch evaluates every requested aggregate and writes one
 // fixed-size partial record per (1024-row vector, aggregate); the host folds
 // the records in row order (fls_scan_agg.hip).  A row contributes when it is
-// selected (mask bit, or row < nrows without a mask) and its operand column(s)
-// are valid there: values at NULL rows are placeholders and are never loaded.
+// selected (mask bit, or row < nrows without a mask), its aggregate's condition
+// (if any: DevAgg::cond) holds there and its operand column(s) are valid
+// there: values at NULL rows are placeholders and are never loaded.
 // The reduction order inside a vector is fixed (lane: its four rows in order;
 // wave: xor butterfly 32..1; block: waves 0..3 in order), so a vector's record
 // depends on that vector's rows alone -- binary64 sums included.
@@ -36,7 +37,7 @@ struct DevFactor {            // 24 B
 };
 
 // One aggregate of a batch as the kernel sees it.
-struct DevAgg {               // 120 B
+struct DevAgg {               // 128 B
     const uint8_t *col;       // decoded operand column of the batch in HBM (row 0 of the batch);
                               // unused by the counts
     const uint8_t *col2;      // SUM_PRODUCT: the second operand
@@ -52,9 +53,13 @@ struct DevAgg {               // 120 B
     uint8_t fkind[kMaxFactors]; // FK_INT / FK_UINT
     uint8_t fneg[kMaxFactors];  // 1: sign = -1
     DevFactor f[kMaxFactors];
+    // the aggregate's condition (agg FILTER (WHERE cond), fls_cond.hip): its plane of
+    // `where & cond` words for the batch rows (HBM, 16 per vector), or NULL: no condition
+    const uint64_t *cond;
 };
 static_assert(sizeof(DevFactor) == 24, "DevFactor is 24 B");
-static_assert(sizeof(DevAgg) == 120 && offsetof(DevAgg, f) == 48, "DevAgg is 48 B + 3 factors");
+static_assert(sizeof(DevAgg) == 128 && offsetof(DevAgg, f) == 48 && offsetof(DevAgg, cond) == 120,
+              "DevAgg is 48 B + 3 factors + the condition's plane");
 
 // Partial result of one aggregate over one vector.
 //   counts:            count only

@@ -6,6 +6,8 @@
 //   fls_launch.hip        the launch policy and the launches of one decode
 //                         (launch_policy, order_for_launch, launch_all), over
 //                         the hooks of fls_tuning.hpp
+//   fls_cond.hip          (kernel) the aggregates' conditions; their host half,
+//                         enqueue_conditions, sits beside enqueue_filter
 //   fls_scan_agg.hip      fls_aggregate / fls_aggregate_grouped: checks,
 //                         per-batch enqueue, the host fold
 //   fls_scan_hashagg.hip  fls_aggregate_hashed: checks, the key layout, the
@@ -351,6 +353,11 @@ struct Slot {                       // one batch of row groups in flight
     PinBuf<DevAgg> h_adesc;
     DevBuf<DevAgg> d_adesc;
     DevBuf<AggRec> d_agg;           // partial records of the batch
+    // the aggregates' conditions (fls_aggregate_conditions)
+    PinBuf<uint8_t> h_qdesc;        // DevTerm[] + DevColTerm[] + DevSetTerm[] + DevPatTerm[], then strings and tokens
+    DevBuf<uint8_t> d_qdesc;
+    DevBuf<uint64_t> d_cond;        // per condition a plane of 16 words per vector: where & cond
+    DevBuf<uint32_t> d_ccounts;     // the narrowing kernels' per-vector counts of a plane (scratch)
     // grouped aggregate batches (fls_aggregate_grouped)
     PinBuf<uint8_t> h_gdesc;        // DevKey[kMaxKeys] + per row group its first vector and vector count
     DevBuf<uint8_t> d_gdesc;
@@ -537,6 +544,7 @@ struct HostAgg {
     uint32_t fcol[kMaxFactors] = {};
     uint8_t fneg[kMaxFactors] = {};
     int64_t fk[kMaxFactors] = {};
+    uint32_t cond = 0;              // 0: none, else condition cond - 1 of the scan's list (ScanCtx::conds)
 };
 
 // What a scan does with a batch's decoded rows instead of delivering them.
@@ -576,6 +584,8 @@ struct ScanPlan {
     // and the scans the engine runs for itself deliver at full width
     bool delivering_scan = false;
     const std::vector<HostAgg> *aggs = nullptr;     // Reduce::Aggregate / GroupAggregate / HashAggregate
+    // the conditions HostAgg::cond numbers (NULL: none); they prune nothing and select no row
+    const std::vector<std::vector<HostTerm>> *conds = nullptr;
     // Reduce::GroupAggregate: the GROUP BY keys, a column each or
     // FLS_KEY_MAPPED | i for binding i of binds
     const std::vector<uint32_t> *keys = nullptr;
@@ -599,6 +609,10 @@ struct ScanCtx {
     // aggregate scan (Reduce::Aggregate / GroupAggregate): no column is
     // delivered, each batch's partial records ride in its HostBatch
     std::vector<HostAgg> aggs;
+    // ... and the conditions their HostAgg::cond numbers, each a filter of its
+    // own sorted by clause: their columns are decoded and their validity
+    // staged like the filter's, per batch they become planes (enqueue_conditions)
+    std::vector<std::vector<HostTerm>> conds;
     // GROUP BY columns of a grouped aggregate scan (Reduce::GroupAggregate):
     // decoded like operands, VARCHAR keys as dictionary codes
     std::vector<uint32_t> keys;
@@ -758,6 +772,7 @@ struct fls_table {
     fls::engine::ScanCtx scan, mat;
     std::vector<fls::engine::HostTerm> filter;  // fls_scan_filter: applies to the next fls_scan_begin / fls_aggregate
     std::vector<fls_agg_expr> exprs;  // fls_aggregate_exprs: what FLS_AGG_SUM_EXPR's spec.col indexes
+    std::vector<std::vector<fls::engine::HostTerm>> conds;  // fls_aggregate_conditions: what spec.cond - 1 indexes
     std::vector<fls::engine::HostBinding> bindings;  // fls_aggregate_key_bindings: what FLS_KEY_MAPPED | i names
     bool dict_codes = false;        // fls_scan_dict_codes: applies to the next fls_scan_begin
     bool narrow = false;            // fls_scan_narrow: applies to the next fls_scan_begin
@@ -833,6 +848,9 @@ bool agg_is_float(const fls_table *t, const HostAgg &h);
 // The aggregates of a batch as the kernels see them (sl.h_adesc -> sl.d_adesc
 // on the slot's stream), over the slot's decoded columns and staged validity.
 int upload_agg_descs(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl);
+// The conditions the aggregates ha name, out of the table's list, into `used`
+// (what ScanPlan::conds takes), ha[i].cond renumbered to index it.
+void used_conditions(const fls_table *t, std::vector<HostAgg> &ha, std::vector<std::vector<HostTerm>> &used);
 
 // ---- mapped GROUP BY keys (fls_scan_keymap.hip) ---------------------------------
 

@@ -217,6 +217,23 @@ enum : uint32_t { KERR_PATTERN = 8192 };
 hipError_t launch_strmatch(const DevPatTerm *d_terms, uint32_t nterms, uint32_t total_tokens, uint32_t nrows,
                            uint64_t *d_mask, uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
 
+// The conditions of a call's aggregates (fls_aggregate_conditions) as
+// cond_kernel sees them: condition c's ordinary terms are terms[first[c] ..
+// first[c + 1]), the last term of each clause marked end_clause (a condition
+// without ordinary terms has an empty range: its plane is the scan's mask).
+constexpr uint32_t kMaxConds = 8;
+struct CondList {
+    uint32_t first[kMaxConds + 1];
+    uint32_t n;
+};
+// One plane per condition, d_planes[c * 16 * nvec + 16 * v + word] =
+// mask word & condition c over the word's rows, for the nrows decoded rows of
+// a batch (nvec = its 1024-row vectors); d_mask as launch_aggregate takes it
+// (nullptr: every row below nrows).  One launch for all conditions
+// (fls_cond.hip).
+hipError_t launch_conditions(const DevTerm *d_terms, const CondList &conds, uint32_t nrows, const uint64_t *d_mask,
+                             uint64_t *d_planes, uint32_t *d_err, hipStream_t stream);
+
 // Narrowed delivery (fls_scan_narrow): an integer column of a batch whose
 // values, per row group, lie in [base, base + 2^(8 nw)) crosses PCIe as the
 // nw-byte differences value - base (the host adds the base back).  Reads ob

@@ -162,6 +162,7 @@ __global__ __launch_bounds__(256) void group_vector_kernel(const DevKey *__restr
 #pragma unroll
             for (uint32_t k = 0; k < 4; ++k) {
                 cm[k] = sel[k];
+                if (g.cond) cm[k] &= g.cond[(size_t)v * 16 + 4 * w + k];
                 for (uint32_t i = 0; i < g.nf; ++i)
                     if (g.f[i].valid) cm[k] &= g.f[i].valid[(size_t)v * 16 + 4 * w + k];
             }
@@ -171,6 +172,7 @@ __global__ __launch_bounds__(256) void group_vector_kernel(const DevKey *__restr
             for (uint32_t k = 0; k < 4; ++k) {
                 const uint32_t word = 4 * w + k;
                 uint64_t m = sel[k];
+                if (g.cond) m &= g.cond[(size_t)v * 16 + word];
                 if (fn != AGG_COUNT_STAR) {
                     if (g.valid) m &= g.valid[(size_t)v * 16 + word];
                     if (fn == AGG_SUM_PRODUCT && g.valid2) m &= g.valid2[(size_t)v * 16 + word];

@@ -137,6 +137,7 @@ __global__ __launch_bounds__(256) void hash_insert_kernel(const DevHashKey *__re
             const DevHashFields fl = fields[a];
             const uint32_t fn = g.fn;
             uint64_t c = m;  // the word's contributing rows
+            if (g.cond) c &= g.cond[(size_t)v * 16 + word];
             if (fn == AGG_SUM_EXPR) {
                 for (uint32_t i = 0; i < g.nf; ++i)
                     if (g.f[i].valid) c &= g.f[i].valid[(size_t)v * 16 + word];

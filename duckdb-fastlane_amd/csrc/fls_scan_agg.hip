@@ -25,6 +25,8 @@ int upload_agg_descs(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl) {
         DevAgg &da = sl.h_adesc.p[i];
         memset(&da, 0, sizeof(da));
         da.fn = a.fn;
+        // (enqueue_conditions wrote the planes: 16 words per vector and condition)
+        if (a.cond) da.cond = sl.d_cond.p + (size_t)(a.cond - 1) * 16 * sl.hb->nvec;
         if (a.fn == AGG_COUNT_STAR) continue;
         if (a.fn == AGG_SUM_EXPR) {
             da.nf = (uint8_t)a.nf;
@@ -62,7 +64,7 @@ int upload_agg_descs(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl) {
 int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
     HostBatch &hb = *sl.hb;
     const bool filtered = !s.terms.empty();
-    if (!filtered)  // (enqueue_filter staged the filter's and the operands' validity together)
+    if (!filtered && s.conds.empty())  // (enqueue_filter, or fill_batch for the conditions, staged every validity together)
         if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
     const uint32_t na = (uint32_t)s.aggs.size();
     hb.nvec = (uint32_t)((rows + 1023) / 1024);
@@ -107,7 +109,7 @@ static KeyLayout key_layout(const fls_table *t, const std::vector<uint32_t> &key
 int enqueue_group_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
     HostBatch &hb = *sl.hb;
     const bool filtered = s.masked();
-    if (!filtered)  // (enqueue_filter staged the filter's, the operands' and the keys' validity together)
+    if (!filtered && s.conds.empty())  // (enqueue_filter, or fill_batch for the conditions, staged every validity together)
         if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
     const std::vector<uint8_t> &need = sl.valid_staged;
     const uint32_t na = (uint32_t)s.aggs.size(), nk = (uint32_t)s.keys.size();
@@ -232,6 +234,10 @@ int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_sp
         const fls_aggregate_spec &a = aggs[i];
         if (a.fn > FLS_AGG_SUM_EXPR) return fail(FLS_ERR_ARG, "aggregate %u: unknown function %u", i, a.fn);
         ha[i].fn = a.fn;
+        if (a.cond > t->conds.size())
+            return fail(FLS_ERR_ARG, "aggregate %u: condition %u out of range (%u set by fls_aggregate_conditions)", i,
+                        a.cond - 1, (uint32_t)t->conds.size());
+        ha[i].cond = a.cond;
         if (a.fn == FLS_AGG_COUNT_STAR) continue;
         if (a.fn == FLS_AGG_SUM_EXPR) {  // (fls_aggregate_exprs checked the factors)
             if (a.col >= t->exprs.size())
@@ -292,6 +298,20 @@ int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_sp
                         ha[i].col2);
     }
     return 0;
+}
+
+void used_conditions(const fls_table *t, std::vector<HostAgg> &ha, std::vector<std::vector<HostTerm>> &used) {
+    std::vector<uint32_t> at(t->conds.size(), 0);  // 1 + the condition's place in `used`
+    used.clear();
+    for (HostAgg &h : ha) {
+        if (!h.cond) continue;
+        uint32_t &p = at[h.cond - 1];
+        if (!p) {
+            used.push_back(t->conds[h.cond - 1]);
+            p = (uint32_t)used.size();
+        }
+        h.cond = p;
+    }
 }
 
 bool agg_is_float(const fls_table *t, const HostAgg &h) {
@@ -411,10 +431,13 @@ int fls_aggregate(fls_table *t, const fls_aggregate_spec *aggs, uint32_t n, uint
     if (!t || !aggs || !out) return fail(FLS_ERR_ARG, "fls_aggregate: NULL argument");
     std::vector<HostAgg> ha;
     if (int rc = check_aggregates(t, "fls_aggregate", aggs, n, rg_begin, rg_end, ha)) return rc;
+    std::vector<std::vector<HostTerm>> conds;
+    used_conditions(t, ha, conds);
     ScanPlan plan;
     plan.rg0 = rg_begin;
     plan.rg1 = rg_end;
     plan.aggs = &ha;
+    plan.conds = &conds;
     // fold the per-vector records in row order
     std::vector<AggAcc> acc;
     for (uint32_t i = 0; i < n; ++i) acc.emplace_back(ha[i].fn);
@@ -486,10 +509,25 @@ int fls_aggregate_grouped(fls_table *t, const uint32_t *keys, uint32_t nkeys, co
                             "key, 16 per VARCHAR or mapped key, 1 per key for NULL)", q, L.total);
     std::vector<HostAgg> ha;
     if (int rc = check_aggregates(t, "fls_aggregate_grouped", aggs, n, rg_begin, rg_end, ha)) return rc;
+    std::vector<std::vector<HostTerm>> conds;
+    used_conditions(t, ha, conds);
+    // (the filter's rule above: a condition's term needs the column decoded as strings)
+    for (uint32_t q = 0; q < nkeys; ++q) {
+        if ((hk[q] & FLS_KEY_MAPPED) || t->meta.cols[hk[q]].type != TY_VARCHAR) continue;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!ha[i].cond) continue;
+            for (const HostTerm &h : conds[ha[i].cond - 1])
+                if (h.col == hk[q])
+                    return fail(FLS_ERR_ARG,
+                                "key %u: VARCHAR column %u is read by a term of condition %u, which needs it decoded as "
+                                "strings, not as the dictionary codes a key is made of", q, hk[q], aggs[i].cond - 1);
+        }
+    }
     ScanPlan plan;
     plan.rg0 = rg_begin;
     plan.rg1 = rg_end;
     plan.aggs = &ha;
+    plan.conds = &conds;
     plan.keys = &hk;
     plan.binds = &binds;
     auto res = std::make_unique<fls_group_result>();

@@ -33,7 +33,7 @@ FLS_ENGINE_BEGIN
 int enqueue_hash_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
     HostBatch &hb = *sl.hb;
     const bool filtered = s.masked();
-    if (!filtered)  // (enqueue_filter staged the filter's, the operands' and the keys' validity together)
+    if (!filtered && s.conds.empty())  // (enqueue_filter, or fill_batch for the conditions, staged every validity together)
         if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
     const std::vector<uint8_t> &need = sl.valid_staged;
     const uint32_t na = (uint32_t)s.aggs.size(), nk = (uint32_t)s.keys.size();
@@ -155,6 +155,7 @@ struct HashCall {
     uint64_t max_groups = 0;
     std::vector<uint32_t> hk;
     std::vector<HostAgg> ha;
+    std::vector<std::vector<HostTerm>> conds;  // the conditions ha[i].cond numbers
     HashPlan H;
     std::vector<uint8_t> fop;               // per field of a slot: how the merge combines it (FieldOp)
     std::vector<DevBuf<uint64_t>> tables;   // per pipeline; none without a row group to read
@@ -205,6 +206,7 @@ int hash_check(fls_table *t, const uint32_t *keys, uint32_t nkeys, const fls_agg
     }
     if (int rc = hash_key_layout(t, hk, rg_begin, rg_end, H)) return rc;
     if (int rc = check_aggregates(t, "fls_aggregate_hashed", aggs, n, rg_begin, rg_end, ha)) return rc;
+    used_conditions(t, ha, c.conds);
     for (uint32_t i = 0; i < n; ++i)
         if (ha[i].fn == AGG_SUM && agg_is_float(t, ha[i]))
             return fail(FLS_ERR_ARG, "aggregate %u: SUM of FLOAT / DOUBLE column %u is order-dependent under atomic "
@@ -271,6 +273,7 @@ int hash_scan(HashCall &c) {
     plan.rg0 = rg_begin;
     plan.rg1 = rg_end;
     plan.aggs = &c.ha;
+    plan.conds = &c.conds;
     plan.keys = &c.hk;
     plan.max_groups = max_groups;
     plan.hash = &H;

@@ -157,7 +157,7 @@ static size_t pinned_bytes(const ScanDev &d) {
     size_t t = 0;
     for (auto &b : d.batches) t += pinned_bytes(*b);
     for (auto &sl : d.slots)
-        t += sl.h_chunks.n * sizeof(DevChunk) + sl.h_stage.n + sl.h_fdesc.n + sl.h_adesc.n * sizeof(DevAgg) +
+        t += sl.h_chunks.n * sizeof(DevChunk) + sl.h_stage.n + sl.h_fdesc.n + sl.h_qdesc.n + sl.h_adesc.n * sizeof(DevAgg) +
              sl.h_gdesc.n + sl.h_tdesc.n * sizeof(uint32_t);
     return t;
 }
@@ -778,6 +778,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
         if (h.op < OP_IS_NULL || is_set_op(h.op) || is_pat_op(h.op)) s.dmask[h.col] = 1;
         else if (is_col_op(h.op)) s.dmask[h.col] = s.dmask[h.col2] = 1;
     s.aggs.clear();
+    s.conds.clear();
     s.keys.clear();
     s.binds.clear();
     s.tk = 0;
@@ -808,6 +809,13 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
         // an aggregate scan decodes the filter's columns and the numeric
         // operands (a COUNT reads its column's validity only)
         s.aggs = *p.aggs;
+        // the conditions' columns are decoded like the filter's, for the row
+        // groups the scan reads: a condition prunes nothing
+        if (p.conds) s.conds = *p.conds;
+        for (auto &q : s.conds)
+            for (auto &h : q)
+                if (h.op < OP_IS_NULL || is_set_op(h.op) || is_pat_op(h.op)) s.dmask[h.col] = 1;
+                else if (is_col_op(h.op)) s.dmask[h.col] = s.dmask[h.col2] = 1;
         for (auto &a : s.aggs) {
             if (a.fn == AGG_SUM_EXPR) {
                 for (uint32_t i = 0; i < a.nf; ++i) s.dmask[a.fcol[i]] = 1;
@@ -924,7 +932,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
 }
 
 // Validity words of the batch rows (HBM, sl.d_valid[c]) for every column the
-// filter's terms or the aggregates' operands read that has a NULL in the
+// filter's terms, the aggregates' conditions or their operands read that has a NULL in the
 // batch (row groups start at whole vectors: rows / 64 words apart);
 // sl.valid_staged[c] ends up 1 for the columns staged.
 int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
@@ -936,6 +944,11 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
         need[h.col] = 1;
         if (is_col_op(h.op)) need[h.col2] = 1;
     }
+    for (auto &q : s.conds)
+        for (auto &h : q) {
+            need[h.col] = 1;
+            if (is_col_op(h.op)) need[h.col2] = 1;
+        }
     for (auto &a : s.aggs) {
         if (a.fn == AGG_SUM_EXPR) {
             for (uint32_t i = 0; i < a.nf; ++i) need[a.fcol[i]] = 1;
@@ -986,6 +999,96 @@ int rg_vec_table(const fls_table *t, const Slot &sl, uint32_t *tab, uint32_t &rg
     return 0;
 }
 
+// One term of a filter or of an aggregate's condition as its kernel sees it,
+// over the slot's decoded columns and staged validity (stage_validity ran).
+static int fill_set_term(const fls_table *t, ScanDev &d, Slot &sl, const HostTerm &h, DevSetTerm &ds) {
+    const std::vector<uint8_t> &need = sl.valid_staged;
+    const KeysetImage &ki = h.set->img;
+    memset(&ds, 0, sizeof(ds));
+    ds.col = sl.d_out[h.col].p;
+    ds.valid = need[h.col] ? sl.d_valid[h.col].p : nullptr;
+    HIP_TRY(h.set->device_image(d.dev, &ds.table));
+    ds.min = ki.min;
+    ds.span = ki.span;
+    ds.empty = ki.empty;
+    ds.cap_log2 = ki.cap_log2;
+    ds.max_probe = ki.max_probe;
+    ds.form = (uint8_t)ki.form;
+    ds.ob = (uint8_t)out_bytes_of(t, h.col);
+    ds.sign = ki.is_signed ? 1 : 0;
+    ds.negate = h.op == OP_NOT_IN_SET ? 1 : 0;
+    return 0;
+}
+
+// (the full decoded values of both sides, never a narrowed copy)
+static void fill_col_term(const fls_table *t, Slot &sl, const HostTerm &h, DevColTerm &dc) {
+    const std::vector<uint8_t> &need = sl.valid_staged;
+    memset(&dc, 0, sizeof(dc));
+    dc.a = sl.d_out[h.col].p;
+    dc.b = sl.d_out[h.col2].p;
+    dc.va = need[h.col] ? sl.d_valid[h.col].p : nullptr;
+    dc.vb = need[h.col2] ? sl.d_valid[h.col2].p : nullptr;
+    dc.oba = (uint8_t)out_bytes_of(t, h.col);
+    dc.obb = (uint8_t)out_bytes_of(t, h.col2);
+    dc.kind = h.kind;
+    dc.op = (uint8_t)(h.op - OP_COL_EQ);
+    dc.f32a = t->meta.cols[h.col].type == TY_FLOAT ? 1 : 0;
+    dc.f32b = t->meta.cols[h.col2].type == TY_FLOAT ? 1 : 0;
+}
+
+// Where the long strings of string column c of the batch live: a batch can
+// hold DICT and FSST chunks of the column (ENC_AUTO chooses per chunk), so
+// both ranges, each with its own device offset.
+static void string_ranges(const fls_table *t, Slot &sl, uint32_t c, uint64_t in_lo, uint64_t in_len, StrRange &heap,
+                          StrRange &image) {
+    if (sl.heap_bytes[c]) {  // FSST rows: long strings live in the batch heap
+        heap.host_lo = (uint64_t)(uintptr_t)sl.hb->h_heap[c].p;
+        heap.host_hi = heap.host_lo + sl.heap_bytes[c];
+        heap.dev_delta = (int64_t)((uintptr_t)sl.d_heap[c].p - (uintptr_t)sl.hb->h_heap[c].p);
+    }
+    // DICT rows: long strings point into the file image, uploaded as d_in
+    image.host_lo = (uint64_t)(uintptr_t)(t->img + in_lo);
+    image.host_hi = image.host_lo + in_len;
+    image.dev_delta = (int64_t)((uintptr_t)sl.in_dev - (uintptr_t)(t->img + in_lo));
+}
+
+// d_tok: where the term's tokens go in HBM
+static void fill_pat_term(const fls_table *t, Slot &sl, const HostTerm &h, uint64_t in_lo, uint64_t in_len,
+                          const uint16_t *d_tok, DevPatTerm &dp) {
+    const std::vector<uint8_t> &need = sl.valid_staged;
+    const CompiledPattern &cp = *h.pat;
+    memset(&dp, 0, sizeof(dp));
+    dp.col = sl.d_out[h.col].p;
+    dp.valid = need[h.col] ? sl.d_valid[h.col].p : nullptr;
+    string_ranges(t, sl, h.col, in_lo, in_len, dp.heap, dp.image);
+    dp.tok = d_tok;
+    dp.ntok = (uint32_t)cp.tok.size();
+    dp.min_len = cp.min_len;
+    dp.prefix_len = (uint8_t)std::min<size_t>(4, cp.prefix.size());
+    memcpy(&dp.prefix, cp.prefix.data(), dp.prefix_len);
+    dp.negate = h.op == OP_NOT_LIKE ? 1 : 0;
+    dp.exact = cp.exact ? 1 : 0;
+}
+
+// d_str: where an FK_STR term's constant bytes go in HBM
+static void fill_term(const fls_table *t, Slot &sl, const HostTerm &h, uint64_t in_lo, uint64_t in_len,
+                      const uint8_t *d_str, bool end_clause, DevTerm &dt) {
+    const std::vector<uint8_t> &need = sl.valid_staged;
+    memset(&dt, 0, sizeof(dt));
+    dt.col = sl.d_out[h.col].p;
+    dt.value = h.value;
+    dt.kind = h.kind;
+    dt.op = h.op;
+    dt.ob = (uint8_t)out_bytes_of(t, h.col);
+    dt.end_clause = end_clause ? 1 : 0;
+    dt.valid = need[h.col] ? sl.d_valid[h.col].p : nullptr;
+    if (h.kind == FK_STR) {
+        dt.str = d_str;
+        dt.str_len = (uint32_t)h.str.size();
+        string_ranges(t, sl, h.col, in_lo, in_len, dt.heap, dt.image);
+    }
+}
+
 // Filter descriptors of a batch: the terms over the slot's decoded columns,
 // the delivered columns' compaction targets, then the constant strings.
 static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo, uint64_t in_len) {
@@ -1001,7 +1104,6 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
         outs.push_back(o);
     }
     if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
-    const std::vector<uint8_t> &need = sl.valid_staged;
     // key-set terms (each a clause of its own) go to keyset_kernel, the rest
     // to filter_kernel, which with no term left writes the row < nrows mask;
     // pattern terms (a clause each too) go to strmatch_kernel after both.
@@ -1025,44 +1127,14 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
         HIP_TRY(sl.h_sdesc.alloc(ns));
         HIP_TRY(sl.d_sdesc.alloc(d.dev, ns));
     }
-    for (size_t i = 0; i < ns; ++i) {
-        const HostTerm &h = *sets[i];
-        const KeysetImage &ki = h.set->img;
-        DevSetTerm &ds = sl.h_sdesc.p[i];
-        memset(&ds, 0, sizeof(ds));
-        ds.col = sl.d_out[h.col].p;
-        ds.valid = need[h.col] ? sl.d_valid[h.col].p : nullptr;
-        HIP_TRY(h.set->device_image(d.dev, &ds.table));
-        ds.min = ki.min;
-        ds.span = ki.span;
-        ds.empty = ki.empty;
-        ds.cap_log2 = ki.cap_log2;
-        ds.max_probe = ki.max_probe;
-        ds.form = (uint8_t)ki.form;
-        ds.ob = (uint8_t)out_bytes_of(t, h.col);
-        ds.sign = ki.is_signed ? 1 : 0;
-        ds.negate = h.op == OP_NOT_IN_SET ? 1 : 0;
-    }
+    for (size_t i = 0; i < ns; ++i)
+        if (int rc = fill_set_term(t, d, sl, *sets[i], sl.h_sdesc.p[i])) return rc;
     // column terms: the full decoded values of both sides (never a narrowed copy)
     if (nc) {
         HIP_TRY(sl.h_cdesc.alloc(nc));
         HIP_TRY(sl.d_cdesc.alloc(d.dev, nc));
     }
-    for (size_t i = 0; i < nc; ++i) {
-        const HostTerm &h = *ccs[i];
-        DevColTerm &dc = sl.h_cdesc.p[i];
-        memset(&dc, 0, sizeof(dc));
-        dc.a = sl.d_out[h.col].p;
-        dc.b = sl.d_out[h.col2].p;
-        dc.va = need[h.col] ? sl.d_valid[h.col].p : nullptr;
-        dc.vb = need[h.col2] ? sl.d_valid[h.col2].p : nullptr;
-        dc.oba = (uint8_t)out_bytes_of(t, h.col);
-        dc.obb = (uint8_t)out_bytes_of(t, h.col2);
-        dc.kind = h.kind;
-        dc.op = (uint8_t)(h.op - OP_COL_EQ);
-        dc.f32a = t->meta.cols[h.col].type == TY_FLOAT ? 1 : 0;
-        dc.f32b = t->meta.cols[h.col2].type == TY_FLOAT ? 1 : 0;
-    }
+    for (size_t i = 0; i < nc; ++i) fill_col_term(t, sl, *ccs[i], sl.h_cdesc.p[i]);
     // pattern descriptors, then each term's tokens (16-byte aligned)
     size_t pat_bytes = np * sizeof(DevPatTerm), total_tokens = 0;
     for (auto *h : pats) pat_bytes += (h->pat->tok.size() * sizeof(uint16_t) + 15) & ~size_t(15);
@@ -1074,24 +1146,7 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
         const HostTerm &h = *pats[i];
         const CompiledPattern &cp = *h.pat;
         DevPatTerm dp;
-        memset(&dp, 0, sizeof(dp));
-        dp.col = sl.d_out[h.col].p;
-        dp.valid = need[h.col] ? sl.d_valid[h.col].p : nullptr;
-        if (sl.heap_bytes[h.col]) {  // FSST rows (as a string term's ranges below)
-            dp.heap.host_lo = (uint64_t)(uintptr_t)sl.hb->h_heap[h.col].p;
-            dp.heap.host_hi = dp.heap.host_lo + sl.heap_bytes[h.col];
-            dp.heap.dev_delta = (int64_t)((uintptr_t)sl.d_heap[h.col].p - (uintptr_t)sl.hb->h_heap[h.col].p);
-        }
-        dp.image.host_lo = (uint64_t)(uintptr_t)(t->img + in_lo);
-        dp.image.host_hi = dp.image.host_lo + in_len;
-        dp.image.dev_delta = (int64_t)((uintptr_t)sl.in_dev - (uintptr_t)(t->img + in_lo));
-        dp.tok = (const uint16_t *)(sl.d_pdesc.p + po);
-        dp.ntok = (uint32_t)cp.tok.size();
-        dp.min_len = cp.min_len;
-        dp.prefix_len = (uint8_t)std::min<size_t>(4, cp.prefix.size());
-        memcpy(&dp.prefix, cp.prefix.data(), dp.prefix_len);
-        dp.negate = h.op == OP_NOT_LIKE ? 1 : 0;
-        dp.exact = cp.exact ? 1 : 0;
+        fill_pat_term(t, sl, h, in_lo, in_len, (const uint16_t *)(sl.d_pdesc.p + po), dp);
         memcpy(sl.h_pdesc.p + i * sizeof(DevPatTerm), &dp, sizeof(dp));
         if (!cp.tok.empty()) memcpy(sl.h_pdesc.p + po, cp.tok.data(), cp.tok.size() * sizeof(uint16_t));
         po += (cp.tok.size() * sizeof(uint16_t) + 15) & ~size_t(15);
@@ -1099,31 +1154,10 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
     }
     for (size_t i = 0; i < nt; ++i) {
         const HostTerm &h = *ord[i];
-        DevTerm &dt = terms[i];
-        memset(&dt, 0, sizeof(dt));
-        dt.col = sl.d_out[h.col].p;
-        dt.value = h.value;
-        dt.kind = h.kind;
-        dt.op = h.op;
-        dt.ob = (uint8_t)out_bytes_of(t, h.col);
-        dt.end_clause = (i + 1 == nt || ord[i + 1]->clause != h.clause) ? 1 : 0;
-        dt.valid = need[h.col] ? sl.d_valid[h.col].p : nullptr;
+        fill_term(t, sl, h, in_lo, in_len, sl.d_fdesc.p + so, i + 1 == nt || ord[i + 1]->clause != h.clause, terms[i]);
         if (h.kind == FK_STR) {
             memcpy(fd + so, h.str.data(), h.str.size());
-            dt.str = sl.d_fdesc.p + so;
-            dt.str_len = (uint32_t)h.str.size();
             so += (h.str.size() + 15) & ~size_t(15);
-            // a batch can hold DICT and FSST chunks of the column (ENC_AUTO
-            // chooses per chunk): both ranges, each with its own device offset
-            if (sl.heap_bytes[h.col]) {  // FSST rows: long strings live in the batch heap
-                dt.heap.host_lo = (uint64_t)(uintptr_t)sl.hb->h_heap[h.col].p;
-                dt.heap.host_hi = dt.heap.host_lo + sl.heap_bytes[h.col];
-                dt.heap.dev_delta = (int64_t)((uintptr_t)sl.d_heap[h.col].p - (uintptr_t)sl.hb->h_heap[h.col].p);
-            }
-            // DICT rows: long strings point into the file image, uploaded as d_in
-            dt.image.host_lo = (uint64_t)(uintptr_t)(t->img + in_lo);
-            dt.image.host_hi = dt.image.host_lo + in_len;
-            dt.image.dev_delta = (int64_t)((uintptr_t)sl.in_dev - (uintptr_t)(t->img + in_lo));
         }
     }
     memcpy(fd + nt * sizeof(DevTerm), outs.data(), no * sizeof(DevOut));
@@ -1159,6 +1193,106 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
     HIP_TRY(hipMemcpyAsync(hb.h_counts.p, sl.d_counts.p, hb.nvec * sizeof(uint32_t), hipMemcpyDeviceToHost,
                            sl.stream));
     hb.sel_ready = false;
+    return 0;
+}
+
+// The conditions of an aggregate scan's batch (ScanCtx::conds): one plane of
+// `where & cond` words per condition into sl.d_cond, which upload_agg_descs
+// hands to the aggregates bound to it.  After the filter's kernels (the
+// planes start from the slot's mask; unfiltered: from row < nrows) and
+// stage_validity.  cond_kernel evaluates the ordinary terms of all conditions
+// in one launch; a condition's column, key-set and pattern terms then narrow
+// its plane through the filter's kernels, one launch per kind, in the
+// filter's order.  One descriptor block: DevTerm[], DevColTerm[], DevSetTerm[],
+// DevPatTerm[], then the constant strings and the pattern tokens.
+static int enqueue_conditions(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo,
+                              uint64_t in_len) {
+    const uint32_t nq = (uint32_t)s.conds.size();
+    if (nq == 0 || nq > kMaxConds) return fail(FLS_ERR_STATE, "internal: %u conditions in a scan", nq);
+    HostBatch &hb = *sl.hb;
+    hb.nvec = (uint32_t)((rows + 1023) / 1024);
+    struct Kinds {
+        std::vector<const HostTerm *> ord, ccs, sets, pats;
+    };
+    std::vector<Kinds> kinds(nq);
+    size_t nt = 0, nc = 0, ns = 0, np = 0, tail = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+        Kinds &k = kinds[q];
+        for (auto &h : s.conds[q])
+            (is_set_op(h.op) ? k.sets : is_pat_op(h.op) ? k.pats : is_col_op(h.op) ? k.ccs : k.ord).push_back(&h);
+        nt += k.ord.size();
+        nc += k.ccs.size();
+        ns += k.sets.size();
+        np += k.pats.size();
+        for (auto *h : k.ord) tail += (h->str.size() + 15) & ~size_t(15);
+        for (auto *h : k.pats) tail += (h->pat->tok.size() * sizeof(uint16_t) + 15) & ~size_t(15);
+    }
+    // (every descriptor size is a multiple of 16, DevTerm's and DevPatTerm's of 32: each array stays aligned)
+    const size_t off_c = nt * sizeof(DevTerm), off_s = off_c + nc * sizeof(DevColTerm);
+    const size_t off_p = (off_s + ns * sizeof(DevSetTerm) + 31) & ~size_t(31);
+    size_t so = off_p + np * sizeof(DevPatTerm);
+    const size_t bytes = so + tail;
+    HIP_TRY(sl.h_qdesc.alloc(bytes));
+    HIP_TRY(sl.d_qdesc.alloc(d.dev, bytes));
+    uint8_t *qd = sl.h_qdesc.p;
+    memset(qd, 0, bytes);
+    DevTerm *terms = (DevTerm *)qd;
+    DevColTerm *cterms = (DevColTerm *)(qd + off_c);
+    DevSetTerm *sterms = (DevSetTerm *)(qd + off_s);
+    CondList cl;
+    memset(&cl, 0, sizeof(cl));
+    cl.n = nq;
+    std::vector<uint32_t> ptok(nq, 0);  // tokens of each condition's pattern terms
+    size_t it = 0, ic = 0, is = 0, ip = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+        const Kinds &k = kinds[q];
+        cl.first[q] = (uint32_t)it;
+        for (size_t i = 0; i < k.ord.size(); ++i) {
+            const HostTerm &h = *k.ord[i];
+            fill_term(t, sl, h, in_lo, in_len, sl.d_qdesc.p + so, i + 1 == k.ord.size() || k.ord[i + 1]->clause != h.clause,
+                      terms[it++]);
+            if (h.kind == FK_STR) {
+                memcpy(qd + so, h.str.data(), h.str.size());
+                so += (h.str.size() + 15) & ~size_t(15);
+            }
+        }
+        for (auto *h : k.ccs) fill_col_term(t, sl, *h, cterms[ic++]);
+        for (auto *h : k.sets)
+            if (int rc = fill_set_term(t, d, sl, *h, sterms[is++])) return rc;
+        for (auto *h : k.pats) {
+            const CompiledPattern &cp = *h->pat;
+            DevPatTerm dp;
+            fill_pat_term(t, sl, *h, in_lo, in_len, (const uint16_t *)(sl.d_qdesc.p + so), dp);
+            memcpy(qd + off_p + ip++ * sizeof(DevPatTerm), &dp, sizeof(dp));
+            if (!cp.tok.empty()) memcpy(qd + so, cp.tok.data(), cp.tok.size() * sizeof(uint16_t));
+            so += (cp.tok.size() * sizeof(uint16_t) + 15) & ~size_t(15);
+            ptok[q] += (uint32_t)cp.tok.size();
+        }
+    }
+    cl.first[nq] = (uint32_t)it;
+    const size_t plane = (size_t)hb.nvec * 16;
+    HIP_TRY(sl.d_cond.alloc(d.dev, plane * nq));
+    HIP_TRY(sl.d_ccounts.alloc(d.dev, hb.nvec));
+    HIP_TRY(hipMemcpyAsync(sl.d_qdesc.p, qd, bytes, hipMemcpyHostToDevice, sl.stream));
+    HIP_TRY(launch_conditions((const DevTerm *)sl.d_qdesc.p, cl, (uint32_t)rows, s.masked() ? sl.d_mask.p : nullptr,
+                              sl.d_cond.p, d.err.p, sl.stream));
+    ic = is = ip = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+        const Kinds &k = kinds[q];
+        uint64_t *pl = sl.d_cond.p + plane * q;
+        if (!k.ccs.empty())
+            HIP_TRY(launch_colcmp((const DevColTerm *)(sl.d_qdesc.p + off_c) + ic, (uint32_t)k.ccs.size(), (uint32_t)rows,
+                                  pl, sl.d_ccounts.p, d.err.p, sl.stream));
+        if (!k.sets.empty())
+            HIP_TRY(launch_keyset((const DevSetTerm *)(sl.d_qdesc.p + off_s) + is, (uint32_t)k.sets.size(), (uint32_t)rows,
+                                  pl, sl.d_ccounts.p, d.err.p, sl.stream));
+        if (!k.pats.empty())
+            HIP_TRY(launch_strmatch((const DevPatTerm *)(sl.d_qdesc.p + off_p) + ip, (uint32_t)k.pats.size(), ptok[q],
+                                    (uint32_t)rows, pl, sl.d_ccounts.p, d.err.p, sl.stream));
+        ic += k.ccs.size();
+        is += k.sets.size();
+        ip += k.pats.size();
+    }
     return 0;
 }
 
@@ -1280,6 +1414,11 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
         in_term[h.col] = 1;
         if (is_col_op(h.op)) in_term[h.col2] = 1;
     }
+    for (auto &q : s.conds)
+        for (auto &h : q) {
+            in_term[h.col] = 1;
+            if (is_col_op(h.op)) in_term[h.col2] = 1;
+        }
     for (uint32_t c : s.keys)
         if (!(c & FLS_KEY_MAPPED)) is_key[c] = 1;
     for (uint32_t c = 0; c < ncols; ++c) {
@@ -1482,6 +1621,12 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
         if (rc) return rc;
     }
     // 3b. a reducing scan: reduce under the mask; what it leaves is the batch's only D2H
+    if (!s.conds.empty()) {
+        // the aggregates' conditions first: their planes, from the mask (or every row)
+        if (!filtered)  // (else enqueue_filter staged every validity the scan reads)
+            if (int rc = stage_validity(t, s, d, sl, rows, lo)) return rc;
+        if (int rc = enqueue_conditions(t, s, d, sl, rows, lo, hi - lo)) return rc;
+    }
     {
         int rc = 0;
         switch (s.reduce) {
@@ -1873,11 +2018,14 @@ int scan_next(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
     return rc;
 }
 
-// fls_predicate[] -> host terms in the comparison domain, sorted by clause
-static int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std::vector<HostTerm> &out) {
+// fls_predicate[] -> host terms in the comparison domain, sorted by clause;
+// *at (if given): the term a refusal is about
+static int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std::vector<HostTerm> &out,
+                    uint32_t *at = nullptr) {
     out.clear();
     if (n && !p) return fail(FLS_ERR_ARG, "fls_scan_filter: NULL predicates");
     for (uint32_t i = 0; i < n; ++i) {
+        if (at) *at = i;
         if (p[i].col >= t->meta.cols.size()) return fail(FLS_ERR_ARG, "filter column %u out of range", p[i].col);
         if (p[i].op > FLS_CMP_COL_GE) return fail(FLS_ERR_ARG, "filter operator %u unknown", p[i].op);
         HostTerm h;
@@ -2298,6 +2446,28 @@ int fls_scan_filter(fls_table *t, const fls_predicate *preds, uint32_t n) {
     int rc = to_terms(t, preds, n, terms);
     if (rc) return rc;
     t->filter.swap(terms);
+    return 0;
+}
+
+int fls_aggregate_conditions(fls_table *t, const fls_predicate *preds, uint32_t npreds, const fls_agg_condition *conds,
+                             uint32_t nconds) {
+    if (!t || (!conds && nconds) || (!preds && npreds)) return fail(FLS_ERR_ARG, "fls_aggregate_conditions: NULL argument");
+    if (nconds > kMaxConds)
+        return fail(FLS_ERR_ARG, "fls_aggregate_conditions: %u conditions (at most %u)", nconds, kMaxConds);
+    std::vector<std::vector<HostTerm>> list(nconds);
+    for (uint32_t i = 0; i < nconds; ++i) {
+        const fls_agg_condition &c = conds[i];
+        if (c.n == 0) return fail(FLS_ERR_ARG, "condition %u: no term (a condition has at least one)", i);
+        if (c.first > npreds || c.n > npreds - c.first)
+            return fail(FLS_ERR_ARG, "condition %u: terms [%u, %llu) past the %u predicates", i, c.first,
+                        (unsigned long long)c.first + c.n, npreds);
+        uint32_t at = 0;
+        if (int rc = to_terms(t, preds + c.first, c.n, list[i], &at)) {
+            const std::string why = fls_last_error();  // (the filter's refusal, its term numbers local to the condition)
+            return fail(rc, "condition %u, term %u: %s", i, at, why.c_str());
+        }
+    }
+    t->conds.swap(list);
     return 0;
 }
 

@@ -12,6 +12,13 @@
 //               one for that column (TPC-H Q1's
 //               `sum(l_extendedprice * (1 - l_discount) * (1 + l_tax))`); each
 //               output column is named by the trimmed text of its item.
+//               An item may end in `FILTER (WHERE <filter text>)` (keywords in
+//               any case): the aggregate over the rows of the call's filter
+//               where that condition holds too, in the grammar of the third
+//               argument (IN lists, LIKE and column pairs included; no OR, no
+//               other parentheses).  Items with identical condition text share
+//               one condition (fls_aggregate_conditions, at most 8); the
+//               item's name and type are what they are without the clause.
 //   filter:     `term AND term ...`, a term `column op literal` (op one of
 //               = != <> < <= > >=) or `column IS [NOT] NULL`.  Literals by
 //               column type: integers, decimal numbers the column's scale
@@ -78,6 +85,11 @@ struct AggBindData : public TableFunctionData {
     std::vector<fls_predicate> preds;
     std::deque<string> pred_strs;        // VARCHAR constants the predicates point at
     std::shared_ptr<KeySets> pred_sets = std::make_shared<KeySets>();  // the key sets of the filter's IN lists
+    // the items' FILTER (WHERE ...) conditions: spec.cond - 1 indexes conds, which
+    // index cond_preds (fls_aggregate_conditions); cond_texts[i] is condition i as written
+    std::vector<fls_predicate> cond_preds;
+    std::vector<fls_agg_condition> conds;
+    vector<string> cond_texts;
     std::shared_ptr<AggTable> table;     // opened at bind (footer only)
     std::vector<uint32_t> keys;          // the group_by columns (empty: ungrouped, one row)
 };
@@ -256,6 +268,35 @@ void ParseAggregate(const Schema &sch, const string &item, fls_aggregate_spec &s
     }
 }
 
+// An item's trailing `FILTER (WHERE text)`: the aggregate before it into agg,
+// the condition's text into cond; false when the item has no such clause.
+bool SplitFilterClause(const string &item, string &agg, string &cond) {
+    agg = item;
+    // the aggregate ends at the parenthesis that closes its first one (its literals hold none)
+    size_t close = string::npos;
+    int depth = 0;
+    for (size_t i = 0; i < item.size() && close == string::npos; ++i) {
+        if (item[i] == '(') ++depth;
+        if (item[i] == ')' && --depth == 0) close = i;
+    }
+    if (close == string::npos || close + 1 == item.size()) return false;
+    const string rest = Trim(item.substr(close + 1));
+    if (rest.empty()) return false;
+    auto bad = [&]() {
+        return BinderException("fastlanes_aggregate: FILTER (WHERE ...) is expected after the aggregate at \"" + rest +
+                               "\" in \"" + item + "\"");
+    };
+    if (rest.size() < 6 || StringUtil::Lower(rest.substr(0, 6)) != "filter") throw bad();
+    const string paren = Trim(rest.substr(6));
+    if (paren.size() < 2 || paren.front() != '(' || paren.back() != ')') throw bad();
+    const string inner = Trim(paren.substr(1, paren.size() - 2));
+    if (inner.size() < 6 || StringUtil::Lower(inner.substr(0, 5)) != "where" || !isspace((unsigned char)inner[5])) throw bad();
+    cond = Trim(inner.substr(5));
+    if (cond.empty()) throw bad();
+    agg = item.substr(0, close + 1);
+    return true;
+}
+
 // the group_by text: 1 to 4 column names separated by commas
 void ParseGroupBy(const Schema &sch, const string &list, std::vector<uint32_t> &keys, vector<string> &names,
                   vector<LogicalType> &types) {
@@ -299,12 +340,16 @@ unique_ptr<FunctionData> AggBind(ClientContext &, TableFunctionBindInput &input,
         throw BinderException("Failed to open FastLanes file: " + bind->file);
     Schema sch;
     sch.Load(bind->table->table);
-    // the aggregate list: items separated by commas outside parentheses
+    // the aggregate list: items separated by commas outside parentheses and
+    // outside the quoted strings of a FILTER clause
     const string list = input.inputs[1].GetValue<string>();
     vector<string> items;
     int depth = 0;
+    bool quoted = false;
     size_t start = 0;
     for (size_t i = 0; i <= list.size(); ++i) {
+        if (i < list.size() && list[i] == '\'') quoted = !quoted;
+        if (i < list.size() && quoted) continue;
         if (i < list.size() && list[i] == '(') ++depth;
         if (i < list.size() && list[i] == ')') --depth;
         if (i == list.size() || (list[i] == ',' && depth == 0)) {
@@ -316,7 +361,25 @@ unique_ptr<FunctionData> AggBind(ClientContext &, TableFunctionBindInput &input,
         if (item.empty()) throw BinderException("fastlanes_aggregate: empty item in aggregate list \"" + list + "\"");
         fls_aggregate_spec spec;
         LogicalType type;
-        ParseAggregate(sch, item, spec, type, bind->exprs);
+        string agg, cond;
+        const bool conditioned = SplitFilterClause(item, agg, cond);
+        ParseAggregate(sch, agg, spec, type, bind->exprs);
+        if (conditioned) {
+            size_t k = 0;
+            while (k < bind->cond_texts.size() && bind->cond_texts[k] != cond) ++k;
+            if (k == bind->cond_texts.size()) {
+                if (k == 8)
+                    throw BinderException("fastlanes_aggregate: at most 8 different FILTER conditions per call, \"" + cond +
+                                          "\" of \"" + item + "\" is the 9th");
+                fls_agg_condition c;
+                c.first = (uint32_t)bind->cond_preds.size();
+                ParseFilter(sch, cond, bind->cond_preds, bind->pred_strs, "fastlanes_aggregate", conn, bind->pred_sets.get());
+                c.n = (uint32_t)bind->cond_preds.size() - c.first;
+                bind->conds.push_back(c);
+                bind->cond_texts.push_back(cond);
+            }
+            spec.cond = (uint32_t)k + 1;
+        }
         bind->specs.push_back(spec);
         bind->types.push_back(type);
         names.push_back(item);
@@ -378,13 +441,16 @@ void AggScanGrouped(const AggBindData &bind, AggGlobalState &g, DataChunk &outpu
     if (!g.done) {
         g.done = true;
         if (fls_scan_filter(t, bind.preds.data(), (uint32_t)bind.preds.size()) != 0 ||
-            fls_aggregate_exprs(t, bind.exprs.data(), (uint32_t)bind.exprs.size()) != 0)
+            fls_aggregate_exprs(t, bind.exprs.data(), (uint32_t)bind.exprs.size()) != 0 ||
+            fls_aggregate_conditions(t, bind.cond_preds.data(), (uint32_t)bind.cond_preds.size(), bind.conds.data(),
+                                     (uint32_t)bind.conds.size()) != 0)
             throw IOException(string("FastLanes aggregate failed: ") + fls_last_error());
         const int rc = fls_aggregate_grouped(t, bind.keys.data(), (uint32_t)bind.keys.size(), bind.specs.data(),
                                              (uint32_t)bind.specs.size(), 0, fls_table_nrowgroups(t), &g.groups);
         const string err = rc ? fls_last_error() : "";
         fls_scan_filter(t, nullptr, 0);
         fls_aggregate_exprs(t, nullptr, 0);
+        fls_aggregate_conditions(t, nullptr, 0, nullptr, 0);
         if (rc == FLS_ERR_LIMIT)
             throw InvalidInputException("fastlanes_aggregate: " + err +
                                         "; use SELECT ... FROM read_fastlanes(...) GROUP BY ... instead");
@@ -430,12 +496,15 @@ void AggScan(ClientContext &, TableFunctionInput &data, DataChunk &output) {
     fls_table *t = bind.table->table;
     std::vector<fls_aggregate_value> vals(bind.specs.size());
     if (fls_scan_filter(t, bind.preds.data(), (uint32_t)bind.preds.size()) != 0 ||
-        fls_aggregate_exprs(t, bind.exprs.data(), (uint32_t)bind.exprs.size()) != 0)
+        fls_aggregate_exprs(t, bind.exprs.data(), (uint32_t)bind.exprs.size()) != 0 ||
+        fls_aggregate_conditions(t, bind.cond_preds.data(), (uint32_t)bind.cond_preds.size(), bind.conds.data(),
+                                 (uint32_t)bind.conds.size()) != 0)
         throw IOException(string("FastLanes aggregate failed: ") + fls_last_error());
     const int rc = fls_aggregate(t, bind.specs.data(), (uint32_t)bind.specs.size(), 0, fls_table_nrowgroups(t), vals.data());
     const string err = rc ? fls_last_error() : "";
     fls_scan_filter(t, nullptr, 0);
     fls_aggregate_exprs(t, nullptr, 0);
+    fls_aggregate_conditions(t, nullptr, 0, nullptr, 0);
     if (rc == FLS_ERR_ARG) throw OutOfRangeException("fastlanes_aggregate: " + err);  // the SUM_PRODUCT / SUM_EXPR bound
     if (rc) throw IOException("FastLanes aggregate failed: " + err);
     for (idx_t j = 0; j < output.ColumnCount() && j < vals.size(); ++j) EmitValue(bind, j, vals[j], output.data[j], 0);

@@ -353,7 +353,10 @@ int fls_scan_pruned(const fls_table *t);
 typedef enum fls_agg_fn { FLS_AGG_COUNT_STAR = 0, FLS_AGG_COUNT = 1, FLS_AGG_SUM = 2,
                           FLS_AGG_MIN = 3, FLS_AGG_MAX = 4, FLS_AGG_SUM_PRODUCT = 5,
                           FLS_AGG_SUM_EXPR = 6 /* spec.col indexes the table's expression list */ } fls_agg_fn;
-typedef struct fls_aggregate_spec { uint8_t fn; uint8_t pad[3]; uint32_t col; uint32_t col2; uint32_t pad2; } fls_aggregate_spec;
+typedef struct fls_aggregate_spec {
+    uint8_t fn; uint8_t pad[3]; uint32_t col; uint32_t col2;
+    uint32_t cond;   /* 0: no condition; i: condition i - 1 of fls_aggregate_conditions (agg FILTER (WHERE ...)) */
+} fls_aggregate_spec;
 typedef enum fls_agg_kind { FLS_AGGV_NULL = 0, FLS_AGGV_INT = 1, FLS_AGGV_DOUBLE = 2 } fls_agg_kind;
 typedef struct fls_aggregate_value {
     uint64_t count;   /* rows that contributed */
@@ -385,6 +388,40 @@ int fls_aggregate(fls_table *t, const fls_aggregate_spec *aggs, uint32_t n,
 typedef struct fls_agg_factor { uint32_t col; int8_t sign; uint8_t pad[3]; int64_t k; } fls_agg_factor;   /* k + sign * column */
 typedef struct fls_agg_expr   { uint32_t nfactors; uint32_t pad; fls_agg_factor f[3]; } fls_agg_expr;     /* product of 1..3 factors */
 int fls_aggregate_exprs(fls_table *t, const fls_agg_expr *exprs, uint32_t n);
+/* Filtered aggregates: SQL's agg(...) FILTER (WHERE cond), in the following
+ * fls_aggregate, fls_aggregate_grouped and fls_aggregate_hashed[_select] calls
+ * (copied and replaced as a whole; at most 8 conditions; nconds = 0 clears;
+ * sticky like fls_aggregate_exprs; fls_topn and plain scans ignore the list).
+ * Condition i is a filter of its own, preds[first .. first + n) in the shape
+ * fls_scan_filter takes: a conjunction of clauses (`clause` numbers are local
+ * to the condition), a clause OR-ed `column op constant` / IS [NOT] NULL terms
+ * or a single key-set, LIKE or column-pair term; its key sets are kept alive
+ * as the filter keeps them.  An aggregate whose spec.cond is i + 1 counts a
+ * row when the scan's filter selects it, condition i is true there (a
+ * comparison on a NULL is not true) and its operands are valid there;
+ * COUNT_STAR under a condition counts the rows where the condition is true;
+ * spec.cond = 0 is the aggregate as before.  A condition prunes nothing and
+ * selects no row: row-group pruning, group membership (grouped and hashed) and
+ * the hashed call's first row follow the scan's filter alone, so a group in
+ * which no row meets the condition is there with count 0 and a NULL SUM / MIN
+ * / MAX.  The SUM_PRODUCT / SUM_EXPR overflow bounds ignore conditions (upper
+ * bounds over a superset of the rows), HAVING / ORDER BY see a conditioned
+ * aggregate like any other, and results are bit-identical across batch sizes,
+ * slots, pipelines and GPU counts as before.  On the GPU one launch per batch
+ * (csrc/fls_cond.hip) writes a plane of `filter & condition` words per
+ * condition, which the reduce kernels AND in where they AND validity; key-set,
+ * LIKE and column-pair terms narrow their plane through the filter's kernels.
+ * The columns conditions read are decoded only in row groups the scan reads.
+ * FLS_ERR_ARG before any device work: more than 8 conditions; "condition i:"
+ * n == 0 or a range past npreds; "condition i, term j: <the refusal
+ * fls_scan_filter gives the term>", j and the clause numbers local to the
+ * condition (the three "shares clause" refusals included); in the aggregate
+ * calls "aggregate i: condition k out of range (n set by
+ * fls_aggregate_conditions)"; in fls_aggregate_grouped a condition term that
+ * reads a VARCHAR key column (the filter's rule).  Not in the reference. */
+typedef struct fls_agg_condition { uint32_t first, n; } fls_agg_condition;   /* preds[first .. first + n) */
+int fls_aggregate_conditions(fls_table *t, const fls_predicate *preds, uint32_t npreds,
+                             const fls_agg_condition *conds, uint32_t nconds);
 /* GROUP BY keys[0..nkeys) of the same aggregates, for low-cardinality keys:
  * fls_aggregate's functions, filter, pruning, argument checks and numeric
  * results, per group.  The batch is reduced in HBM per (1024-row vector, key)
