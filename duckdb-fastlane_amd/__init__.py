@@ -160,6 +160,53 @@ class AggCondition(C.Structure):   # fls_agg_condition: preds[first .. first + n
 MAX_AGG_CONDITIONS = 8             # kMaxConds
 
 
+class FilterAlternative(C.Structure):   # fls_filter_alternative: preds[first .. first + n)
+    _fields_ = [("first", C.c_uint32), ("n", C.c_uint32)]
+
+
+MAX_FILTER_ALTERNATIVES = 8        # kMaxConds
+
+
+class AnyOf:
+    """(filt_1 OR filt_2 OR ...) as one element of a filter: each argument a
+    filter list as scan_filtered takes it (its terms AND-ed, clause numbers
+    its own), the element true on a row where at least one of them is; a row
+    counts once however many are.  At most one AnyOf per filter, of 1 to 8
+    alternatives, none of them holding an AnyOf itself:
+
+        filt = [(SHIPMODE, "=", "AIR"),
+                fl.AnyOf([(PARTKEY, "in_set", s1), (QTY, ">=", 1), (QTY, "<=", 11)],
+                         [(PARTKEY, "in_set", s2), (QTY, ">=", 10), (QTY, "<=", 20)])]
+
+    Accepted wherever a method takes filt (fls_scan_filter_alternatives); not
+    in When's condition nor in Table.may_match."""
+
+    def __init__(self, *alternatives):
+        self.alternatives = [list(a) for a in alternatives]
+
+    def __repr__(self):
+        return "AnyOf(" + ", ".join(repr(a) for a in self.alternatives) + ")"
+
+
+def _split_filter(filt):
+    """(base terms, alternatives or None) of a filter that may hold one AnyOf"""
+    filt = list(filt or [])
+    groups = [t for t in filt if isinstance(t, AnyOf)]
+    if not groups:
+        return filt, None
+    if len(groups) > 1:
+        raise ValueError(f"filter: {len(groups)} AnyOf elements (at most one per filter)")
+    alts = groups[0].alternatives
+    if not alts:
+        raise ValueError("filter: an empty AnyOf (it takes at least one alternative)")
+    for i, a in enumerate(alts):
+        if not a:
+            raise ValueError(f"filter: alternative {i} of the AnyOf is empty")
+        if any(isinstance(t, AnyOf) for t in a):
+            raise ValueError(f"filter: alternative {i} of the AnyOf holds an AnyOf (they do not nest)")
+    return [t for t in filt if not isinstance(t, AnyOf)], alts
+
+
 class When:
     """agg FILTER (WHERE filt): any aggregate tuple of aggregate() under a
     condition of its own, filt as scan_filtered takes it.  The aggregate
@@ -169,6 +216,8 @@ class When:
     and aggregate_hashed()."""
 
     def __init__(self, agg, filt):
+        if any(isinstance(term, AnyOf) for term in filt):
+            raise ValueError("When: a condition holds no AnyOf")
         self.agg = tuple(agg)
         self.filt = [tuple(term) for term in filt]
 
@@ -285,6 +334,8 @@ _sig("fls_aggregate", C.c_int, _P, C.POINTER(AggregateSpec), C.c_uint32, C.c_uin
      C.POINTER(AggregateValue))
 _sig("fls_aggregate_exprs", C.c_int, _P, C.POINTER(AggExpr), C.c_uint32)
 _sig("fls_aggregate_conditions", C.c_int, _P, C.POINTER(Predicate), C.c_uint32, C.POINTER(AggCondition), C.c_uint32)
+_sig("fls_scan_filter_alternatives", C.c_int, _P, C.POINTER(Predicate), C.c_uint32, C.POINTER(FilterAlternative),
+     C.c_uint32)
 _sig("fls_aggregate_grouped", C.c_int, _P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(AggregateSpec), C.c_uint32,
      C.c_uint32, C.c_uint32, C.POINTER(_P))
 _sig("fls_group_result_ngroups", C.c_uint64, _P)
@@ -929,6 +980,7 @@ class HashGroups:
 class Table:
     def __init__(self, h, conn):
         self.h, self.conn, self._keep = h, conn, None
+        self._alts_set = False   # alternatives are set on the table (set_filter_alternatives)
 
     def close(self):
         if self.h:
@@ -1094,6 +1146,9 @@ class Table:
         values valid and a op b; a clause of its own; two signed or two
         unsigned integer columns of any widths, two DATE, two DECIMAL of one
         scale, or FLOAT / DOUBLE in any mix."""
+        if any(isinstance(term, AnyOf) for term in filt):
+            raise ValueError("an AnyOf is an element of a call's filt, not of a condition, an alternative or "
+                             "may_match's terms")
         sch = self.schema()
         arr = (Predicate * max(1, len(filt)))()
         keep = []
@@ -1153,11 +1208,58 @@ class Table:
         return arr, len(filt), keep
 
     def set_filter(self, filt):
-        arr, n, keep = self._preds(filt or [])
+        """The filter of the following scans and aggregate / top-N calls: its
+        terms (fls_scan_filter) and, when it holds an AnyOf, that element's
+        alternatives (fls_scan_filter_alternatives); without one, alternatives
+        set earlier are cleared."""
+        base, alts = _split_filter(filt)
+        arr, n, keep = self._preds(base)
+        packed = self._pack_lists(alts) if alts is not None else None
         _check(_lib.fls_scan_filter(self.h, arr, n))
+        if packed is not None or self._alts_set:
+            try:
+                self._set_alternatives(packed)
+            except FlsError:
+                _lib.fls_scan_filter(self.h, None, 0)   # a refused AnyOf leaves no half of the filter behind
+                raise
+
+    def _pack_lists(self, lists, range_type=FilterAlternative):
+        """several filters as one Predicate array and their ranges in it"""
+        parts = [self._preds(c) for c in lists]
+        preds = (Predicate * max(1, sum(n for _, n, _ in parts)))()
+        ranges = (range_type * max(1, len(lists)))()
+        k = 0
+        for i, (arr, n, _keep) in enumerate(parts):
+            ranges[i].first, ranges[i].n = k, n
+            for j in range(n):
+                preds[k + j] = arr[j]
+            k += n
+        return preds, k, ranges, len(lists), parts   # (parts keep the strings alive until the call has copied them)
+
+    def _set_alternatives(self, packed):
+        if packed is None:
+            _check(_lib.fls_scan_filter_alternatives(self.h, None, 0, None, 0))
+            self._alts_set = False
+            return
+        preds, k, ranges, n, _parts = packed
+        _check(_lib.fls_scan_filter_alternatives(self.h, preds if k else None, k, ranges if n else None, n))
+        self._alts_set = n > 0
+
+    def set_filter_alternatives(self, alternatives):
+        """fls_scan_filter_alternatives, the raw call: the alternatives (each a
+        filter as scan_filtered takes it, at most 8) AND-ed as a group to the
+        filter set by set_filter in the following calls; a row is selected
+        where the filter and at least one alternative hold.  [] or None
+        clears.  What an AnyOf element of a filt sets and clears per call."""
+        self._set_alternatives(self._pack_lists(alternatives) if alternatives else None)
+
+    def _clear_filter(self):
+        _check(_lib.fls_scan_filter(self.h, None, 0))
+        if self._alts_set:
+            self._set_alternatives(None)
 
     def may_match(self, rg: int, filt) -> bool:
-        arr, n, keep = self._preds(filt)
+        arr, n, keep = self._preds(filt)   # (no AnyOf: the call takes explicit terms)
         return _check(_lib.fls_rowgroup_may_match(self.h, rg, arr, n)) == 1
 
     @property
@@ -1195,7 +1297,7 @@ class Table:
                     sel = np.arange(out.nrows, dtype=np.uint32)
                 yield out.rowgroup, out.first_row, sel, self._rg_arrays(out)
         finally:
-            _check(_lib.fls_scan_filter(self.h, None, 0))
+            self._clear_filter()
 
     def keyset(self, col: int, filt=None, form: int = KEYSET_AUTO) -> "KeySet":
         """The build side of a semi-join: the key set of the non-NULL values
@@ -1262,16 +1364,8 @@ class Table:
         and clears per call); each condition a filter as scan_filtered takes
         it, at most 8.  [] or None clears."""
         conds = conds or []
-        parts = [self._preds(c) for c in conds]
-        preds = (Predicate * max(1, sum(n for _, n, _ in parts)))()
-        ranges = (AggCondition * max(1, len(conds)))()
-        k = 0
-        for i, (arr, n, _keep) in enumerate(parts):
-            ranges[i].first, ranges[i].n = k, n
-            for j in range(n):
-                preds[k + j] = arr[j]   # (the strings stay alive in parts until the call has copied them)
-            k += n
-        _check(_lib.fls_aggregate_conditions(self.h, preds if k else None, k, ranges if conds else None, len(conds)))
+        preds, k, ranges, n, _parts = self._pack_lists(conds, AggCondition)
+        _check(_lib.fls_aggregate_conditions(self.h, preds if k else None, k, ranges if conds else None, n))
 
     def aggregate_raw(self, aggs, rg_begin=0, rg_end=None) -> list[AggregateValue]:
         """fls_aggregate under the filter currently set (set_filter): the raw
@@ -1311,7 +1405,7 @@ class Table:
         try:
             vals = self.aggregate_raw(aggs, rg_begin, rg_end)
         finally:
-            _check(_lib.fls_scan_filter(self.h, None, 0))
+            self._clear_filter()
         return [_agg_value(v) for v in vals]
 
     def aggregate_grouped(self, keys, aggs, filt=None, rg_begin=0, rg_end=None) -> list:
@@ -1354,7 +1448,7 @@ class Table:
             _check(_lib.fls_aggregate_grouped(self.h, karr, len(keys), arr, len(aggs), rg_begin, rg_end,
                                               C.byref(res)))
         finally:
-            _check(_lib.fls_scan_filter(self.h, None, 0))
+            self._clear_filter()
             if exprs:
                 self.set_aggregate_exprs(None)
             if conds:
@@ -1456,7 +1550,7 @@ class Table:
                 _check(_lib.fls_aggregate_hashed(self.h, karr, len(keys), arr, len(aggs), max_groups, rg_begin,
                                                  rg_end, C.byref(res)))
         finally:
-            _check(_lib.fls_scan_filter(self.h, None, 0))
+            self._clear_filter()
             if exprs:
                 self.set_aggregate_exprs(None)
             if conds:
@@ -1495,7 +1589,7 @@ class Table:
         try:
             _check(_lib.fls_topn(self.h, C.byref(key), k, _mask(self, cols), rg_begin, rg_end, C.byref(res)))
         finally:
-            _check(_lib.fls_scan_filter(self.h, None, 0))
+            self._clear_filter()
         try:
             p1, p2 = C.c_double(), C.c_double()
             _check(_lib.fls_topn_result_times(res, C.byref(p1), C.byref(p2)))

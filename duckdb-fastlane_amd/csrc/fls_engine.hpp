@@ -8,6 +8,8 @@
 //                         the hooks of fls_tuning.hpp
 //   fls_cond.hip          (kernel) the aggregates' conditions; their host half,
 //                         enqueue_conditions, sits beside enqueue_filter
+//   fls_alt.hip           (kernels) the filter's alternatives; their host half,
+//                         enqueue_alternatives, runs inside enqueue_filter
 //   fls_scan_agg.hip      fls_aggregate / fls_aggregate_grouped: checks,
 //                         per-batch enqueue, the host fold
 //   fls_scan_hashagg.hip  fls_aggregate_hashed: checks, the key layout, the
@@ -358,6 +360,10 @@ struct Slot {                       // one batch of row groups in flight
     DevBuf<uint8_t> d_qdesc;
     DevBuf<uint64_t> d_cond;        // per condition a plane of 16 words per vector: where & cond
     DevBuf<uint32_t> d_ccounts;     // the narrowing kernels' per-vector counts of a plane (scratch)
+    // the filter's alternatives (fls_scan_filter_alternatives)
+    PinBuf<uint8_t> h_altdesc;      // laid out as h_qdesc
+    DevBuf<uint8_t> d_altdesc;
+    DevBuf<uint64_t> d_alt;         // per alternative a plane of 16 words per vector: mask & alternative
     // grouped aggregate batches (fls_aggregate_grouped)
     PinBuf<uint8_t> h_gdesc;        // DevKey[kMaxKeys] + per row group its first vector and vector count
     DevBuf<uint8_t> d_gdesc;
@@ -579,6 +585,9 @@ struct ScanPlan {
     const uint8_t *col_mask = nullptr;              // per column: delivered (NULL: every column)
     uint32_t rg0 = 0, rg1 = 0;                      // row groups [rg0, rg1)
     const std::vector<HostTerm> *filter = nullptr;  // pushed-down filter (NULL: none)
+    // the filter's alternatives (NULL: none): a row is selected when the filter
+    // selects it and one of them is true there
+    const std::vector<std::vector<HostTerm>> *alts = nullptr;
     // a consumer's scan (fls_scan_begin), which honours the table's delivery
     // options (dictionary codes, narrowing, deferred records); fls_materialize
     // and the scans the engine runs for itself deliver at full width
@@ -606,6 +615,10 @@ struct ScanCtx {
     std::vector<uint8_t> mask;      // delivered columns
     std::vector<uint8_t> dmask;     // decoded columns (delivered + filter columns)
     std::vector<HostTerm> terms;    // filter of this scan, sorted by clause (empty: none)
+    // ... and its alternatives (fls_scan_filter_alternatives), each a filter of
+    // its own sorted by clause: the mask keeps a row of the filter's where one
+    // of them is true (enqueue_alternatives).  Empty: none.
+    std::vector<std::vector<HostTerm>> alts;
     // aggregate scan (Reduce::Aggregate / GroupAggregate): no column is
     // delivered, each batch's partial records ride in its HostBatch
     std::vector<HostAgg> aggs;
@@ -619,7 +632,7 @@ struct ScanCtx {
     // ... where FLS_KEY_MAPPED | i stands for the code binding i gives its
     // column (keymap_kernel).  With a binding the scan always has a mask.
     std::vector<HostBinding> binds;
-    bool masked() const { return !terms.empty() || !binds.empty(); }
+    bool masked() const { return !terms.empty() || !alts.empty() || !binds.empty(); }
     // hash aggregate scan (Reduce::HashAggregate): the key layout and the
     // pipelines' tables, and the groups one table may hold
     HashPlan hash;
@@ -771,6 +784,7 @@ struct fls_table {
 
     fls::engine::ScanCtx scan, mat;
     std::vector<fls::engine::HostTerm> filter;  // fls_scan_filter: applies to the next fls_scan_begin / fls_aggregate
+    std::vector<std::vector<fls::engine::HostTerm>> alts;  // fls_scan_filter_alternatives: OR-ed, AND-ed to the filter
     std::vector<fls_agg_expr> exprs;  // fls_aggregate_exprs: what FLS_AGG_SUM_EXPR's spec.col indexes
     std::vector<std::vector<fls::engine::HostTerm>> conds;  // fls_aggregate_conditions: what spec.cond - 1 indexes
     std::vector<fls::engine::HostBinding> bindings;  // fls_aggregate_key_bindings: what FLS_KEY_MAPPED | i names
@@ -815,8 +829,13 @@ hipError_t launch_all(const DevChunk *d_chunks, uint32_t nmain, uint32_t ntotal,
 // ---- the scan pipeline (flsgpu.hip) -------------------------------------------
 
 bool rowgroup_may_match(const fls_table *t, uint32_t rg, const std::vector<HostTerm> &terms);
+// ... under a filter with alternatives: the filter may match and (where there
+// are alternatives) one of them may
+bool rowgroup_may_match(const fls_table *t, uint32_t rg, const std::vector<HostTerm> &terms,
+                        const std::vector<std::vector<HostTerm>> &alts);
 bool topn_key_type(const ColumnMeta &c);
-uint32_t select_rowgroups(const fls_table *t, const std::vector<HostTerm> &terms, const fls_order_key *order, uint32_t k,
+uint32_t select_rowgroups(const fls_table *t, const std::vector<HostTerm> &terms,
+                          const std::vector<std::vector<HostTerm>> &alts, const fls_order_key *order, uint32_t k,
                           uint32_t rg0, uint32_t rg1, std::vector<uint32_t> &rgs);
 int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &plan);
 int scan_start(fls_table *t, ScanCtx &s);
@@ -871,6 +890,7 @@ int reduce_scan(fls_table *t, ScanPlan plan, const char *what, Fold &&fold) {
     plan.devices = t->devices;
     plan.col_mask = none.data();
     plan.filter = &t->filter;
+    plan.alts = &t->alts;
     ScanCtx &s = t->scan;
     int rc = scan_setup(t, s, plan);
     if (!rc) rc = scan_start(t, s);

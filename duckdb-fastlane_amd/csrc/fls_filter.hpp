@@ -29,6 +29,10 @@
 // evaluated by colcmp_kernel (fls_colcmp.hip), which narrows the mask right
 // after filter_kernel -- two coalesced loads and a compare are cheaper than a
 // probe or a string match, so the later kernels skip the words it empties.
+// A filter may have alternatives (fls_scan_filter_alternatives): filters of
+// this very shape of which at least one must hold beside it.  They prune a row
+// group none of them can match, and on the GPU alt_kernel / alt_merge_kernel
+// (fls_alt.hip) OR them into the mask the kernels above wrote.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -233,6 +237,27 @@ struct CondList {
 // (fls_cond.hip).
 hipError_t launch_conditions(const DevTerm *d_terms, const CondList &conds, uint32_t nrows, const uint64_t *d_mask,
                              uint64_t *d_planes, uint32_t *d_err, hipStream_t stream);
+
+// The alternatives of a filter (fls_scan_filter_alternatives) as alt_kernel
+// sees them: alternative a's ordinary terms are terms[first[a] .. first[a + 1])
+// as in CondList (an empty range: the alternative starts from the mask); bit a
+// of `closed` is set when no key-set, column-pair or pattern term follows.
+struct AltList {
+    uint32_t first[kMaxConds + 1];
+    uint32_t n;
+    uint32_t closed;
+};
+// The first step (fls_alt.hip): d_mask, which the filter's kernels wrote for
+// the nrows decoded rows of a batch, becomes mask & (OR of the closed
+// alternatives) with its per-vector counts in d_counts; an open alternative
+// a's `mask & ordinary terms` goes to d_planes[a * 16 * nvec + 16 * v + word]
+// for the narrowing kernels.  One launch for all alternatives.
+hipError_t launch_alternatives(const DevTerm *d_terms, const AltList &alts, uint32_t nrows, uint64_t *d_mask,
+                               uint64_t *d_planes, uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
+// The last step, after the open planes were narrowed: d_mask |= the open
+// alternatives' planes, and d_counts again.  No launch without an open one.
+hipError_t launch_alt_merge(const AltList &alts, uint32_t nrows, uint64_t *d_mask, const uint64_t *d_planes,
+                            uint32_t *d_counts, hipStream_t stream);
 
 // Narrowed delivery (fls_scan_narrow): an integer column of a batch whose
 // values, per row group, lie in [base, base + 2^(8 nw)) crosses PCIe as the

@@ -63,7 +63,7 @@ int upload_agg_descs(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl) {
 // (enqueue_filter ran before) or none.
 int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
     HostBatch &hb = *sl.hb;
-    const bool filtered = !s.terms.empty();
+    const bool filtered = s.masked();
     if (!filtered && s.conds.empty())  // (enqueue_filter, or fill_batch for the conditions, staged every validity together)
         if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
     const uint32_t na = (uint32_t)s.aggs.size();
@@ -275,7 +275,7 @@ int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_sp
             // term takes at an end of the column's range
             double bound = 0;
             for (uint32_t r = rg_begin; r < rg_end; ++r) {
-                if (!t->filter.empty() && !rowgroup_may_match(t, r, t->filter)) continue;
+                if (!rowgroup_may_match(t, r, t->filter, t->alts)) continue;
                 double term = dbl_up(t->meta.rgs[r].nrows);
                 for (uint32_t k = 0; k < ha[i].nf; ++k)
                     term = mul_up(term, max_factor(t, r, ha[i].fcol[k], ha[i].fneg[k], ha[i].fk[k]));
@@ -288,7 +288,7 @@ int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_sp
         if (ha[i].fn != AGG_SUM_PRODUCT) continue;
         double bound = 0;
         for (uint32_t r = rg_begin; r < rg_end; ++r) {
-            if (!t->filter.empty() && !rowgroup_may_match(t, r, t->filter)) continue;
+            if (!rowgroup_may_match(t, r, t->filter, t->alts)) continue;
             const double term = mul_up(mul_up(dbl_up(t->meta.rgs[r].nrows), dbl_up(max_magnitude(t, r, ha[i].col))),
                                        dbl_up(max_magnitude(t, r, ha[i].col2)));
             bound = std::nextafter(bound + term, HUGE_VAL);
@@ -490,9 +490,15 @@ int fls_aggregate_grouped(fls_table *t, const uint32_t *keys, uint32_t nkeys, co
                 return fail(FLS_ERR_ARG,
                             "key %u: VARCHAR column %u is read by a filter term, which needs it decoded as strings, "
                             "not as the dictionary codes a key is made of", q, c);
+        for (size_t a = 0; a < t->alts.size(); ++a)
+            for (const HostTerm &h : t->alts[a])
+                if (h.col == c || (is_col_op(h.op) && h.col2 == c))
+                    return fail(FLS_ERR_ARG,
+                                "key %u: VARCHAR column %u is read by a term of alternative %u, which needs it decoded "
+                                "as strings, not as the dictionary codes a key is made of", q, c, (uint32_t)a);
         // the row groups the scan will read (the same set the SUM_PRODUCT bound walks)
         for (uint32_t r = rg_begin; r < rg_end; ++r) {
-            if (!t->filter.empty() && !rowgroup_may_match(t, r, t->filter)) continue;
+            if (!rowgroup_may_match(t, r, t->filter, t->alts)) continue;
             const ChunkHeader &h = t->meta.rgs[r].chunks[c].hdr;
             if (h.enc != ENC_DICT)
                 return fail(FLS_ERR_ARG, "key %u: VARCHAR column %u is not dictionary-encoded in row group %u", q, c, r);

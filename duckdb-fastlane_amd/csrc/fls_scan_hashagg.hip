@@ -253,7 +253,7 @@ int hash_scan(HashCall &c) {
     // Is there a row group to read?  (scan_setup prunes the same way; without
     // one the scan below does no device work and no table is needed)
     std::vector<uint32_t> rgs;
-    select_rowgroups(t, t->filter, nullptr, 0, rg_begin, rg_end, rgs);
+    select_rowgroups(t, t->filter, t->alts, nullptr, 0, rg_begin, rg_end, rgs);
     const size_t G = t->devices.size();
     tables = std::vector<DevBuf<uint64_t>>(rgs.empty() ? 0 : G);
     for (size_t g = 0; g < tables.size(); ++g) {

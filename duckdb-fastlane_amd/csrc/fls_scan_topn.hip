@@ -19,7 +19,7 @@ FLS_ENGINE_BEGIN
 // the row groups' lists are the batch's only D2H.
 int enqueue_topn(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo) {
     HostBatch &hb = *sl.hb;
-    const bool filtered = !s.terms.empty();
+    const bool filtered = s.masked();
     if (!filtered)  // (enqueue_filter staged the filter's and the key's validity together)
         if (int rc = stage_validity(t, s, d, sl, rows, in_lo)) return rc;
     const uint32_t c = s.tkey.col;
@@ -253,7 +253,7 @@ int fls_topn_pruned(const fls_table *t, const fls_order_key *key, uint32_t k, ui
     if (!t || !key) return fail(FLS_ERR_ARG, "fls_topn_pruned: NULL argument");
     if (int rc = check_topn(t, key, k, nullptr, rg_begin, rg_end)) return rc;
     std::vector<uint32_t> rgs;
-    return (int)select_rowgroups(t, t->filter, key, k, rg_begin, rg_end, rgs);
+    return (int)select_rowgroups(t, t->filter, t->alts, key, k, rg_begin, rg_end, rgs);
 }
 
 uint64_t fls_topn_result_nrows(const fls_topn_result *r) { return r ? r->rows.size() : 0; }

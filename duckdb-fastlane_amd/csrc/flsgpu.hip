@@ -599,6 +599,14 @@ bool rowgroup_may_match(const fls_table *t, uint32_t rg, const std::vector<HostT
     return true;
 }
 
+bool rowgroup_may_match(const fls_table *t, uint32_t rg, const std::vector<HostTerm> &terms,
+                        const std::vector<std::vector<HostTerm>> &alts) {
+    if (!rowgroup_may_match(t, rg, terms)) return false;
+    for (auto &a : alts)
+        if (rowgroup_may_match(t, rg, a)) return true;
+    return alts.empty();
+}
+
 // Is column c a possible ORDER BY key of fls_topn?
 bool topn_key_type(const ColumnMeta &c) {
     return !type_is_string(c.type) && type_valid(c.type) && !(c.type == TY_DECIMAL && c.width > 18);
@@ -652,16 +660,17 @@ static uint32_t topn_prune(const fls_table *t, const fls_order_key &key, uint32_
 
 // The row groups of [rg0, rg1) a scan reads, in order, and how many it skips:
 // those the filter's zone maps / dictionaries rule out, and for a top-N scan
-// without a filter those topn_prune drops.
-uint32_t select_rowgroups(const fls_table *t, const std::vector<HostTerm> &terms, const fls_order_key *order, uint32_t k,
+// without a filter (alternatives count as one) those topn_prune drops.
+uint32_t select_rowgroups(const fls_table *t, const std::vector<HostTerm> &terms,
+                          const std::vector<std::vector<HostTerm>> &alts, const fls_order_key *order, uint32_t k,
                           uint32_t rg0, uint32_t rg1, std::vector<uint32_t> &rgs) {
     uint32_t pruned = 0;
     rgs.clear();
     for (uint32_t r = rg0; r < rg1; ++r) {
-        if (terms.empty() || rowgroup_may_match(t, r, terms)) rgs.push_back(r);
+        if (rowgroup_may_match(t, r, terms, alts)) rgs.push_back(r);
         else pruned++;
     }
-    if (order && terms.empty()) pruned += topn_prune(t, *order, k, rgs);
+    if (order && terms.empty() && alts.empty()) pruned += topn_prune(t, *order, k, rgs);
     return pruned;
 }
 
@@ -764,6 +773,8 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
         for (uint32_t c = 0; c < ncols; ++c) s.mask[c] = p.col_mask[c] ? 1 : 0;
     s.terms.clear();
     if (p.filter) s.terms = *p.filter;
+    s.alts.clear();
+    if (p.alts) s.alts = *p.alts;
     // the one place that decides what kind of scan this is
     s.reduce = Reduce::None;
     if (p.aggs) s.reduce = p.hash ? Reduce::HashAggregate : p.keys ? Reduce::GroupAggregate : Reduce::Aggregate;
@@ -774,9 +785,14 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     s.narrow = options && t->narrow;
     s.defer_records = options && t->defer_records;
     s.dmask = s.mask;
-    for (auto &h : s.terms)
-        if (h.op < OP_IS_NULL || is_set_op(h.op) || is_pat_op(h.op)) s.dmask[h.col] = 1;
-        else if (is_col_op(h.op)) s.dmask[h.col] = s.dmask[h.col2] = 1;
+    // (an IS [NOT] NULL term reads the validity alone)
+    auto decode_columns_of = [&](const std::vector<HostTerm> &terms) {
+        for (auto &h : terms)
+            if (h.op < OP_IS_NULL || is_set_op(h.op) || is_pat_op(h.op)) s.dmask[h.col] = 1;
+            else if (is_col_op(h.op)) s.dmask[h.col] = s.dmask[h.col2] = 1;
+    };
+    decode_columns_of(s.terms);
+    for (auto &a : s.alts) decode_columns_of(a);
     s.aggs.clear();
     s.conds.clear();
     s.keys.clear();
@@ -812,10 +828,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
         // the conditions' columns are decoded like the filter's, for the row
         // groups the scan reads: a condition prunes nothing
         if (p.conds) s.conds = *p.conds;
-        for (auto &q : s.conds)
-            for (auto &h : q)
-                if (h.op < OP_IS_NULL || is_set_op(h.op) || is_pat_op(h.op)) s.dmask[h.col] = 1;
-                else if (is_col_op(h.op)) s.dmask[h.col] = s.dmask[h.col2] = 1;
+        for (auto &q : s.conds) decode_columns_of(q);
         for (auto &a : s.aggs) {
             if (a.fn == AGG_SUM_EXPR) {
                 for (uint32_t i = 0; i < a.nf; ++i) s.dmask[a.fcol[i]] = 1;
@@ -834,7 +847,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     }
     // row-group pruning on zone maps / dictionaries (a top-N scan without a
     // filter: by the k-th bound of the key's zone maps)
-    s.pruned = select_rowgroups(t, s.terms, s.reduce == Reduce::TopN ? &s.tkey : nullptr, s.tk, rg0, rg1, s.rgs);
+    s.pruned = select_rowgroups(t, s.terms, s.alts, s.reduce == Reduce::TopN ? &s.tkey : nullptr, s.tk, rg0, rg1, s.rgs);
     // an inner binding prunes as `col IN keys(map)` would
     for (const HostBinding &b : s.binds) {
         if (b.keep) continue;
@@ -944,11 +957,12 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
         need[h.col] = 1;
         if (is_col_op(h.op)) need[h.col2] = 1;
     }
-    for (auto &q : s.conds)
-        for (auto &h : q) {
-            need[h.col] = 1;
-            if (is_col_op(h.op)) need[h.col2] = 1;
-        }
+    for (auto *lists : {&s.alts, &s.conds})
+        for (auto &q : *lists)
+            for (auto &h : q) {
+                need[h.col] = 1;
+                if (is_col_op(h.op)) need[h.col2] = 1;
+            }
     for (auto &a : s.aggs) {
         if (a.fn == AGG_SUM_EXPR) {
             for (uint32_t i = 0; i < a.nf; ++i) need[a.fcol[i]] = 1;
@@ -1089,6 +1103,137 @@ static void fill_term(const fls_table *t, Slot &sl, const HostTerm &h, uint64_t 
     }
 }
 
+// The descriptor block of several term lists -- the aggregates' conditions,
+// the filter's alternatives -- over the slot's decoded columns and staged
+// validity: DevTerm[], DevColTerm[], DevSetTerm[], DevPatTerm[], then the
+// constant strings and the pattern tokens, list after list within each array.
+struct ListDescs {
+    struct Kinds {
+        std::vector<const HostTerm *> ord, ccs, sets, pats;
+        uint32_t ptok = 0;  // tokens of the list's pattern terms
+    };
+    std::vector<Kinds> kinds;            // per list
+    uint32_t first[kMaxConds + 1] = {};  // list q's ordinary terms are DevTerm[first[q] .. first[q + 1])
+    size_t off_c = 0, off_s = 0, off_p = 0, bytes = 0;
+};
+// Fills h_desc (the caller copies L.bytes of it to d_desc, whose addresses the
+// descriptors hold); at most kMaxConds lists.
+static int build_list_descs(const fls_table *t, ScanDev &d, Slot &sl, const std::vector<std::vector<HostTerm>> &lists,
+                            uint64_t in_lo, uint64_t in_len, PinBuf<uint8_t> &h_desc, DevBuf<uint8_t> &d_desc,
+                            ListDescs &L) {
+    const uint32_t nq = (uint32_t)lists.size();
+    L.kinds.assign(nq, ListDescs::Kinds());
+    size_t nt = 0, nc = 0, ns = 0, np = 0, tail = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+        ListDescs::Kinds &k = L.kinds[q];
+        for (auto &h : lists[q])
+            (is_set_op(h.op) ? k.sets : is_pat_op(h.op) ? k.pats : is_col_op(h.op) ? k.ccs : k.ord).push_back(&h);
+        nt += k.ord.size();
+        nc += k.ccs.size();
+        ns += k.sets.size();
+        np += k.pats.size();
+        for (auto *h : k.ord) tail += (h->str.size() + 15) & ~size_t(15);
+        for (auto *h : k.pats) tail += (h->pat->tok.size() * sizeof(uint16_t) + 15) & ~size_t(15);
+    }
+    // (every descriptor size is a multiple of 16, DevTerm's and DevPatTerm's of 32: each array stays aligned)
+    L.off_c = nt * sizeof(DevTerm);
+    L.off_s = L.off_c + nc * sizeof(DevColTerm);
+    L.off_p = (L.off_s + ns * sizeof(DevSetTerm) + 31) & ~size_t(31);
+    size_t so = L.off_p + np * sizeof(DevPatTerm);
+    L.bytes = so + tail;
+    HIP_TRY(h_desc.alloc(L.bytes));
+    HIP_TRY(d_desc.alloc(d.dev, L.bytes));
+    uint8_t *qd = h_desc.p;
+    memset(qd, 0, L.bytes);
+    DevTerm *terms = (DevTerm *)qd;
+    DevColTerm *cterms = (DevColTerm *)(qd + L.off_c);
+    DevSetTerm *sterms = (DevSetTerm *)(qd + L.off_s);
+    size_t it = 0, ic = 0, is = 0, ip = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+        ListDescs::Kinds &k = L.kinds[q];
+        L.first[q] = (uint32_t)it;
+        for (size_t i = 0; i < k.ord.size(); ++i) {
+            const HostTerm &h = *k.ord[i];
+            fill_term(t, sl, h, in_lo, in_len, d_desc.p + so, i + 1 == k.ord.size() || k.ord[i + 1]->clause != h.clause,
+                      terms[it++]);
+            if (h.kind == FK_STR) {
+                memcpy(qd + so, h.str.data(), h.str.size());
+                so += (h.str.size() + 15) & ~size_t(15);
+            }
+        }
+        for (auto *h : k.ccs) fill_col_term(t, sl, *h, cterms[ic++]);
+        for (auto *h : k.sets)
+            if (int rc = fill_set_term(t, d, sl, *h, sterms[is++])) return rc;
+        for (auto *h : k.pats) {
+            const CompiledPattern &cp = *h->pat;
+            DevPatTerm dp;
+            fill_pat_term(t, sl, *h, in_lo, in_len, (const uint16_t *)(d_desc.p + so), dp);
+            memcpy(qd + L.off_p + ip++ * sizeof(DevPatTerm), &dp, sizeof(dp));
+            if (!cp.tok.empty()) memcpy(qd + so, cp.tok.data(), cp.tok.size() * sizeof(uint16_t));
+            so += (cp.tok.size() * sizeof(uint16_t) + 15) & ~size_t(15);
+            k.ptok += (uint32_t)cp.tok.size();
+        }
+    }
+    L.first[nq] = (uint32_t)it;
+    return 0;
+}
+
+// Each list's column, key-set and pattern terms narrow its plane (list q's at
+// planes + q * 16 * nvec) through the filter's kernels, one launch per kind,
+// in the filter's order; their per-vector counts go to a scratch buffer.
+static int narrow_planes(ScanDev &d, Slot &sl, const ListDescs &L, const uint8_t *d_desc, uint64_t rows,
+                         uint64_t *planes) {
+    const size_t plane = (size_t)sl.hb->nvec * 16;
+    HIP_TRY(sl.d_ccounts.alloc(d.dev, sl.hb->nvec));
+    size_t ic = 0, is = 0, ip = 0;
+    for (size_t q = 0; q < L.kinds.size(); ++q) {
+        const ListDescs::Kinds &k = L.kinds[q];
+        uint64_t *pl = planes + plane * q;
+        if (!k.ccs.empty())
+            HIP_TRY(launch_colcmp((const DevColTerm *)(d_desc + L.off_c) + ic, (uint32_t)k.ccs.size(), (uint32_t)rows, pl,
+                                  sl.d_ccounts.p, d.err.p, sl.stream));
+        if (!k.sets.empty())
+            HIP_TRY(launch_keyset((const DevSetTerm *)(d_desc + L.off_s) + is, (uint32_t)k.sets.size(), (uint32_t)rows, pl,
+                                  sl.d_ccounts.p, d.err.p, sl.stream));
+        if (!k.pats.empty())
+            HIP_TRY(launch_strmatch((const DevPatTerm *)(d_desc + L.off_p) + ip, (uint32_t)k.pats.size(), k.ptok,
+                                    (uint32_t)rows, pl, sl.d_ccounts.p, d.err.p, sl.stream));
+        ic += k.ccs.size();
+        is += k.sets.size();
+        ip += k.pats.size();
+    }
+    return 0;
+}
+
+// The alternatives of a filtered batch (ScanCtx::alts), after the filter's
+// kernels on the slot's mask: alt_kernel evaluates the ordinary terms of all
+// alternatives in one launch, OR-s the closed ones into the mask and writes a
+// plane per open one into sl.d_alt (sl.d_cond stays with the conditions, whose
+// cond_kernel runs afterwards from the merged mask); the open planes are
+// narrowed (narrow_planes) and alt_merge_kernel OR-s them into the mask.  The
+// launches do not grow with the alternatives: one, or with an open
+// alternative one per kind it holds and the merge.
+static int enqueue_alternatives(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo,
+                                uint64_t in_len) {
+    const uint32_t na = (uint32_t)s.alts.size();
+    if (na == 0 || na > kMaxConds) return fail(FLS_ERR_STATE, "internal: %u alternatives in a scan", na);
+    ListDescs L;
+    if (int rc = build_list_descs(t, d, sl, s.alts, in_lo, in_len, sl.h_altdesc, sl.d_altdesc, L)) return rc;
+    AltList al;
+    memset(&al, 0, sizeof(al));
+    al.n = na;
+    memcpy(al.first, L.first, sizeof(al.first));
+    for (uint32_t a = 0; a < na; ++a)
+        if (L.kinds[a].ccs.empty() && L.kinds[a].sets.empty() && L.kinds[a].pats.empty()) al.closed |= 1u << a;
+    HIP_TRY(sl.d_alt.alloc(d.dev, (size_t)sl.hb->nvec * 16 * na));
+    HIP_TRY(hipMemcpyAsync(sl.d_altdesc.p, sl.h_altdesc.p, L.bytes, hipMemcpyHostToDevice, sl.stream));
+    HIP_TRY(launch_alternatives((const DevTerm *)sl.d_altdesc.p, al, (uint32_t)rows, sl.d_mask.p, sl.d_alt.p,
+                                sl.d_counts.p, d.err.p, sl.stream));
+    if (int rc = narrow_planes(d, sl, L, sl.d_altdesc.p, rows, sl.d_alt.p)) return rc;
+    HIP_TRY(launch_alt_merge(al, (uint32_t)rows, sl.d_mask.p, sl.d_alt.p, sl.d_counts.p, sl.stream));
+    return 0;
+}
+
 // Filter descriptors of a batch: the terms over the slot's decoded columns,
 // the delivered columns' compaction targets, then the constant strings.
 static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo, uint64_t in_len) {
@@ -1183,6 +1328,8 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
         HIP_TRY(launch_strmatch((const DevPatTerm *)sl.d_pdesc.p, (uint32_t)np, (uint32_t)total_tokens, (uint32_t)rows,
                                 sl.d_mask.p, sl.d_counts.p, d.err.p, sl.stream));
     }
+    if (!s.alts.empty())  // the alternatives: the mask keeps the rows where one of them is true
+        if (int rc = enqueue_alternatives(t, s, d, sl, rows, in_lo, in_len)) return rc;
     if (!s.binds.empty())  // mapped GROUP BY keys: their codes, and the inner ones' narrowing of the mask
         if (int rc = enqueue_keymap(t, s, d, sl, rows)) return rc;
     if (s.reduce != Reduce::None) return 0;  // an aggregate / top-N scan reduces under the mask: nothing is compacted or delivered
@@ -1202,98 +1349,25 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
 // planes start from the slot's mask; unfiltered: from row < nrows) and
 // stage_validity.  cond_kernel evaluates the ordinary terms of all conditions
 // in one launch; a condition's column, key-set and pattern terms then narrow
-// its plane through the filter's kernels, one launch per kind, in the
-// filter's order.  One descriptor block: DevTerm[], DevColTerm[], DevSetTerm[],
-// DevPatTerm[], then the constant strings and the pattern tokens.
+// its plane (narrow_planes).  One descriptor block (build_list_descs).
 static int enqueue_conditions(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo,
                               uint64_t in_len) {
     const uint32_t nq = (uint32_t)s.conds.size();
     if (nq == 0 || nq > kMaxConds) return fail(FLS_ERR_STATE, "internal: %u conditions in a scan", nq);
     HostBatch &hb = *sl.hb;
     hb.nvec = (uint32_t)((rows + 1023) / 1024);
-    struct Kinds {
-        std::vector<const HostTerm *> ord, ccs, sets, pats;
-    };
-    std::vector<Kinds> kinds(nq);
-    size_t nt = 0, nc = 0, ns = 0, np = 0, tail = 0;
-    for (uint32_t q = 0; q < nq; ++q) {
-        Kinds &k = kinds[q];
-        for (auto &h : s.conds[q])
-            (is_set_op(h.op) ? k.sets : is_pat_op(h.op) ? k.pats : is_col_op(h.op) ? k.ccs : k.ord).push_back(&h);
-        nt += k.ord.size();
-        nc += k.ccs.size();
-        ns += k.sets.size();
-        np += k.pats.size();
-        for (auto *h : k.ord) tail += (h->str.size() + 15) & ~size_t(15);
-        for (auto *h : k.pats) tail += (h->pat->tok.size() * sizeof(uint16_t) + 15) & ~size_t(15);
-    }
-    // (every descriptor size is a multiple of 16, DevTerm's and DevPatTerm's of 32: each array stays aligned)
-    const size_t off_c = nt * sizeof(DevTerm), off_s = off_c + nc * sizeof(DevColTerm);
-    const size_t off_p = (off_s + ns * sizeof(DevSetTerm) + 31) & ~size_t(31);
-    size_t so = off_p + np * sizeof(DevPatTerm);
-    const size_t bytes = so + tail;
-    HIP_TRY(sl.h_qdesc.alloc(bytes));
-    HIP_TRY(sl.d_qdesc.alloc(d.dev, bytes));
-    uint8_t *qd = sl.h_qdesc.p;
-    memset(qd, 0, bytes);
-    DevTerm *terms = (DevTerm *)qd;
-    DevColTerm *cterms = (DevColTerm *)(qd + off_c);
-    DevSetTerm *sterms = (DevSetTerm *)(qd + off_s);
+    ListDescs L;
+    if (int rc = build_list_descs(t, d, sl, s.conds, in_lo, in_len, sl.h_qdesc, sl.d_qdesc, L)) return rc;
     CondList cl;
     memset(&cl, 0, sizeof(cl));
     cl.n = nq;
-    std::vector<uint32_t> ptok(nq, 0);  // tokens of each condition's pattern terms
-    size_t it = 0, ic = 0, is = 0, ip = 0;
-    for (uint32_t q = 0; q < nq; ++q) {
-        const Kinds &k = kinds[q];
-        cl.first[q] = (uint32_t)it;
-        for (size_t i = 0; i < k.ord.size(); ++i) {
-            const HostTerm &h = *k.ord[i];
-            fill_term(t, sl, h, in_lo, in_len, sl.d_qdesc.p + so, i + 1 == k.ord.size() || k.ord[i + 1]->clause != h.clause,
-                      terms[it++]);
-            if (h.kind == FK_STR) {
-                memcpy(qd + so, h.str.data(), h.str.size());
-                so += (h.str.size() + 15) & ~size_t(15);
-            }
-        }
-        for (auto *h : k.ccs) fill_col_term(t, sl, *h, cterms[ic++]);
-        for (auto *h : k.sets)
-            if (int rc = fill_set_term(t, d, sl, *h, sterms[is++])) return rc;
-        for (auto *h : k.pats) {
-            const CompiledPattern &cp = *h->pat;
-            DevPatTerm dp;
-            fill_pat_term(t, sl, *h, in_lo, in_len, (const uint16_t *)(sl.d_qdesc.p + so), dp);
-            memcpy(qd + off_p + ip++ * sizeof(DevPatTerm), &dp, sizeof(dp));
-            if (!cp.tok.empty()) memcpy(qd + so, cp.tok.data(), cp.tok.size() * sizeof(uint16_t));
-            so += (cp.tok.size() * sizeof(uint16_t) + 15) & ~size_t(15);
-            ptok[q] += (uint32_t)cp.tok.size();
-        }
-    }
-    cl.first[nq] = (uint32_t)it;
+    memcpy(cl.first, L.first, sizeof(cl.first));
     const size_t plane = (size_t)hb.nvec * 16;
     HIP_TRY(sl.d_cond.alloc(d.dev, plane * nq));
-    HIP_TRY(sl.d_ccounts.alloc(d.dev, hb.nvec));
-    HIP_TRY(hipMemcpyAsync(sl.d_qdesc.p, qd, bytes, hipMemcpyHostToDevice, sl.stream));
+    HIP_TRY(hipMemcpyAsync(sl.d_qdesc.p, sl.h_qdesc.p, L.bytes, hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(launch_conditions((const DevTerm *)sl.d_qdesc.p, cl, (uint32_t)rows, s.masked() ? sl.d_mask.p : nullptr,
                               sl.d_cond.p, d.err.p, sl.stream));
-    ic = is = ip = 0;
-    for (uint32_t q = 0; q < nq; ++q) {
-        const Kinds &k = kinds[q];
-        uint64_t *pl = sl.d_cond.p + plane * q;
-        if (!k.ccs.empty())
-            HIP_TRY(launch_colcmp((const DevColTerm *)(sl.d_qdesc.p + off_c) + ic, (uint32_t)k.ccs.size(), (uint32_t)rows,
-                                  pl, sl.d_ccounts.p, d.err.p, sl.stream));
-        if (!k.sets.empty())
-            HIP_TRY(launch_keyset((const DevSetTerm *)(sl.d_qdesc.p + off_s) + is, (uint32_t)k.sets.size(), (uint32_t)rows,
-                                  pl, sl.d_ccounts.p, d.err.p, sl.stream));
-        if (!k.pats.empty())
-            HIP_TRY(launch_strmatch((const DevPatTerm *)(sl.d_qdesc.p + off_p) + ip, (uint32_t)k.pats.size(), ptok[q],
-                                    (uint32_t)rows, pl, sl.d_ccounts.p, d.err.p, sl.stream));
-        ic += k.ccs.size();
-        is += k.sets.size();
-        ip += k.pats.size();
-    }
-    return 0;
+    return narrow_planes(d, sl, L, sl.d_qdesc.p, rows, sl.d_cond.p);
 }
 
 
@@ -1414,11 +1488,12 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
         in_term[h.col] = 1;
         if (is_col_op(h.op)) in_term[h.col2] = 1;
     }
-    for (auto &q : s.conds)
-        for (auto &h : q) {
-            in_term[h.col] = 1;
-            if (is_col_op(h.op)) in_term[h.col2] = 1;
-        }
+    for (auto *lists : {&s.alts, &s.conds})
+        for (auto &q : *lists)
+            for (auto &h : q) {
+                in_term[h.col] = 1;
+                if (is_col_op(h.op)) in_term[h.col2] = 1;
+            }
     for (uint32_t c : s.keys)
         if (!(c & FLS_KEY_MAPPED)) is_key[c] = 1;
     for (uint32_t c = 0; c < ncols; ++c) {
@@ -1477,7 +1552,7 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     // against 6.78e8 (profiles/r4/e2e_arms_strlen_r4t.txt).
     hb.strlen_w.assign(ncols, 0);
     const bool strlen_on = knob_value("FLS_SCAN_STRLEN") != 0;
-    for (uint32_t c = 0; strlen_on && s.narrow && s.terms.empty() && c < ncols; ++c) {
+    for (uint32_t c = 0; strlen_on && s.narrow && !s.masked() && c < ncols; ++c) {
         if (!col_selected(s.mask, c) || !type_is_string(t->meta.cols[c].type) || hb.ob[c] != 16) continue;
         bool ok = true;
         uint64_t maxlen = 0;
@@ -1896,7 +1971,7 @@ static int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
     out->ncols = ncols;
     out->nrows_scanned = out->nrows;
     out->sel = nullptr;
-    if (!s.terms.empty() && s.reduce == Reduce::None) {
+    if (s.masked() && s.reduce == Reduce::None) {
         batch_selection(t, s, *hb);
         const uint32_t i = rg - hb->rg0;
         out->nrows = hb->sel_off[i + 1] - hb->sel_off[i];
@@ -2434,6 +2509,7 @@ int fls_scan_begin(fls_table *t, const uint8_t *col_mask, uint32_t rg_begin, uin
     plan.rg0 = rg_begin;
     plan.rg1 = rg_end;
     plan.filter = &t->filter;
+    plan.alts = &t->alts;
     plan.delivering_scan = true;
     int rc = scan_setup(t, t->scan, plan);
     if (rc) return rc;
@@ -2446,6 +2522,29 @@ int fls_scan_filter(fls_table *t, const fls_predicate *preds, uint32_t n) {
     int rc = to_terms(t, preds, n, terms);
     if (rc) return rc;
     t->filter.swap(terms);
+    return 0;
+}
+
+int fls_scan_filter_alternatives(fls_table *t, const fls_predicate *preds, uint32_t npreds,
+                                 const fls_filter_alternative *alts, uint32_t nalts) {
+    if (!t || (!alts && nalts) || (!preds && npreds))
+        return fail(FLS_ERR_ARG, "fls_scan_filter_alternatives: NULL argument");
+    if (nalts > kMaxConds)
+        return fail(FLS_ERR_ARG, "fls_scan_filter_alternatives: %u alternatives (at most %u)", nalts, kMaxConds);
+    std::vector<std::vector<HostTerm>> list(nalts);
+    for (uint32_t i = 0; i < nalts; ++i) {
+        const fls_filter_alternative &a = alts[i];
+        if (a.n == 0) return fail(FLS_ERR_ARG, "alternative %u: no term (an alternative has at least one)", i);
+        if (a.first > npreds || a.n > npreds - a.first)
+            return fail(FLS_ERR_ARG, "alternative %u: terms [%u, %llu) past the %u predicates", i, a.first,
+                        (unsigned long long)a.first + a.n, npreds);
+        uint32_t at = 0;
+        if (int rc = to_terms(t, preds + a.first, a.n, list[i], &at)) {
+            const std::string why = fls_last_error();  // (the filter's refusal, its term numbers local to the alternative)
+            return fail(rc, "alternative %u, term %u: %s", i, at, why.c_str());
+        }
+    }
+    t->alts.swap(list);
     return 0;
 }
 

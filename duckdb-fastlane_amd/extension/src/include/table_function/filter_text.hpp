@@ -23,7 +23,16 @@
 //           column when it is an identifier the schema resolves and neither
 //           NULL nor the start of a typed literal (DATE '...'); a word that
 //           names no column is read as a literal as before (nan, inf, true).
-//           No OR, no other parentheses.
+//
+//   filter := item (AND item)*
+//   item   := term | '(' branch (OR branch)+ ')'
+//   branch := term | '(' term (AND term)* ')'
+//           One parenthesised OR group (2 to 8 branches) may stand among the
+//           AND-ed items: its branches become the filter's alternatives
+//           (fls_scan_filter_alternatives), a row passing when the AND-ed terms
+//           hold and at least one branch does.  No OR outside parentheses, no
+//           second group, no parenthesis inside a branch's own, no group in an
+//           aggregate's FILTER (WHERE ...) condition.
 //
 // Everything unparsable, unknown or ill-typed is a BinderException that starts
 // with the calling function's name (`who`) and quotes the offending text.
@@ -429,99 +438,172 @@ inline void CheckColumnPair(const Schema &sch, int a, int b, const string &who, 
                               ") in filter \"" + filter + "\"");
 }
 
+// The filter's one OR group: alternative i is preds[ranges[i].first ..
+// ranges[i].first + ranges[i].n), its clause numbers its own
+// (fls_scan_filter_alternatives).
+struct Alternatives {
+    std::vector<fls_predicate> preds;
+    std::vector<fls_filter_alternative> ranges;
+};
+constexpr size_t kMaxBranches = 8;  // the engine's planes per call
+
+// One term, its first token (the column) read already: its predicates --
+// several for an IN list on a VARCHAR / FLOAT / DOUBLE column -- onto preds.
+inline void ParseTerm(const Schema &sch, Lexer &lex, const Token &col, const string &filter, uint32_t &clause,
+                      std::vector<fls_predicate> &preds, std::deque<string> &strs, fls_connection *conn, KeySets *sets) {
+    const string &who = lex.who;
+    if (col.kind != Token::WORD)
+        throw BinderException(who + ": a column name is expected at \"" + col.text + "\" in filter \"" + filter + "\"");
+    const int c = sch.Find(col.text);
+    if (c < 0) throw BinderException(who + ": column \"" + col.text + "\" of filter \"" + filter + "\" not found");
+    fls_predicate p;
+    memset(&p, 0, sizeof(p));
+    p.col = (uint32_t)c;
+    Token op = lex.Next();
+    bool in_list = op.kind == Token::WORD && StringUtil::Lower(op.text) == "in", negate = false;
+    bool like = op.kind == Token::WORD && StringUtil::Lower(op.text) == "like";
+    if (op.kind == Token::WORD && StringUtil::Lower(op.text) == "not") {
+        Token t = lex.Next();
+        const string low = t.kind == Token::WORD ? StringUtil::Lower(t.text) : "";
+        if (low != "in" && low != "like")
+            throw BinderException(who + ": NOT IN or NOT LIKE is expected after \"" + col.text + "\" in filter \"" +
+                                  filter + "\"");
+        negate = true;
+        (low == "in" ? in_list : like) = true;
+    }
+    if (in_list || like) {
+        if (like) ParseLike(sch, c, negate, lex, filter, clause, preds, strs);
+        else ParseInList(sch, c, negate, lex, filter, clause, preds, strs, conn, sets);
+        return;
+    }
+    p.clause = clause++;
+    if (op.kind == Token::WORD && StringUtil::Lower(op.text) == "is") {
+        Token t = lex.Next();
+        bool is_not = false;
+        if (t.kind == Token::WORD && StringUtil::Lower(t.text) == "not") {
+            is_not = true;
+            t = lex.Next();
+        }
+        if (t.kind != Token::WORD || StringUtil::Lower(t.text) != "null")
+            throw BinderException(who + ": IS [NOT] NULL is expected after \"" + col.text + "\" in filter \"" + filter +
+                                  "\"");
+        p.op = is_not ? FLS_CMP_IS_NOT_NULL : FLS_CMP_IS_NULL;
+    } else if (op.kind == Token::OP) {
+        p.op = op.text == "="                        ? FLS_CMP_EQ
+               : (op.text == "!=" || op.text == "<>") ? FLS_CMP_NE
+               : op.text == "<"                      ? FLS_CMP_LT
+               : op.text == "<="                     ? FLS_CMP_LE
+               : op.text == ">"                      ? FLS_CMP_GT
+                                                     : FLS_CMP_GE;
+        // the right side: a column when it is an identifier the schema resolves and
+        // neither NULL nor the start of a typed literal (DATE '...'); else a literal
+        Token rhs = lex.Next();
+        const string low = rhs.kind == Token::WORD ? StringUtil::Lower(rhs.text) : "";
+        bool typed = false;
+        if (low == "date") {
+            const size_t after = lex.pos;
+            typed = lex.Next().kind == Token::STRING;
+            lex.pos = after;
+        }
+        const bool word = rhs.kind == Token::WORD && low != "null" && !typed;
+        const int c2 = word ? sch.Find(rhs.text) : -1;
+        if (c2 >= 0) {
+            CheckColumnPair(sch, c, c2, who, filter);
+            p.op = (uint8_t)(FLS_CMP_COL_EQ + p.op);
+            p.value = (uint64_t)c2;
+        } else if (word && low != "date") {
+            // a word that names no column is still a literal where it was one before (nan, inf,
+            // infinity on a FLOAT / DOUBLE column, true / false on a BOOLEAN one); only a word
+            // the literal parser refuses as well is reported as an unknown column
+            try {
+                SetLiteral(sch, c, lex, rhs, filter, p, strs);
+            } catch (const BinderException &) {
+                throw BinderException(who + ": column \"" + rhs.text + "\" on the right of \"" + col.text + " " +
+                                      op.text + "\" in filter \"" + filter + "\" not found");
+            }
+        } else {
+            SetLiteral(sch, c, lex, rhs, filter, p, strs);
+        }
+    } else {
+        throw BinderException(who + ": a comparison or IS [NOT] NULL is expected after \"" + col.text +
+                              "\" in filter \"" + filter + "\"");
+    }
+    preds.push_back(p);
+}
+
+// filter := item (AND item)*
+// item   := term | '(' branch (OR branch)+ ')'
+// branch := term | '(' term (AND term)* ')'
+// The AND-ed terms go to preds; the OR group (at most one, 2 to 8 branches)
+// to alts, a branch an alternative.  alts == NULL (the condition text of an
+// aggregate's FILTER (WHERE ...)): no OR group.
 inline void ParseFilter(const Schema &sch, const string &filter, std::vector<fls_predicate> &preds,
                         std::deque<string> &strs, const string &who = "fastlanes_aggregate",
-                        fls_connection *conn = nullptr, KeySets *sets = nullptr) {
+                        fls_connection *conn = nullptr, KeySets *sets = nullptr, Alternatives *alts = nullptr) {
     if (Trim(filter).empty()) return;
     Lexer lex(filter, who);
     uint32_t clause = 0;
+    auto open_paren = [](const Token &t) { return t.kind == Token::PUNCT && t.text == "("; };
+    auto close_paren = [](const Token &t) { return t.kind == Token::PUNCT && t.text == ")"; };
+    auto is_word = [](const Token &t, const char *w) { return t.kind == Token::WORD && StringUtil::Lower(t.text) == w; };
+    auto shown = [](const Token &t) { return t.kind == Token::END ? string("end of text") : t.text; };
     for (;;) {
-        Token col = lex.Next();
-        if (col.kind != Token::WORD)
-            throw BinderException(who + ": a column name is expected at \"" + col.text + "\" in filter \"" + filter + "\"");
-        const int c = sch.Find(col.text);
-        if (c < 0) throw BinderException(who + ": column \"" + col.text + "\" of filter \"" + filter + "\" not found");
-        fls_predicate p;
-        memset(&p, 0, sizeof(p));
-        p.col = (uint32_t)c;
-        Token op = lex.Next();
-        bool in_list = op.kind == Token::WORD && StringUtil::Lower(op.text) == "in", negate = false;
-        bool like = op.kind == Token::WORD && StringUtil::Lower(op.text) == "like";
-        if (op.kind == Token::WORD && StringUtil::Lower(op.text) == "not") {
-            Token t = lex.Next();
-            const string low = t.kind == Token::WORD ? StringUtil::Lower(t.text) : "";
-            if (low != "in" && low != "like")
-                throw BinderException(who + ": NOT IN or NOT LIKE is expected after \"" + col.text + "\" in filter \"" +
-                                      filter + "\"");
-            negate = true;
-            (low == "in" ? in_list : like) = true;
-        }
-        if (in_list || like) {
-            if (like) ParseLike(sch, c, negate, lex, filter, clause, preds, strs);
-            else ParseInList(sch, c, negate, lex, filter, clause, preds, strs, conn, sets);
-            Token next = lex.Next();
-            if (next.kind == Token::END) return;
-            if (next.kind != Token::WORD || StringUtil::Lower(next.text) != "and")
-                throw BinderException(who + ": only AND joins filter terms, found \"" + next.text + "\" in filter \"" +
-                                      filter + "\"");
-            continue;
-        }
-        p.clause = clause++;
-        if (op.kind == Token::WORD && StringUtil::Lower(op.text) == "is") {
-            Token t = lex.Next();
-            bool is_not = false;
-            if (t.kind == Token::WORD && StringUtil::Lower(t.text) == "not") {
-                is_not = true;
-                t = lex.Next();
-            }
-            if (t.kind != Token::WORD || StringUtil::Lower(t.text) != "null")
-                throw BinderException(who + ": IS [NOT] NULL is expected after \"" + col.text + "\" in filter \"" + filter +
-                                      "\"");
-            p.op = is_not ? FLS_CMP_IS_NOT_NULL : FLS_CMP_IS_NULL;
-        } else if (op.kind == Token::OP) {
-            p.op = op.text == "="                        ? FLS_CMP_EQ
-                   : (op.text == "!=" || op.text == "<>") ? FLS_CMP_NE
-                   : op.text == "<"                      ? FLS_CMP_LT
-                   : op.text == "<="                     ? FLS_CMP_LE
-                   : op.text == ">"                      ? FLS_CMP_GT
-                                                         : FLS_CMP_GE;
-            // the right side: a column when it is an identifier the schema resolves and
-            // neither NULL nor the start of a typed literal (DATE '...'); else a literal
-            Token rhs = lex.Next();
-            const string low = rhs.kind == Token::WORD ? StringUtil::Lower(rhs.text) : "";
-            bool typed = false;
-            if (low == "date") {
-                const size_t after = lex.pos;
-                typed = lex.Next().kind == Token::STRING;
-                lex.pos = after;
-            }
-            const bool word = rhs.kind == Token::WORD && low != "null" && !typed;
-            const int c2 = word ? sch.Find(rhs.text) : -1;
-            if (c2 >= 0) {
-                CheckColumnPair(sch, c, c2, who, filter);
-                p.op = (uint8_t)(FLS_CMP_COL_EQ + p.op);
-                p.value = (uint64_t)c2;
-            } else if (word && low != "date") {
-                // a word that names no column is still a literal where it was one before (nan, inf,
-                // infinity on a FLOAT / DOUBLE column, true / false on a BOOLEAN one); only a word
-                // the literal parser refuses as well is reported as an unknown column
-                try {
-                    SetLiteral(sch, c, lex, rhs, filter, p, strs);
-                } catch (const BinderException &) {
-                    throw BinderException(who + ": column \"" + rhs.text + "\" on the right of \"" + col.text + " " +
-                                          op.text + "\" in filter \"" + filter + "\" not found");
+        const size_t at = lex.pos;
+        Token first = lex.Next();
+        if (open_paren(first)) {
+            const string rest = Trim(filter.substr(at));
+            if (!alts)
+                throw BinderException(who + ": an OR group is not supported in a FILTER (WHERE ...) condition, found \"" +
+                                      rest + "\" in \"" + filter + "\"");
+            if (!alts->ranges.empty())
+                throw BinderException(who + ": a second OR group \"" + rest + "\" in filter \"" + filter +
+                                      "\" (one per filter)");
+            for (;;) {  // a branch
+                if (alts->ranges.size() == kMaxBranches)
+                    throw BinderException(who + ": more than " + std::to_string(kMaxBranches) +
+                                          " branches in the OR group of filter \"" + filter + "\"");
+                fls_filter_alternative r;
+                r.first = (uint32_t)alts->preds.size();
+                uint32_t local = 0;  // clause numbers are the alternative's own
+                const size_t bat = lex.pos;
+                Token t = lex.Next();
+                if (open_paren(t)) {
+                    for (;;) {
+                        const size_t tat = lex.pos;
+                        t = lex.Next();
+                        if (open_paren(t))
+                            throw BinderException(who + ": a parenthesis nested deeper than a branch at \"" +
+                                                  Trim(filter.substr(tat)) + "\" in filter \"" + filter + "\"");
+                        ParseTerm(sch, lex, t, filter, local, alts->preds, strs, conn, sets);
+                        t = lex.Next();
+                        if (close_paren(t)) break;
+                        if (!is_word(t, "and"))
+                            throw BinderException(who + ": AND or \")\" is expected in the branch \"" +
+                                                  Trim(filter.substr(bat, lex.pos - bat)) + "\", found \"" + shown(t) +
+                                                  "\" in filter \"" + filter + "\"");
+                    }
+                } else {
+                    ParseTerm(sch, lex, t, filter, local, alts->preds, strs, conn, sets);
                 }
-            } else {
-                SetLiteral(sch, c, lex, rhs, filter, p, strs);
+                r.n = (uint32_t)alts->preds.size() - r.first;
+                alts->ranges.push_back(r);
+                t = lex.Next();
+                if (close_paren(t)) break;
+                if (!is_word(t, "or"))
+                    throw BinderException(who + ": OR or \")\" is expected after the branch \"" +
+                                          Trim(filter.substr(bat, lex.pos - bat)) + "\", found \"" + shown(t) +
+                                          "\" (a branch of several terms takes its own parentheses) in filter \"" +
+                                          filter + "\"");
             }
+            if (alts->ranges.size() < 2)
+                throw BinderException(who + ": \"(\" opens an OR group of 2 to 8 branches, \"" +
+                                      Trim(filter.substr(at, lex.pos - at)) + "\" holds no OR in filter \"" + filter + "\"");
         } else {
-            throw BinderException(who + ": a comparison or IS [NOT] NULL is expected after \"" + col.text +
-                                  "\" in filter \"" + filter + "\"");
+            ParseTerm(sch, lex, first, filter, clause, preds, strs, conn, sets);
         }
-        preds.push_back(p);
         Token next = lex.Next();
         if (next.kind == Token::END) return;
-        if (next.kind != Token::WORD || StringUtil::Lower(next.text) != "and")
+        if (!is_word(next, "and"))
             throw BinderException(who + ": only AND joins filter terms, found \"" + next.text + "\" in filter \"" + filter +
                                   "\"");
     }

@@ -15,15 +15,23 @@
 //               An item may end in `FILTER (WHERE <filter text>)` (keywords in
 //               any case): the aggregate over the rows of the call's filter
 //               where that condition holds too, in the grammar of the third
-//               argument (IN lists, LIKE and column pairs included; no OR, no
-//               other parentheses).  Items with identical condition text share
+//               argument (IN lists, LIKE and column pairs included; no OR
+//               group).  Items with identical condition text share
 //               one condition (fls_aggregate_conditions, at most 8); the
 //               item's name and type are what they are without the clause.
 //   filter:     `term AND term ...`, a term `column op literal` (op one of
 //               = != <> < <= > >=) or `column IS [NOT] NULL`.  Literals by
 //               column type: integers, decimal numbers the column's scale
 //               represents exactly, DATE 'YYYY-MM-DD', floats, single-quoted
-//               strings ('' escapes a quote).  No OR, no parentheses.
+//               strings ('' escapes a quote); IN lists, LIKE and column pairs
+//               as table_function/filter_text.hpp describes them.  Among the
+//               AND-ed items one parenthesised OR group may stand,
+//                 filter := item (AND item)*
+//                 item   := term | '(' branch (OR branch)+ ')'
+//                 branch := term | '(' term (AND term)* ')'
+//               with 2 to 8 branches (TPC-H Q19's shape): the branches become
+//               the filter's alternatives (fls_scan_filter_alternatives).  No
+//               OR outside parentheses, no second group, nothing nested deeper.
 //
 // `fastlanes_aggregate(path, aggregates, filter, group_by)` returns one row per
 // group of a low-cardinality GROUP BY (fls_aggregate_grouped): group_by is a
@@ -85,6 +93,7 @@ struct AggBindData : public TableFunctionData {
     std::vector<fls_predicate> preds;
     std::deque<string> pred_strs;        // VARCHAR constants the predicates point at
     std::shared_ptr<KeySets> pred_sets = std::make_shared<KeySets>();  // the key sets of the filter's IN lists
+    Alternatives alts;                   // the filter's OR group (fls_scan_filter_alternatives; empty: none)
     // the items' FILTER (WHERE ...) conditions: spec.cond - 1 indexes conds, which
     // index cond_preds (fls_aggregate_conditions); cond_texts[i] is condition i as written
     std::vector<fls_predicate> cond_preds;
@@ -390,7 +399,7 @@ unique_ptr<FunctionData> AggBind(ClientContext &, TableFunctionBindInput &input,
                               std::to_string(bind->specs.size()));
     if (input.inputs.size() >= 3)
         ParseFilter(sch, input.inputs[2].GetValue<string>(), bind->preds, bind->pred_strs, "fastlanes_aggregate", conn,
-                    bind->pred_sets.get());
+                    bind->pred_sets.get(), &bind->alts);
     return_types = bind->types;
     if (input.inputs.size() == 4) {
         // the key columns come first, named and typed as the table's columns
@@ -441,6 +450,8 @@ void AggScanGrouped(const AggBindData &bind, AggGlobalState &g, DataChunk &outpu
     if (!g.done) {
         g.done = true;
         if (fls_scan_filter(t, bind.preds.data(), (uint32_t)bind.preds.size()) != 0 ||
+            fls_scan_filter_alternatives(t, bind.alts.preds.data(), (uint32_t)bind.alts.preds.size(),
+                                         bind.alts.ranges.data(), (uint32_t)bind.alts.ranges.size()) != 0 ||
             fls_aggregate_exprs(t, bind.exprs.data(), (uint32_t)bind.exprs.size()) != 0 ||
             fls_aggregate_conditions(t, bind.cond_preds.data(), (uint32_t)bind.cond_preds.size(), bind.conds.data(),
                                      (uint32_t)bind.conds.size()) != 0)
@@ -449,6 +460,7 @@ void AggScanGrouped(const AggBindData &bind, AggGlobalState &g, DataChunk &outpu
                                              (uint32_t)bind.specs.size(), 0, fls_table_nrowgroups(t), &g.groups);
         const string err = rc ? fls_last_error() : "";
         fls_scan_filter(t, nullptr, 0);
+        fls_scan_filter_alternatives(t, nullptr, 0, nullptr, 0);
         fls_aggregate_exprs(t, nullptr, 0);
         fls_aggregate_conditions(t, nullptr, 0, nullptr, 0);
         if (rc == FLS_ERR_LIMIT)
@@ -496,6 +508,8 @@ void AggScan(ClientContext &, TableFunctionInput &data, DataChunk &output) {
     fls_table *t = bind.table->table;
     std::vector<fls_aggregate_value> vals(bind.specs.size());
     if (fls_scan_filter(t, bind.preds.data(), (uint32_t)bind.preds.size()) != 0 ||
+        fls_scan_filter_alternatives(t, bind.alts.preds.data(), (uint32_t)bind.alts.preds.size(), bind.alts.ranges.data(),
+                                     (uint32_t)bind.alts.ranges.size()) != 0 ||
         fls_aggregate_exprs(t, bind.exprs.data(), (uint32_t)bind.exprs.size()) != 0 ||
         fls_aggregate_conditions(t, bind.cond_preds.data(), (uint32_t)bind.cond_preds.size(), bind.conds.data(),
                                  (uint32_t)bind.conds.size()) != 0)
@@ -503,6 +517,7 @@ void AggScan(ClientContext &, TableFunctionInput &data, DataChunk &output) {
     const int rc = fls_aggregate(t, bind.specs.data(), (uint32_t)bind.specs.size(), 0, fls_table_nrowgroups(t), vals.data());
     const string err = rc ? fls_last_error() : "";
     fls_scan_filter(t, nullptr, 0);
+    fls_scan_filter_alternatives(t, nullptr, 0, nullptr, 0);
     fls_aggregate_exprs(t, nullptr, 0);
     fls_aggregate_conditions(t, nullptr, 0, nullptr, 0);
     if (rc == FLS_ERR_ARG) throw OutOfRangeException("fastlanes_aggregate: " + err);  // the SUM_PRODUCT / SUM_EXPR bound

@@ -12,7 +12,11 @@
 //             DECIMAL, FLOAT and DOUBLE columns; equal keys come in table
 //             order.
 //   k:        INTEGER, 0 to 1024.
-//   filter:   fastlanes_aggregate's grammar (table_function/filter_text.hpp);
+//   filter:   fastlanes_aggregate's grammar (table_function/filter_text.hpp),
+//             its one parenthesised OR group included:
+//               filter := item (AND item)*
+//               item   := term | '(' branch (OR branch)+ ')'
+//               branch := term | '(' term (AND term)* ')'
 //             empty or blank means none.
 //   columns:  a comma-separated list of the columns to return, in that
 //             order; empty or absent means all, in table order.
@@ -59,6 +63,7 @@ struct TopnBindData : public TableFunctionData {
     std::vector<fls_predicate> preds;
     std::deque<string> pred_strs;        // VARCHAR constants the predicates point at
     std::shared_ptr<KeySets> pred_sets = std::make_shared<KeySets>();  // the key sets of the filter's IN lists
+    Alternatives alts;                   // the filter's OR group (fls_scan_filter_alternatives; empty: none)
     std::shared_ptr<TopnTable> table;    // opened at bind (footer only)
 };
 
@@ -169,7 +174,7 @@ unique_ptr<FunctionData> TopnBind(ClientContext &, TableFunctionBindInput &input
     ParseOrderBy(sch, input.inputs[1].GetValue<string>(), bind->key);
     if (input.inputs.size() >= 4)
         ParseFilter(sch, input.inputs[3].GetValue<string>(), bind->preds, bind->pred_strs, kWho, conn,
-                    bind->pred_sets.get());
+                    bind->pred_sets.get(), &bind->alts);
     ParseColumns(sch, input.inputs.size() == 5 ? input.inputs[4].GetValue<string>() : string(), bind->out_cols);
     bind->mask.assign(sch.cols.size(), 0);
     for (uint32_t c : bind->out_cols) {
@@ -225,11 +230,14 @@ void TopnScan(ClientContext &, TableFunctionInput &data, DataChunk &output) {
     fls_table *t = bind.table->table;
     if (!g.done) {
         g.done = true;
-        if (fls_scan_filter(t, bind.preds.data(), (uint32_t)bind.preds.size()) != 0)
+        if (fls_scan_filter(t, bind.preds.data(), (uint32_t)bind.preds.size()) != 0 ||
+            fls_scan_filter_alternatives(t, bind.alts.preds.data(), (uint32_t)bind.alts.preds.size(),
+                                         bind.alts.ranges.data(), (uint32_t)bind.alts.ranges.size()) != 0)
             throw IOException(string("FastLanes top-N failed: ") + fls_last_error());
         const int rc = fls_topn(t, &bind.key, bind.k, bind.mask.data(), 0, fls_table_nrowgroups(t), &g.result);
         const string err = rc ? fls_last_error() : "";
         fls_scan_filter(t, nullptr, 0);
+        fls_scan_filter_alternatives(t, nullptr, 0, nullptr, 0);
         if (rc == FLS_ERR_ARG || rc == FLS_ERR_LIMIT) throw InvalidInputException(string(kWho) + ": " + err);
         if (rc) throw IOException("FastLanes top-N failed: " + err);
     }

@@ -327,6 +327,44 @@ int fls_scan_next(fls_table *t, fls_rowgroup *out);
  * only qualifying rows (fls_rowgroup.nrows / sel), in row order.  The
  * filter's columns are decoded whether or not col_mask delivers them. */
 int fls_scan_filter(fls_table *t, const fls_predicate *preds, uint32_t n);
+/* Alternatives of the filter: AND-groups joined by OR (TPC-H Q19's shape), for
+ * the following fls_scan_begin, fls_aggregate*, fls_topn and every other call
+ * that honours fls_scan_filter
+ * (copied and replaced as a whole; at most 8 alternatives; nalts = 0 clears;
+ * sticky like the filter, which fls_scan_filter keeps replacing alone).  A row
+ * is selected when the filter set by fls_scan_filter selects it (an empty
+ * filter selects every row) and at least one alternative is true there; it
+ * counts once however many hold.  Alternative i is a filter of its own,
+ * preds[first .. first + n) in the shape fls_scan_filter takes: a conjunction
+ * of clauses (`clause` numbers are local to the alternative), a clause OR-ed
+ * `column op constant` / IS [NOT] NULL terms or a single key-set, LIKE or
+ * column-pair term; its key sets are kept alive as the filter keeps them, and
+ * the filter's limits (8 pattern terms, 256 tokens) hold per alternative.  A
+ * comparison on a NULL is not true, so `A OR B` selects a row when A is true
+ * or B is true.  One alternative alone equals AND-ing its terms to the filter.
+ * An aggregate condition (fls_aggregate_conditions) holds no alternatives.
+ * Pruning: a row group is read when the filter may match it and at least one
+ * alternative may (zone maps, DICT dictionaries, key-set keys and LIKE on
+ * dictionaries per alternative, as for the filter); fls_scan_pruned, the
+ * aggregate calls' overflow bounds and "no row group left" paths follow that
+ * set, and a top-N scan with alternatives counts as filtered (no zone-map cut
+ * on the key).  fls_rowgroup_may_match takes explicit terms and ignores the
+ * list.  On the GPU, after the filter's kernels, one launch per batch
+ * (csrc/fls_alt.hip) evaluates the ordinary terms of every alternative and
+ * ORs those that hold nothing else into the mask; an alternative with key-set,
+ * LIKE or column-pair terms gets a plane that the filter's kernels narrow, and
+ * one more launch ORs the planes into the mask.  The consumers' kernels see an
+ * ordinary mask.  The columns alternatives read are decoded whether or not
+ * they are delivered.
+ * FLS_ERR_ARG before any device work: more than 8 alternatives; "alternative
+ * i:" n == 0 or a range past npreds; "alternative i, term j: <the refusal
+ * fls_scan_filter gives the term>", j and the clause numbers local to the
+ * alternative (the three "shares clause" refusals included); in
+ * fls_aggregate_grouped an alternative term that reads a VARCHAR key column
+ * (the filter's rule).  Not in the reference. */
+typedef struct fls_filter_alternative { uint32_t first, n; } fls_filter_alternative;   /* preds[first .. first + n) */
+int fls_scan_filter_alternatives(fls_table *t, const fls_predicate *preds, uint32_t npreds,
+                                 const fls_filter_alternative *alts, uint32_t nalts);
 /* Row groups the current scan skipped by zone maps / dictionaries. */
 int fls_scan_pruned(const fls_table *t);
 
