@@ -125,6 +125,12 @@ class KeySetInfo(C.Structure):     # fls_keyset_info_t
                 ("max", C.c_uint64), ("empty", C.c_uint64)]
 
 
+class KeySetBuildInfo(C.Structure):     # fls_keyset_build_info_t
+    _fields_ = [("rows_selected", C.c_uint64), ("bitmap_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64),
+                ("base", C.c_uint64), ("span", C.c_uint64), ("rowgroups_read", C.c_uint32),
+                ("rowgroups_pruned", C.c_uint32)]
+
+
 # fls_keymap_form, FLS_KEY_MAPPED, FLS_KEYMAP_KEEP_UNMATCHED
 KEYMAP_AUTO, KEYMAP_DENSE, KEYMAP_HASH = 0, 1, 2
 KEYMAP_ABSENT = 0xFFFF             # kKeymapAbsent: no code
@@ -325,6 +331,8 @@ _sig("fls_keyset_create", C.c_int, _P, _P, C.c_uint64, C.c_int, C.c_int, C.POINT
 _sig("fls_keyset_free", None, _P)
 _sig("fls_keyset_info", C.c_int, _P, C.POINTER(KeySetInfo))
 _sig("fls_keyset_contains", C.c_int, _P, C.c_uint64)
+_sig("fls_keyset_from_scan", C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P),
+     C.POINTER(KeySetBuildInfo))
 _sig("fls_keymap_create", C.c_int, _P, _P, _P, C.c_uint64, C.c_int, C.c_int, C.POINTER(_P))
 _sig("fls_keymap_free", None, _P)
 _sig("fls_keymap_info", C.c_int, _P, C.POINTER(KeyMapInfo))
@@ -813,10 +821,12 @@ class KeyMap:
 
 class KeySet:
     """fls_keyset: the build side of a semi-join.  The handle is a token the
-    library looks up; a closed set in a filter is refused, never dereferenced."""
+    library looks up; a closed set in a filter is refused, never dereferenced.
+    build_info: the KeySetBuildInfo of a set Table.keyset built on the GPU
+    (fls_keyset_from_scan), None for a set built on the host."""
 
-    def __init__(self, h, conn):
-        self.h, self.conn = h, conn
+    def __init__(self, h, conn, build_info=None):
+        self.h, self.conn, self.build_info = h, conn, build_info
 
     @property
     def info(self) -> KeySetInfo:
@@ -1302,12 +1312,30 @@ class Table:
     def keyset(self, col: int, filt=None, form: int = KEYSET_AUTO) -> "KeySet":
         """The build side of a semi-join: the key set of the non-NULL values
         of one integer-like column (INT*, UINT*, BOOLEAN, DATE, DECIMAL of at
-        most 64 bits) over the rows filt selects (a filtered scan of that
-        column).  Use it as (col, "in_set", keyset) on this or another table
-        of the same connection."""
+        most 64 bits) over the rows filt selects.  Use it as
+        (col, "in_set", keyset) on this or another table of the same
+        connection.  Built on the GPU (fls_keyset_from_scan: the selected keys
+        are collected as bits over the range of the column's zone maps, and
+        the set's build_info says what that took); where that range is too
+        wide for the call (FlsError ERR_LIMIT), or with FLS_KEYSET_BUILD=host
+        in the environment, from a filtered scan of the column on the host.
+        The set is the same either way."""
         ci = self.column(col)
         if ci.type in STRING_TYPES or ci.type in (FLOAT, DOUBLE) or ci.out_bytes > 8:
             raise ValueError(f"keyset: column {col} ({TYPE_NAMES.get(ci.type, ci.type)}) is not integer-like")
+        # (a DECIMAL wider than 64 bits is no key column of a filter term or of the device build)
+        wide_decimal = ci.type == DECIMAL and ci.width > 18
+        if os.environ.get("FLS_KEYSET_BUILD", "") != "host" and not wide_decimal:
+            self.set_filter(filt or [])
+            try:
+                h, info = _P(), KeySetBuildInfo()
+                _check(_lib.fls_keyset_from_scan(self.h, col, 0, self.nrowgroups, form, C.byref(h), C.byref(info)))
+                return KeySet(h.value, self.conn, info)
+            except FlsError as e:
+                if e.code != ERR_LIMIT:
+                    raise
+            finally:
+                self._clear_filter()
         terms = list(filt or []) + [(col, "is_not_null", None)]
         parts = [arrs[col].view(NP_DTYPE[ci.type]) for _, _, _, arrs in self.scan_filtered(terms, cols=[col])]
         vals = np.concatenate(parts) if parts else np.zeros(0, NP_DTYPE[ci.type])

@@ -17,7 +17,10 @@
 //                         and the host merge
 //   fls_scan_topn.hip     fls_topn: checks, per-batch enqueue, the host merge
 //                         and the late materialisation
-//   fls_scan_keyset.hip   the key-set registry and fls_keyset_*
+//   fls_scan_keyset.hip   the key-set registry and fls_keyset_*; the build of a
+//                         set from a scan (fls_keyset_from_scan): checks, the
+//                         collecting range and its gate, per-batch enqueue, the
+//                         bitmaps' way back and the host finish
 //   fls_scan_keymap.hip   the key-map registry, fls_keymap_*, the bindings of
 //                         mapped GROUP BY keys and their per-batch probe
 //   fls_device_table.hip  the device-resident table (fls_device_*)
@@ -262,7 +265,7 @@ struct HostBatch {
     std::vector<PinBuf<uint8_t>> h_out;   // per delivered column (pinned)
     std::vector<PinBuf<uint8_t>> h_heap;  // per FSST column: pinned copy string_t points into
     std::vector<const void *> col_ptrs;   // per (rg - rg0) * ncols + col: pinned host column start
-    PinBuf<uint32_t> h_counts;            // filtered: selected rows per vector
+    PinBuf<uint32_t> h_counts;            // filtered: selected rows per vector (key-set build: rows that set a bit)
     PinBuf<uint32_t> h_sel;               // filtered: selected row indices within their row group
     uint32_t nvec = 0;                    // vectors of the batch
     bool sel_ready = false;               // sel_off computed from h_counts
@@ -561,6 +564,19 @@ enum class Reduce {
     GroupAggregate,  // fls_aggregate_grouped: per-row-group tables of groups (enqueue_group_aggregate)
     TopN,            // fls_topn: per-row-group candidate lists (enqueue_topn)
     HashAggregate,   // fls_aggregate_hashed: every batch into the pipeline's table in HBM (enqueue_hash_aggregate)
+    KeySet,          // fls_keyset_from_scan: every batch's keys into the GPU's collecting bitmap (enqueue_keyset_build)
+};
+
+// The collecting range and bitmaps of a key-set build (fls_scan_keyset.hip):
+// bit key - base of a bitmap over [base, base + span], span < kKeysetMaxSpan.
+// The bitmaps belong to the call, one per GPU its row groups shard over
+// (bitmaps[g] for ScanCtx::devs[g]; pipelines on one GPU share theirs),
+// allocated and zeroed before scan_start.
+struct KeyBuildPlan {
+    uint32_t col = 0;
+    uint64_t base = 0, span = 0;
+    bool window = true;                  // clustered words go through the wave's LDS window
+    std::vector<uint32_t *> bitmaps;     // per pipeline, in HBM (NULL: the pipeline reads no row group)
 };
 
 // The packed key and the tables of a hash aggregate (fls_scan_hashagg.hip):
@@ -604,8 +620,10 @@ struct ScanPlan {
     const HashPlan *hash = nullptr;
     const fls_order_key *order = nullptr;           // Reduce::TopN: the key and
     uint32_t k = 0;                                 // ... how many rows
+    const KeyBuildPlan *keybuild = nullptr;         // Reduce::KeySet: the key column, the range and the bitmaps
     // exactly these row groups (ascending, inside the range) instead of
-    // pruning the range: fls_topn's late materialisation
+    // pruning the range: fls_topn's late materialisation, and the survivors
+    // fls_keyset_from_scan took its range from
     const std::vector<uint32_t> *only = nullptr;
 };
 
@@ -632,7 +650,11 @@ struct ScanCtx {
     // ... where FLS_KEY_MAPPED | i stands for the code binding i gives its
     // column (keymap_kernel).  With a binding the scan always has a mask.
     std::vector<HostBinding> binds;
-    bool masked() const { return !terms.empty() || !alts.empty() || !binds.empty(); }
+    // key-set build (Reduce::KeySet): nothing is delivered, the batches' keys
+    // meet in the plan's bitmaps; their per-vector counts ride in the HostBatch.
+    // Such a scan always has a mask, as one with a binding has.
+    KeyBuildPlan keybuild;
+    bool masked() const { return !terms.empty() || !alts.empty() || !binds.empty() || reduce == Reduce::KeySet; }
     // hash aggregate scan (Reduce::HashAggregate): the key layout and the
     // pipelines' tables, and the groups one table may hold
     HashPlan hash;
@@ -768,6 +790,7 @@ struct fls_table {
     std::vector<int> devices;          // the connection's GPUs (row groups shard over them)
     std::shared_ptr<MappedFile> mapped;  // fls_read_fls: the file and its validated metadata (shared)
     std::shared_ptr<fls::engine::ConnRes> res;  // the connection's scan resources (outlive a disconnect)
+    const fls_connection *conn = nullptr;  // who owns the sets built from this table (a token: never dereferenced)
     std::vector<uint8_t> owned;
     const uint8_t *img = nullptr;
     uint64_t len = 0;
@@ -854,6 +877,7 @@ int enqueue_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t r
 int enqueue_group_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);  // fls_scan_agg.hip
 int enqueue_topn(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);             // fls_scan_topn.hip
 int enqueue_hash_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);   // fls_scan_hashagg.hip
+int enqueue_keyset_build(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);     // fls_scan_keyset.hip
 
 // ---- what the aggregate calls share (fls_scan_agg.hip) ---------------------------
 

@@ -170,6 +170,30 @@ enum : uint32_t { KERR_KEYSET = 512 };
 hipError_t launch_keyset(const DevSetTerm *d_terms, uint32_t nterms, uint32_t nrows, uint64_t *d_mask,
                          uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
 
+// The build of a key set from a scan (fls_keyset_from_scan) as
+// keyset_build_kernel sees a batch: the selected, valid rows' keys of one
+// column are collected as bits of a bitmap over [base, base + span] that the
+// call's batches on one GPU share (bit d = key - base: bit d & 31 of dword
+// d >> 5; span < 2^32, so the bitmap has span / 32 + 1 dwords at most 2^27).
+struct DevKeyBuild {          // 56 B, a kernel argument
+    const uint8_t *col;       // decoded column of the batch in HBM (row 0 of the batch)
+    const uint64_t *valid;    // as DevTerm::valid
+    const uint64_t *mask;     // the batch's selection mask, 16 words per vector
+    uint32_t *bitmap;         // the collecting bitmap of the call on this GPU
+    uint64_t base, span;
+    uint32_t nrows;
+    uint8_t ob, sign;         // bytes per decoded value; values sign-extend to 64 bits
+    uint8_t window;           // clustered words go through the wave's LDS window (0: one global atomic per row)
+    uint8_t pad;
+};
+static_assert(sizeof(DevKeyBuild) == 56, "DevKeyBuild is 56 B");
+// a selected, valid key outside [base, base + span]: the zone maps that gave
+// the range do not bound the data (corrupt or foreign file); it sets no bit
+enum : uint32_t { KERR_KEYBUILD = 32768 };
+// Collects the batch's keys into p.bitmap and writes per vector the rows that
+// set a bit into d_counts (fls_keyset_build.hip).
+hipError_t launch_keyset_build(const DevKeyBuild &p, uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
+
 // One column term (OP_COL_EQ .. OP_COL_GE) as colcmp_kernel sees it, rebuilt
 // per scan batch.  A row stays selected when both values are valid and
 // `a op b` holds: op_holds(op, cmp_int | cmp_uint | cmp_float) over the values

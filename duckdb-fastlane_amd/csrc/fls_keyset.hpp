@@ -3,7 +3,10 @@
 //
 // Host only (no HIP include): a set is built, queried and used for pruning
 // without a GPU, and a stand-alone CPU program can drive this header
-// (tests/fuzz/fuzz_keyset.cpp).  The image built here is the very byte
+// (tests/fuzz/fuzz_keyset.cpp, tests/fuzz/keyset_bitmap_host.cpp).  A set is
+// built from a key list (keyset_build) or from the bitmap a scan collected its
+// keys in (keyset_from_bitmap, fls_keyset_from_scan); both end in
+// keyset_finish.  The image built here is the very byte
 // sequence the scan uploads; keyset_contains probes it the way keyset_kernel
 // (fls_keyset.hip) does.
 //
@@ -108,17 +111,19 @@ inline bool keyset_contains(const KeysetImage &s, uint64_t key) {
     return false;
 }
 
-// Builds the set of keys[0, n): n is checked before keys is read.
-inline int keyset_build(const uint64_t *keys, uint64_t n, bool is_signed, uint32_t form, KeysetImage &out) {
+// The second half of every construction: out.is_signed is set and out.keys
+// holds the distinct keys, ascending in the set's order; chooses the form
+// (the auto rule above) and fills min / max / span, the bitmap or the hash
+// table, the sentinel and max_probe.
+inline int keyset_finish(KeysetImage &out, uint32_t form) {
     if (form > KS_HASH) return KS_BAD_FORM;
-    if (n > kMaxKeysetKeys) return KS_TOO_MANY;
-    out = KeysetImage();
-    out.is_signed = is_signed;
-    out.keys.assign(keys, keys + n);
-    std::sort(out.keys.begin(), out.keys.end(),
-              [is_signed](uint64_t a, uint64_t b) { return keyset_ord(a, is_signed) < keyset_ord(b, is_signed); });
-    out.keys.erase(std::unique(out.keys.begin(), out.keys.end()), out.keys.end());
     const uint64_t nd = out.keys.size();
+    if (nd > kMaxKeysetKeys) return KS_TOO_MANY;
+    out.min = out.max = out.span = 0;
+    out.cap_log2 = 0;
+    out.empty = ~0ull;
+    out.max_probe = 0;
+    out.words.clear();
     if (nd) {
         out.min = out.keys.front();
         out.max = out.keys.back();
@@ -157,6 +162,43 @@ inline int keyset_build(const uint64_t *keys, uint64_t n, bool is_signed, uint32
         out.max_probe = std::max(out.max_probe, probes);
     }
     return KS_OK;
+}
+
+// Builds the set of keys[0, n): n is checked before keys is read.
+inline int keyset_build(const uint64_t *keys, uint64_t n, bool is_signed, uint32_t form, KeysetImage &out) {
+    if (form > KS_HASH) return KS_BAD_FORM;
+    if (n > kMaxKeysetKeys) return KS_TOO_MANY;
+    out = KeysetImage();
+    out.is_signed = is_signed;
+    out.keys.assign(keys, keys + n);
+    std::sort(out.keys.begin(), out.keys.end(),
+              [is_signed](uint64_t a, uint64_t b) { return keyset_ord(a, is_signed) < keyset_ord(b, is_signed); });
+    out.keys.erase(std::unique(out.keys.begin(), out.keys.end()), out.keys.end());
+    return keyset_finish(out, form);
+}
+
+// Builds the set a collecting bitmap holds (the device build of
+// fls_keyset_from_scan): bit d of words[0, span / 64 + 1), d <= span, stands
+// for the key base + d (mod 2^64); bits past span are ignored.  base is the
+// smallest value of the collecting range in the set's order, so ascending d
+// is that order (the caller keeps base + span from wrapping past the order's
+// end).  The image equals keyset_build's over the same keys: the count is
+// checked before a key is stored.
+inline int keyset_from_bitmap(const uint64_t *words, uint64_t base, uint64_t span, bool is_signed, uint32_t form,
+                              KeysetImage &out) {
+    if (form > KS_HASH) return KS_BAD_FORM;
+    const uint64_t nw = span / 64 + 1;
+    const uint64_t last = (span & 63) == 63 ? ~0ull : (1ull << ((span & 63) + 1)) - 1;  // the last word's bits <= span
+    uint64_t n = 0;
+    for (uint64_t i = 0; i < nw; ++i) n += (uint64_t)__builtin_popcountll(i + 1 == nw ? words[i] & last : words[i]);
+    if (n > kMaxKeysetKeys) return KS_TOO_MANY;
+    out = KeysetImage();
+    out.is_signed = is_signed;
+    out.keys.reserve(n);
+    for (uint64_t i = 0; i < nw; ++i)
+        for (uint64_t w = i + 1 == nw ? words[i] & last : words[i]; w; w &= w - 1)
+            out.keys.push_back(base + (i * 64 + (uint64_t)__builtin_ctzll(w)));
+    return keyset_finish(out, form);
 }
 
 }  // namespace fls

@@ -779,6 +779,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     s.reduce = Reduce::None;
     if (p.aggs) s.reduce = p.hash ? Reduce::HashAggregate : p.keys ? Reduce::GroupAggregate : Reduce::Aggregate;
     else if (p.order && p.k) s.reduce = Reduce::TopN;
+    else if (p.keybuild) s.reduce = Reduce::KeySet;
     // the delivery options: consumers' scans only (not materialize); a reducing scan delivers nothing
     const bool options = p.delivering_scan && s.reduce == Reduce::None;
     s.dict_codes = options && t->dict_codes;
@@ -802,8 +803,14 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     bool string_key = false;
     s.hash = HashPlan();
     s.max_groups = 0;
+    s.keybuild = KeyBuildPlan();
     switch (s.reduce) {
     case Reduce::None: break;
+    case Reduce::KeySet:
+        // a key-set build decodes the filter's columns and its key column
+        s.keybuild = *p.keybuild;
+        s.dmask[s.keybuild.col] = 1;
+        break;
     case Reduce::HashAggregate:
         // the key columns (plain integer-like columns) and the operands are
         // decoded, as a grouped aggregate scan's are
@@ -975,6 +982,7 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
         if (!(c & FLS_KEY_MAPPED)) need[c] = 1;
     for (const HostBinding &b : s.binds) need[b.col] = 1;
     if (s.reduce == Reduce::TopN) need[s.tkey.col] = 1;
+    if (s.reduce == Reduce::KeySet) need[s.keybuild.col] = 1;
     for (uint32_t c = 0; c < ncols; ++c) {
         bool any = false;
         for (uint32_t r = sl.rg0; need[c] && r < sl.rg0 + sl.nrg; ++r)
@@ -1710,6 +1718,7 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
         case Reduce::GroupAggregate: rc = enqueue_group_aggregate(t, s, d, sl, rows, lo); break;  // tables of groups
         case Reduce::TopN: rc = enqueue_topn(t, s, d, sl, rows, lo); break;                       // candidate lists
         case Reduce::HashAggregate: rc = enqueue_hash_aggregate(t, s, d, sl, rows, lo); break;    // into the pipeline's table
+        case Reduce::KeySet: rc = enqueue_keyset_build(t, s, d, sl, rows, lo); break;             // into the GPU's bitmap
         }
         if (rc) return rc;
     }
@@ -1929,6 +1938,9 @@ static int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
         if (err & KERR_COLCMP)
             return fail(FLS_ERR_FORMAT, "filter: damaged column-comparison descriptor (flags 0x%x)", err);
         if (err & KERR_KEYMAP) return fail(FLS_ERR_FORMAT, "grouped aggregate: damaged key-map descriptor (flags 0x%x)", err);
+        if (err & KERR_KEYBUILD)
+            return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a key-set build's key column "
+                        "(flags 0x%x)", err);
         if (err & KERR_NARROW)
             return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a narrowed column (flags 0x%x)", err);
         if (err & KERR_HASH_RANGE)
@@ -2223,6 +2235,7 @@ static int open_common(fls_connection *conn, fls_table *t, fls_table **out) {
     }
     t->devices = conn->devices;
     t->res = conn->res;
+    t->conn = conn;
     for (auto &c : t->meta.cols) t->names.push_back(c.name);
     *out = t;
     if (debug_enabled())
@@ -2407,6 +2420,7 @@ int fls_read_fls(fls_connection *conn, const char *path, fls_table **out) {
             t->meta = hit->meta;
             t->devices = conn->devices;
             t->res = conn->res;
+            t->conn = conn;
             for (auto &c : t->meta.cols) t->names.push_back(c.name);
             *out = t;
             return 0;

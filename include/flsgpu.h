@@ -296,6 +296,43 @@ int fls_keyset_info(const fls_keyset *set, fls_keyset_info_t *info);
 /* Host probe of the very image a scan uploads: 1 in the set, 0 not. */
 int fls_keyset_contains(const fls_keyset *set, uint64_t key);
 
+/* The build side on the GPU: the set of the non-NULL values of column col over
+ * the rows of row groups [rg_begin, rg_end) that the filter and alternatives
+ * currently set on the table select (fls_scan_filter,
+ * fls_scan_filter_alternatives) -- the set fls_keyset_create builds from those
+ * values, image for image: the same form under the auto rule, min / max,
+ * sentinel, max_probe and sorted keys.  Its kind follows the column (signed:
+ * INT*, DATE, DECIMAL; unsigned: UINT*, BOOLEAN); it belongs to the table's
+ * connection and is used, queried and freed like any other set.
+ * The scan decodes the filter's, the alternatives' and the key column and
+ * delivers nothing: the selected keys are collected on each GPU as bits of a
+ * bitmap over the union of the key column's zone maps over the row groups
+ * that survive pruning (the physical type's range where one of them has no
+ * zone map; a row group whose key chunk is all NULL is skipped), and the host
+ * receives span / 8 bytes per GPU instead of the keys.  That needs
+ *   span + 1 <= 2^32, and
+ *   a bitmap of at most 1 MiB, or no larger than the surviving row groups'
+ *   rows times the column's width (the copy it replaces);
+ * otherwise FLS_ERR_LIMIT before any device work, the message naming the span
+ * and both sizes: build the set from a filtered scan and fls_keyset_create.
+ * No surviving row group (an empty table or range, everything pruned) gives
+ * the empty set without device work.
+ * FLS_ERR_ARG before any device work: a column out of range, a VARCHAR / BLOB
+ * / FLOAT / DOUBLE column, a DECIMAL wider than 64 bits, a form outside 0..2,
+ * a row-group range outside the table.  FLS_ERR_FORMAT: a decoded key outside
+ * the zone maps that gave the range (it sets no bit).
+ * FLS_KEYSET_BUILD_WINDOW=0 (A/B) sends every row's atomic straight to HBM
+ * instead of combining clustered rows in LDS first.  Not in the reference. */
+typedef struct fls_keyset_build_info_t {
+    uint64_t rows_selected;   /* selected, non-NULL rows that set a bit */
+    uint64_t bitmap_bytes;    /* per device */
+    uint64_t d2h_bytes;       /* everything the build copied to the host */
+    uint64_t base, span;      /* the collecting range */
+    uint32_t rowgroups_read, rowgroups_pruned;
+} fls_keyset_build_info_t;
+int fls_keyset_from_scan(fls_table *t, uint32_t col, uint32_t rg_begin, uint32_t rg_end, int form, fls_keyset **out,
+                         fls_keyset_build_info_t *info /* may be NULL */);
+
 /* Connection::read_fls(): parse footer + schema (no GPU work). */
 int fls_read_fls(fls_connection *conn, const char *path, fls_table **out);
 /* Same over an in-memory image (copy=0: caller keeps img alive). */

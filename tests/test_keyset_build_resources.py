@@ -1,0 +1,26 @@
+"""keyset_build_kernel (csrc/fls_keyset_build.hip) collects a batch's selected
+keys into the call's bitmap: one kernel, no scratch, no spill, at most 64 VGPRs
+(eight waves per SIMD) and in LDS the four waves' 64-dword windows and their
+counts.  Read from the built library's gfx950 code
+object; no GPU is needed."""
+import sys
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parents[1]
+LIB = ROOT / "duckdb-fastlane_amd" / "libflsgpu.so"
+
+
+def test_keyset_build_kernel_resources():
+    if not LIB.exists():
+        pytest.skip("libflsgpu.so not built")
+    sys.path.insert(0, str(ROOT / "scripts"))
+    import kernel_resources
+    res = kernel_resources.resources(str(LIB))
+    hits = {k: v for k, v in res.items() if "keyset_build_kernel" in k}
+    assert len(hits) == 1, sorted(res)
+    for name, r in hits.items():
+        assert r["scratch"] == 0 and r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0, (name, r)
+        assert r["vgpr"] + r["agpr"] <= 64, (name, r)
+        assert r["lds"] <= 4 * 64 * 4 + 4 * 4, (name, r)
