@@ -63,7 +63,8 @@ class RowGroup(C.Structure):
 
 
 class Predicate(C.Structure):
-    _fields_ = [("col", C.c_uint32), ("clause", C.c_uint32), ("op", C.c_uint8), ("pad", C.c_uint8 * 7),
+    _fields_ = [("col", C.c_uint32), ("clause", C.c_uint32), ("op", C.c_uint8), ("pad", C.c_uint8 * 3),
+                ("key_col", C.c_uint32),   # MAP_EQ .. MAP_GE: the key column (the tail of what was pad[7])
                 ("value", C.c_uint64), ("str", C.c_char_p), ("str_len", C.c_uint64)]
 
 
@@ -72,11 +73,14 @@ EQ, NE, LT, LE, GT, GE, IS_NULL, IS_NOT_NULL = range(8)
 OPS = {"=": EQ, "==": EQ, "!=": NE, "<>": NE, "<": LT, "<=": LE, ">": GT, ">=": GE,
        "is_null": IS_NULL, "is_not_null": IS_NOT_NULL, "false": 8,
        "in_set": 9, "not_in_set": 10, "like": 11, "not_like": 12,
-       "col=": 13, "col!=": 14, "col<": 15, "col<=": 16, "col>": 17, "col>=": 18}
+       "col=": 13, "col!=": 14, "col<": 15, "col<=": 16, "col>": 17, "col>=": 18,
+       "map=": 19, "map!=": 20, "map<": 21, "map<=": 22, "map>": 23, "map>=": 24}
 IN_SET, NOT_IN_SET = 9, 10
 LIKE, NOT_LIKE = 11, 12
 MAX_PATTERN_TERMS, MAX_PATTERN_TOKENS = 8, 256   # kMaxPatTerms, kMaxPatTokens
 COL_EQ, COL_NE, COL_LT, COL_LE, COL_GT, COL_GE = range(13, 19)
+MAP_EQ, MAP_NE, MAP_LT, MAP_LE, MAP_GT, MAP_GE = range(19, 25)
+MAX_MAP_TERMS = 8                  # kMaxMapTerms
 
 
 class Col:
@@ -94,6 +98,20 @@ class Col:
 
     def __hash__(self):
         return hash(("Col", self.index))
+
+
+class Mapped:
+    """the right-hand side of a map filter term: (a, "<", Mapped(key_col, vm))
+    holds for the rows where column a and column key_col are valid, the key is
+    in the ValueMap vm and a < vm[key]; a NULL on either side or an absent
+    key satisfies no operator, "!=" included"""
+
+    def __init__(self, key_col: int, valuemap):
+        self.key_col = int(key_col)
+        self.valuemap = valuemap
+
+    def __repr__(self):
+        return f"Mapped({self.key_col}, {self.valuemap!r})"
 
 
 def _pat_bytes(x, what):
@@ -143,6 +161,19 @@ class KeyMapInfo(C.Structure):     # fls_keymap_info_t
     _fields_ = [("count", C.c_uint64), ("form", C.c_uint32), ("kind", C.c_uint32), ("device_bytes", C.c_uint64),
                 ("capacity", C.c_uint64), ("max_probe", C.c_uint32), ("max_code", C.c_uint32), ("min", C.c_uint64),
                 ("max", C.c_uint64), ("empty", C.c_uint64)]
+
+
+# fls_valuemap_form
+VALUEMAP_AUTO, VALUEMAP_DENSE, VALUEMAP_HASH = 0, 1, 2
+VALUEMAP_MAX_SPAN = 1 << 28        # kValuemapMaxSpan
+VALUEMAP_SMALL_DENSE = 1 << 20     # kValuemapSmallDense (bytes)
+
+
+class ValueMapInfo(C.Structure):   # fls_valuemap_info_t
+    _fields_ = [("count", C.c_uint64), ("form", C.c_uint32), ("key_kind", C.c_uint32), ("value_kind", C.c_uint32),
+                ("max_probe", C.c_uint32), ("device_bytes", C.c_uint64), ("capacity", C.c_uint64),
+                ("key_min", C.c_uint64), ("key_max", C.c_uint64), ("value_min", C.c_uint64),
+                ("value_max", C.c_uint64), ("empty", C.c_uint64)]
 
 
 class KeyBinding(C.Structure):     # fls_key_binding
@@ -337,6 +368,10 @@ _sig("fls_keymap_create", C.c_int, _P, _P, _P, C.c_uint64, C.c_int, C.c_int, C.P
 _sig("fls_keymap_free", None, _P)
 _sig("fls_keymap_info", C.c_int, _P, C.POINTER(KeyMapInfo))
 _sig("fls_keymap_lookup", C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint32))
+_sig("fls_valuemap_create", C.c_int, _P, _P, _P, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(_P))
+_sig("fls_valuemap_free", None, _P)
+_sig("fls_valuemap_info", C.c_int, _P, C.POINTER(ValueMapInfo))
+_sig("fls_valuemap_lookup", C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64))
 _sig("fls_aggregate_key_bindings", C.c_int, _P, C.POINTER(KeyBinding), C.c_uint32)
 _sig("fls_aggregate", C.c_int, _P, C.POINTER(AggregateSpec), C.c_uint32, C.c_uint32, C.c_uint32,
      C.POINTER(AggregateValue))
@@ -759,6 +794,24 @@ class Connection:
                                       k.size, 0 if signed else 1, form, C.byref(h)))
         return KeyMap(h.value, self)
 
+    def valuemap(self, keys, values, signed: bool = True, value_signed: bool = True,
+                 form: int = VALUEMAP_AUTO) -> "ValueMap":
+        """A value map for (a, op, Mapped(key_col, valuemap)) filter terms
+        (fls_valuemap_create): keys as keyset() takes them, values integers of
+        the compared column's physical type (DATE days, DECIMAL scaled);
+        signed / value_signed the order of the keys / of the values (False for
+        UINT* and BOOLEAN columns).  A key listed with two values is refused.
+        form 0 auto / 1 dense / 2 hash table.  Built on the host; no GPU is
+        needed."""
+        k = _key_patterns(keys, "valuemap")
+        v = _key_patterns(values, "valuemap")
+        if v.size != k.size:
+            raise ValueError(f"valuemap: {k.size} keys and {v.size} values")
+        h = _P()
+        _check(_lib.fls_valuemap_create(self.h, k.ctypes.data if k.size else None, v.ctypes.data if v.size else None,
+                                        k.size, 0 if signed else 1, 0 if value_signed else 1, form, C.byref(h)))
+        return ValueMap(h.value, self)
+
     def close(self):
         if self.h:
             _lib.fls_disconnect(self.h)
@@ -810,6 +863,42 @@ class KeyMap:
     def close(self):
         if self.h:
             _lib.fls_keymap_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ValueMap:
+    """fls_valuemap: the build side of a join whose payload is a value a row
+    is compared with.  The handle is a token the library looks up; a closed
+    map in a filter term is refused, never dereferenced."""
+
+    def __init__(self, h, conn):
+        self.h, self.conn = h, conn
+
+    @property
+    def info(self) -> ValueMapInfo:
+        out = ValueMapInfo()
+        _check(_lib.fls_valuemap_info(self.h, C.byref(out)))
+        return out
+
+    def lookup(self, key: int):
+        """Host probe of the image a scan uploads: the value (an int in the
+        value kind's range), or None."""
+        val = C.c_uint64()
+        found = _check(_lib.fls_valuemap_lookup(self.h, int(key) & 0xFFFFFFFFFFFFFFFF, C.byref(val)))
+        if found != 1:
+            return None
+        v = val.value
+        return v - (1 << 64) if self.info.value_kind == 0 and v >> 63 else v
+
+    def close(self):
+        if self.h:
+            _lib.fls_valuemap_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -1155,7 +1244,13 @@ class Table:
         `<`, `<=`, `>`, `>=` (or (a, "col<", b) with the index itself): both
         values valid and a op b; a clause of its own; two signed or two
         unsigned integer columns of any widths, two DATE, two DECIMAL of one
-        scale, or FLOAT / DOUBLE in any mix."""
+        scale, or FLOAT / DOUBLE in any mix.
+        A column against a joined attribute: (a, op, Mapped(key_col, vm)) with
+        op one of the six and vm a ValueMap (or (a, "map<", (key_col, vm)), or
+        (a, "map<", vm) with the left column as its own key):
+        both columns valid, the key in the map and a op vm[key]; a clause of
+        its own, at most 8 per list; integer-like columns whose signedness
+        matches the map's value / key kind."""
         if any(isinstance(term, AnyOf) for term in filt):
             raise ValueError("an AnyOf is an element of a call's filt, not of a condition, an alternative or "
                              "may_match's terms")
@@ -1179,7 +1274,17 @@ class Table:
                     raise TypeError(f"filter term {i}: operator {op!r} takes no column on its right")
                 p.op += COL_EQ
                 val = val.index
-            if COL_EQ <= p.op <= COL_GE:
+            if isinstance(val, Mapped):
+                if p.op > GE:
+                    raise TypeError(f"filter term {i}: operator {op!r} takes no mapped value on its right")
+                p.op += MAP_EQ
+                val = (val.key_col, val.valuemap)
+            if MAP_EQ <= p.op <= MAP_GE:
+                kc, vm = val if isinstance(val, tuple) else (col, val)   # (a map alone: keyed by the left column itself)
+                p.key_col = int(kc) & 0xFFFFFFFF
+                p.value = (vm.h or 0) if isinstance(vm, ValueMap) else int(vm)   # the map's handle
+                keep.append(vm)
+            elif COL_EQ <= p.op <= COL_GE:
                 p.value = int(val) & 0xFFFFFFFFFFFFFFFF   # the right column's index, no literal conversion
             elif p.op in (LIKE, NOT_LIKE):
                 pat, esc = val if isinstance(val, tuple) else (val, None)
@@ -1364,6 +1469,27 @@ class Table:
             raise ValueError(f"keymap: value {bad} of column {value_col} is outside [0, 65534]")
         signed = cis[0].type in (INT8, INT16, INT32, INT64, DATE, DECIMAL)
         return self.conn.keymap(keys, vals.astype(np.uint16), signed=signed, form=form)
+
+    def valuemap(self, key_col: int, value_col: int, filt=None, form: int = VALUEMAP_AUTO) -> "ValueMap":
+        """The build side of a join: the value map key_col -> value_col of two
+        integer-like columns of this (dimension) table over the rows filt
+        selects; rows with a NULL in either column are left out, and a key
+        with two different values raises.  A host build, like keymap().  Use
+        it as (a, op, Mapped(col, valuemap)) on this or another table of the
+        same connection."""
+        cis = [self.column(c) for c in (key_col, value_col)]
+        for c, ci in zip((key_col, value_col), cis):
+            if ci.type in STRING_TYPES or ci.type in (FLOAT, DOUBLE) or ci.out_bytes > 8:
+                raise ValueError(f"valuemap: column {c} ({TYPE_NAMES.get(ci.type, ci.type)}) is not integer-like")
+        terms = list(filt or []) + [(key_col, "is_not_null", None), (value_col, "is_not_null", None)]
+        ks, vs = [], []
+        for _, _, _, arrs in self.scan_filtered(terms, cols=sorted({key_col, value_col})):
+            ks.append(arrs[key_col].view(NP_DTYPE[cis[0].type]))
+            vs.append(arrs[value_col].view(NP_DTYPE[cis[1].type]))
+        keys = np.concatenate(ks) if ks else np.zeros(0, NP_DTYPE[cis[0].type])
+        vals = np.concatenate(vs) if vs else np.zeros(0, NP_DTYPE[cis[1].type])
+        sg = (INT8, INT16, INT32, INT64, DATE, DECIMAL)
+        return self.conn.valuemap(keys, vals, signed=cis[0].type in sg, value_signed=cis[1].type in sg, form=form)
 
     def set_key_bindings(self, bindings):
         """fls_aggregate_key_bindings: what a key KEY_MAPPED | i names in the

@@ -23,12 +23,15 @@
 //                         bitmaps' way back and the host finish
 //   fls_scan_keymap.hip   the key-map registry, fls_keymap_*, the bindings of
 //                         mapped GROUP BY keys and their per-batch probe
+//   fls_scan_valuemap.hip the value-map registry and fls_valuemap_*; the map
+//                         terms themselves are filter terms (flsgpu.hip)
 //   fls_device_table.hip  the device-resident table (fls_device_*)
 //
 // The pushdown and device-table units depend on flsgpu.hip's scan pipeline and
 // fls_launch.hip's launches; flsgpu.hip depends on them only through the four enqueue_*
 // functions fill_batch switches over, keyset_registry() and, for mapped GROUP
-// BY keys, enqueue_keymap, binding_may_match and keymap_registry().  Every function
+// BY keys, enqueue_keymap, binding_may_match and keymap_registry(), and for map
+// terms valuemap_registry().  Every function
 // and registry declared here is defined in exactly one unit.
 //
 // All of it lives in fls::engine, which is hidden: nothing here reaches
@@ -69,6 +72,7 @@
 #include "fls_strmatch.hpp"
 #include "fls_topn.hpp"
 #include "fls_tuning.hpp"
+#include "fls_valuemap.hpp"
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -347,6 +351,8 @@ struct Slot {                       // one batch of row groups in flight
     DevBuf<DevSetTerm> d_sdesc;
     PinBuf<DevColTerm> h_cdesc;     // the filter's column-to-column terms
     DevBuf<DevColTerm> d_cdesc;
+    PinBuf<DevMapCmpTerm> h_vdesc;  // the filter's map terms
+    DevBuf<DevMapCmpTerm> d_vdesc;
     PinBuf<uint8_t> h_pdesc;        // the filter's pattern terms: DevPatTerm[] + their tokens
     DevBuf<uint8_t> d_pdesc;
     std::vector<DevBuf<uint64_t>> d_valid;  // per filtered / aggregated column with a NULL: batch validity words
@@ -359,7 +365,7 @@ struct Slot {                       // one batch of row groups in flight
     DevBuf<DevAgg> d_adesc;
     DevBuf<AggRec> d_agg;           // partial records of the batch
     // the aggregates' conditions (fls_aggregate_conditions)
-    PinBuf<uint8_t> h_qdesc;        // DevTerm[] + DevColTerm[] + DevSetTerm[] + DevPatTerm[], then strings and tokens
+    PinBuf<uint8_t> h_qdesc;        // DevTerm[] + DevColTerm[] + DevSetTerm[] + DevMapCmpTerm[] + DevPatTerm[], then strings and tokens
     DevBuf<uint8_t> d_qdesc;
     DevBuf<uint64_t> d_cond;        // per condition a plane of 16 words per vector: where & cond
     DevBuf<uint32_t> d_ccounts;     // the narrowing kernels' per-vector counts of a plane (scratch)
@@ -522,6 +528,51 @@ struct KeyMapRegistry {
 };
 KeyMapRegistry &keymap_registry();  // (fls_scan_keymap.hip)
 
+// A value map (fls_valuemap_create): the host image and its copies in HBM,
+// held and uploaded as a key map's are (KeyMap::device_image).  Filters that
+// hold a map term and running scans hold a reference; the copies are outside
+// FLS_SCAN_RESIDENT_MB.
+struct ValueMap {
+    ValuemapImage img;
+    const fls_connection *conn = nullptr;
+    std::mutex mu;
+    std::vector<std::unique_ptr<DevBuf<uint64_t>>> copies;
+    // the image on GPU dev (the current device), uploaded on first use
+    hipError_t device_image(int dev, const uint64_t **out) {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto &c : copies)
+            if (c->dev == dev) {
+                *out = c->p;
+                return hipSuccess;
+            }
+        auto b = std::make_unique<DevBuf<uint64_t>>();
+        hipError_t e = b->alloc(dev, img.words.size());
+        // a synchronous copy: complete before any kernel enqueued after this call
+        if (e == hipSuccess && !img.words.empty())
+            e = hipMemcpy(b->p, img.words.data(), img.bytes(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return e;
+        *out = b->p;
+        copies.push_back(std::move(b));
+        return hipSuccess;
+    }
+};
+
+// Live value maps by handle: counter tokens with tag bits of their own, so no
+// key-set (| 0x5) or key-map (| 0xA) handle resolves as a value map, nor a
+// value map as either.
+struct ValueMapRegistry {
+    std::mutex mu;
+    uint64_t next = 1;
+    std::unordered_map<uint64_t, std::shared_ptr<ValueMap>> live;
+    static uint64_t handle_of(uint64_t id) { return (id << 4) | 0x3; }
+    std::shared_ptr<ValueMap> find(uint64_t handle) {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = live.find(handle);
+        return it == live.end() ? nullptr : it->second;
+    }
+};
+ValueMapRegistry &valuemap_registry();  // (fls_scan_valuemap.hip)
+
 // One mapped GROUP BY key (fls_aggregate_key_bindings), host side: the code
 // the map gives column col.
 struct HostBinding {
@@ -533,16 +584,21 @@ struct HostBinding {
 // One term of a pushed-down filter (fls_scan_filter), host side.
 struct HostTerm {
     uint32_t col = 0, clause = 0;
-    uint32_t col2 = 0;              // OP_COL_EQ .. OP_COL_GE: the right column
+    uint32_t col2 = 0;              // OP_COL_EQ .. OP_COL_GE: the right column; OP_MAP_EQ .. OP_MAP_GE: the key column
     uint8_t op = 0, kind = 0;
     uint64_t value = 0;             // comparison domain: int64 / uint64 / double bits
     std::string str;
     std::shared_ptr<KeySet> set;    // OP_IN_SET / OP_NOT_IN_SET
     std::shared_ptr<const CompiledPattern> pat;  // OP_LIKE / OP_NOT_LIKE
+    std::shared_ptr<ValueMap> map;  // OP_MAP_EQ .. OP_MAP_GE
 };
 inline bool is_set_op(uint8_t op) { return op == OP_IN_SET || op == OP_NOT_IN_SET; }
 inline bool is_pat_op(uint8_t op) { return op == OP_LIKE || op == OP_NOT_LIKE; }
 inline bool is_col_op(uint8_t op) { return op >= OP_COL_EQ && op <= OP_COL_GE; }
+inline bool is_map_op(uint8_t op) { return op >= OP_MAP_EQ && op <= OP_MAP_GE; }
+// does the term read a second column (HostTerm::col2) beside col?
+inline bool reads_col2(uint8_t op) { return is_col_op(op) || is_map_op(op); }
+constexpr uint32_t kMaxMapTerms = 8;  // map terms of one term list (a filter, a condition, an alternative)
 
 // One aggregate of fls_aggregate, host side.
 struct HostAgg {

@@ -33,6 +33,11 @@
 // this very shape of which at least one must hold beside it.  They prune a row
 // group none of them can match, and on the GPU alt_kernel / alt_merge_kernel
 // (fls_alt.hip) OR them into the mask the kernels above wrote.
+// A map term (`column op map[key column]`, OP_MAP_EQ .. OP_MAP_GE,
+// fls_valuemap.hpp) is a clause of its own too: pruned by the map's sorted
+// keys and its value range against the two zone maps and evaluated by
+// mapcmp_kernel (fls_mapcmp.hip), which narrows the mask after the key sets
+// -- its 8-byte gather is the dearest probe, so it sees the fewest rows.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -57,7 +62,11 @@ enum FilterOp : uint8_t {
     OP_LIKE = 11, OP_NOT_LIKE = 12,
     // column against column: op - OP_COL_EQ is OP_EQ .. OP_GE; a clause of its
     // own, evaluated by colcmp_kernel after filter_kernel, never by eval_term
-    OP_COL_EQ = 13, OP_COL_NE = 14, OP_COL_LT = 15, OP_COL_LE = 16, OP_COL_GT = 17, OP_COL_GE = 18
+    OP_COL_EQ = 13, OP_COL_NE = 14, OP_COL_LT = 15, OP_COL_LE = 16, OP_COL_GT = 17, OP_COL_GE = 18,
+    // column against the value a value map gives a key column of the same row
+    // (fls_valuemap.hpp): op - OP_MAP_EQ is OP_EQ .. OP_GE; a clause of its
+    // own, evaluated by mapcmp_kernel after keyset_kernel, never by eval_term
+    OP_MAP_EQ = 19, OP_MAP_NE = 20, OP_MAP_LT = 21, OP_MAP_LE = 22, OP_MAP_GT = 23, OP_MAP_GE = 24
 };
 
 __host__ __device__ inline bool op_holds(uint8_t op, int c) {
@@ -217,6 +226,36 @@ enum : uint32_t { KERR_COLCMP = 16384 };
 hipError_t launch_colcmp(const DevColTerm *d_terms, uint32_t nterms, uint32_t nrows, uint64_t *d_mask,
                          uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
 
+// One map term (OP_MAP_EQ .. OP_MAP_GE) as mapcmp_kernel sees it, rebuilt per
+// scan batch; the map's image (fls_valuemap.hpp) lives in HBM with the map.  A
+// row stays selected when the left value and the key are valid, the key is in
+// the map and `left op map[key]` holds: op_holds(op, cmp_int | cmp_uint) over
+// the left value sign- (vsign) or zero-extended to 64 bits and the map's value.
+// (DevMapTerm is the key maps' descriptor, fls_groupagg.hpp.)
+struct DevMapCmpTerm {        // 80 B
+    const uint8_t *a, *key;   // the decoded left / key column of the batch in HBM (row 0 of the batch)
+    const uint64_t *va, *vk;  // as DevTerm::valid, per column
+    const uint64_t *table;    // dense: values then presence words; hash: slots then values
+    uint64_t min, span;       // dense: value (key - min) for key - min <= span
+    uint64_t empty;           // hash: the empty slot's sentinel
+    uint32_t cap_log2;        // hash: log2 of the capacity
+    uint32_t max_probe;       // hash: slots a lookup examines at most
+    uint8_t form;             // VM_DENSE / VM_HASH
+    uint8_t oba, obk;         // bytes per decoded value: 1, 2, 4 or 8
+    uint8_t ksign, vsign;     // keys / left values sign-extend to 64 bits; vsign: the comparison is signed
+    uint8_t op;               // OP_EQ .. OP_GE
+    uint8_t pad[2];
+};
+static_assert(sizeof(DevMapCmpTerm) == 80 && sizeof(DevMapCmpTerm) % 16 == 0, "DevMapCmpTerm is 80 B");
+// a map-comparison descriptor no sound map produces (an unknown form, a width
+// outside {1, 2, 4, 8}, an op above OP_GE, a dense span or a capacity past the
+// format's limits, max_probe above the capacity)
+enum : uint32_t { KERR_MAPCMP = 65536 };
+// Narrows the mask and recomputes the counts launch_filter / launch_keyset
+// wrote for the same nrows rows (fls_mapcmp.hip).
+hipError_t launch_mapcmp(const DevMapCmpTerm *d_terms, uint32_t nterms, uint32_t nrows, uint64_t *d_mask,
+                         uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
+
 // One pattern term (OP_LIKE / OP_NOT_LIKE) as strmatch_kernel sees it, rebuilt
 // per scan batch; the tokens (fls_strmatch.hpp) follow the descriptors in one
 // buffer.  A row stays selected when its string is valid and matches (negate:
@@ -265,7 +304,7 @@ hipError_t launch_conditions(const DevTerm *d_terms, const CondList &conds, uint
 // The alternatives of a filter (fls_scan_filter_alternatives) as alt_kernel
 // sees them: alternative a's ordinary terms are terms[first[a] .. first[a + 1])
 // as in CondList (an empty range: the alternative starts from the mask); bit a
-// of `closed` is set when no key-set, column-pair or pattern term follows.
+// of `closed` is set when no key-set, column-pair, map or pattern term follows.
 struct AltList {
     uint32_t first[kMaxConds + 1];
     uint32_t n;

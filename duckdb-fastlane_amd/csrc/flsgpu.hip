@@ -536,6 +536,30 @@ static bool term_may_match(const fls_table *t, uint32_t rg, const HostTerm &h) {
         default: return cmp(ahi, blo) >= 0;  // OP_GE
         }
     }
+    if (is_map_op(h.op)) {
+        // the key zone map against the map's sorted keys (as IN_SET prunes),
+        // then the left zone map against the map's value range as side b of a
+        // column term; the empty map matches nowhere
+        const ValuemapImage &vm = h.map->img;
+        if (vm.set.keys.empty()) return false;
+        if (r.zones.empty()) return true;
+        const ZoneMap &za = r.zones[h.col], &zk = r.zones[h.col2];
+        if (zk.flags & ZM_ALL_NULL) return false;  // no row with a valid key
+        if ((zk.flags & ZM_VALID) && !keyset_any_in_range(vm.set, zk.min, zk.max)) return false;
+        if (!(za.flags & ZM_VALID)) return true;
+        const uint64_t alo = za.min, ahi = za.max, blo = vm.vmin, bhi = vm.vmax;
+        auto cmp = [&](uint64_t x, uint64_t y) {
+            return vm.value_signed ? cmp_int((int64_t)x, (int64_t)y) : cmp_uint(x, y);
+        };
+        switch (h.op - OP_MAP_EQ) {
+        case OP_EQ: return cmp(alo, bhi) <= 0 && cmp(blo, ahi) <= 0;  // the ranges intersect
+        case OP_NE: return !(cmp(alo, ahi) == 0 && cmp(blo, bhi) == 0 && cmp(alo, blo) == 0);  // not one single value
+        case OP_LT: return cmp(alo, bhi) < 0;
+        case OP_LE: return cmp(alo, bhi) <= 0;
+        case OP_GT: return cmp(ahi, blo) > 0;
+        default: return cmp(ahi, blo) >= 0;  // OP_GE
+        }
+    }
     if (is_pat_op(h.op)) {
         // exact on a DICT chunk: some dictionary string matches (NOT LIKE: some does not)
         if (ch.hdr.enc != ENC_DICT) return true;  // FSST: no statistics
@@ -790,7 +814,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     auto decode_columns_of = [&](const std::vector<HostTerm> &terms) {
         for (auto &h : terms)
             if (h.op < OP_IS_NULL || is_set_op(h.op) || is_pat_op(h.op)) s.dmask[h.col] = 1;
-            else if (is_col_op(h.op)) s.dmask[h.col] = s.dmask[h.col2] = 1;
+            else if (reads_col2(h.op)) s.dmask[h.col] = s.dmask[h.col2] = 1;  // (a map term: the left and the key column)
     };
     decode_columns_of(s.terms);
     for (auto &a : s.alts) decode_columns_of(a);
@@ -962,13 +986,13 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
     need.assign(ncols, 0);
     for (auto &h : s.terms) {
         need[h.col] = 1;
-        if (is_col_op(h.op)) need[h.col2] = 1;
+        if (reads_col2(h.op)) need[h.col2] = 1;
     }
     for (auto *lists : {&s.alts, &s.conds})
         for (auto &q : *lists)
             for (auto &h : q) {
                 need[h.col] = 1;
-                if (is_col_op(h.op)) need[h.col2] = 1;
+                if (reads_col2(h.op)) need[h.col2] = 1;
             }
     for (auto &a : s.aggs) {
         if (a.fn == AGG_SUM_EXPR) {
@@ -1058,6 +1082,30 @@ static void fill_col_term(const fls_table *t, Slot &sl, const HostTerm &h, DevCo
     dc.f32b = t->meta.cols[h.col2].type == TY_FLOAT ? 1 : 0;
 }
 
+// (the full decoded values of the left and the key column, never a narrowed copy)
+static int fill_map_term(const fls_table *t, ScanDev &d, Slot &sl, const HostTerm &h, DevMapCmpTerm &dm) {
+    const std::vector<uint8_t> &need = sl.valid_staged;
+    const ValuemapImage &vi = h.map->img;
+    memset(&dm, 0, sizeof(dm));
+    dm.a = sl.d_out[h.col].p;
+    dm.key = sl.d_out[h.col2].p;
+    dm.va = need[h.col] ? sl.d_valid[h.col].p : nullptr;
+    dm.vk = need[h.col2] ? sl.d_valid[h.col2].p : nullptr;
+    HIP_TRY(h.map->device_image(d.dev, &dm.table));
+    dm.min = vi.set.min;
+    dm.span = vi.set.span;
+    dm.empty = vi.set.empty;
+    dm.cap_log2 = vi.set.cap_log2;
+    dm.max_probe = vi.set.max_probe;
+    dm.form = (uint8_t)vi.form;
+    dm.oba = (uint8_t)out_bytes_of(t, h.col);
+    dm.obk = (uint8_t)out_bytes_of(t, h.col2);
+    dm.ksign = vi.set.is_signed ? 1 : 0;
+    dm.vsign = vi.value_signed ? 1 : 0;
+    dm.op = (uint8_t)(h.op - OP_MAP_EQ);
+    return 0;
+}
+
 // Where the long strings of string column c of the batch live: a batch can
 // hold DICT and FSST chunks of the column (ENC_AUTO chooses per chunk), so
 // both ranges, each with its own device offset.
@@ -1113,16 +1161,17 @@ static void fill_term(const fls_table *t, Slot &sl, const HostTerm &h, uint64_t 
 
 // The descriptor block of several term lists -- the aggregates' conditions,
 // the filter's alternatives -- over the slot's decoded columns and staged
-// validity: DevTerm[], DevColTerm[], DevSetTerm[], DevPatTerm[], then the
-// constant strings and the pattern tokens, list after list within each array.
+// validity: DevTerm[], DevColTerm[], DevSetTerm[], DevMapCmpTerm[],
+// DevPatTerm[], then the constant strings and the pattern tokens, list after
+// list within each array.
 struct ListDescs {
     struct Kinds {
-        std::vector<const HostTerm *> ord, ccs, sets, pats;
+        std::vector<const HostTerm *> ord, ccs, sets, maps, pats;
         uint32_t ptok = 0;  // tokens of the list's pattern terms
     };
     std::vector<Kinds> kinds;            // per list
     uint32_t first[kMaxConds + 1] = {};  // list q's ordinary terms are DevTerm[first[q] .. first[q + 1])
-    size_t off_c = 0, off_s = 0, off_p = 0, bytes = 0;
+    size_t off_c = 0, off_s = 0, off_m = 0, off_p = 0, bytes = 0;
 };
 // Fills h_desc (the caller copies L.bytes of it to d_desc, whose addresses the
 // descriptors hold); at most kMaxConds lists.
@@ -1131,14 +1180,16 @@ static int build_list_descs(const fls_table *t, ScanDev &d, Slot &sl, const std:
                             ListDescs &L) {
     const uint32_t nq = (uint32_t)lists.size();
     L.kinds.assign(nq, ListDescs::Kinds());
-    size_t nt = 0, nc = 0, ns = 0, np = 0, tail = 0;
+    size_t nt = 0, nc = 0, ns = 0, nm = 0, np = 0, tail = 0;
     for (uint32_t q = 0; q < nq; ++q) {
         ListDescs::Kinds &k = L.kinds[q];
         for (auto &h : lists[q])
-            (is_set_op(h.op) ? k.sets : is_pat_op(h.op) ? k.pats : is_col_op(h.op) ? k.ccs : k.ord).push_back(&h);
+            (is_set_op(h.op) ? k.sets : is_pat_op(h.op) ? k.pats : is_col_op(h.op) ? k.ccs : is_map_op(h.op) ? k.maps : k.ord)
+                .push_back(&h);
         nt += k.ord.size();
         nc += k.ccs.size();
         ns += k.sets.size();
+        nm += k.maps.size();
         np += k.pats.size();
         for (auto *h : k.ord) tail += (h->str.size() + 15) & ~size_t(15);
         for (auto *h : k.pats) tail += (h->pat->tok.size() * sizeof(uint16_t) + 15) & ~size_t(15);
@@ -1146,7 +1197,8 @@ static int build_list_descs(const fls_table *t, ScanDev &d, Slot &sl, const std:
     // (every descriptor size is a multiple of 16, DevTerm's and DevPatTerm's of 32: each array stays aligned)
     L.off_c = nt * sizeof(DevTerm);
     L.off_s = L.off_c + nc * sizeof(DevColTerm);
-    L.off_p = (L.off_s + ns * sizeof(DevSetTerm) + 31) & ~size_t(31);
+    L.off_m = L.off_s + ns * sizeof(DevSetTerm);
+    L.off_p = (L.off_m + nm * sizeof(DevMapCmpTerm) + 31) & ~size_t(31);
     size_t so = L.off_p + np * sizeof(DevPatTerm);
     L.bytes = so + tail;
     HIP_TRY(h_desc.alloc(L.bytes));
@@ -1156,7 +1208,8 @@ static int build_list_descs(const fls_table *t, ScanDev &d, Slot &sl, const std:
     DevTerm *terms = (DevTerm *)qd;
     DevColTerm *cterms = (DevColTerm *)(qd + L.off_c);
     DevSetTerm *sterms = (DevSetTerm *)(qd + L.off_s);
-    size_t it = 0, ic = 0, is = 0, ip = 0;
+    DevMapCmpTerm *mterms = (DevMapCmpTerm *)(qd + L.off_m);
+    size_t it = 0, ic = 0, is = 0, im = 0, ip = 0;
     for (uint32_t q = 0; q < nq; ++q) {
         ListDescs::Kinds &k = L.kinds[q];
         L.first[q] = (uint32_t)it;
@@ -1172,6 +1225,8 @@ static int build_list_descs(const fls_table *t, ScanDev &d, Slot &sl, const std:
         for (auto *h : k.ccs) fill_col_term(t, sl, *h, cterms[ic++]);
         for (auto *h : k.sets)
             if (int rc = fill_set_term(t, d, sl, *h, sterms[is++])) return rc;
+        for (auto *h : k.maps)
+            if (int rc = fill_map_term(t, d, sl, *h, mterms[im++])) return rc;
         for (auto *h : k.pats) {
             const CompiledPattern &cp = *h->pat;
             DevPatTerm dp;
@@ -1186,14 +1241,14 @@ static int build_list_descs(const fls_table *t, ScanDev &d, Slot &sl, const std:
     return 0;
 }
 
-// Each list's column, key-set and pattern terms narrow its plane (list q's at
+// Each list's column, key-set, map and pattern terms narrow its plane (list q's at
 // planes + q * 16 * nvec) through the filter's kernels, one launch per kind,
 // in the filter's order; their per-vector counts go to a scratch buffer.
 static int narrow_planes(ScanDev &d, Slot &sl, const ListDescs &L, const uint8_t *d_desc, uint64_t rows,
                          uint64_t *planes) {
     const size_t plane = (size_t)sl.hb->nvec * 16;
     HIP_TRY(sl.d_ccounts.alloc(d.dev, sl.hb->nvec));
-    size_t ic = 0, is = 0, ip = 0;
+    size_t ic = 0, is = 0, im = 0, ip = 0;
     for (size_t q = 0; q < L.kinds.size(); ++q) {
         const ListDescs::Kinds &k = L.kinds[q];
         uint64_t *pl = planes + plane * q;
@@ -1203,11 +1258,15 @@ static int narrow_planes(ScanDev &d, Slot &sl, const ListDescs &L, const uint8_t
         if (!k.sets.empty())
             HIP_TRY(launch_keyset((const DevSetTerm *)(d_desc + L.off_s) + is, (uint32_t)k.sets.size(), (uint32_t)rows, pl,
                                   sl.d_ccounts.p, d.err.p, sl.stream));
+        if (!k.maps.empty())
+            HIP_TRY(launch_mapcmp((const DevMapCmpTerm *)(d_desc + L.off_m) + im, (uint32_t)k.maps.size(), (uint32_t)rows,
+                                  pl, sl.d_ccounts.p, d.err.p, sl.stream));
         if (!k.pats.empty())
             HIP_TRY(launch_strmatch((const DevPatTerm *)(d_desc + L.off_p) + ip, (uint32_t)k.pats.size(), k.ptok,
                                     (uint32_t)rows, pl, sl.d_ccounts.p, d.err.p, sl.stream));
         ic += k.ccs.size();
         is += k.sets.size();
+        im += k.maps.size();
         ip += k.pats.size();
     }
     return 0;
@@ -1232,7 +1291,8 @@ static int enqueue_alternatives(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, 
     al.n = na;
     memcpy(al.first, L.first, sizeof(al.first));
     for (uint32_t a = 0; a < na; ++a)
-        if (L.kinds[a].ccs.empty() && L.kinds[a].sets.empty() && L.kinds[a].pats.empty()) al.closed |= 1u << a;
+        if (L.kinds[a].ccs.empty() && L.kinds[a].sets.empty() && L.kinds[a].maps.empty() && L.kinds[a].pats.empty())
+            al.closed |= 1u << a;
     HIP_TRY(sl.d_alt.alloc(d.dev, (size_t)sl.hb->nvec * 16 * na));
     HIP_TRY(hipMemcpyAsync(sl.d_altdesc.p, sl.h_altdesc.p, L.bytes, hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(launch_alternatives((const DevTerm *)sl.d_altdesc.p, al, (uint32_t)rows, sl.d_mask.p, sl.d_alt.p,
@@ -1264,10 +1324,13 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
     // before the key sets: two coalesced loads and a compare are cheaper than
     // a probe or a string match, and the later kernels skip the words it
     // empties (all clauses are AND-ed, so the order changes no result).
-    std::vector<const HostTerm *> ord, sets, pats, ccs;
+    // Map terms (a clause each) go to mapcmp_kernel after the key sets and
+    // before the patterns: its 8-byte gather then sees the rows the cheaper
+    // probes left.
+    std::vector<const HostTerm *> ord, sets, pats, ccs, maps;
     for (auto &h : s.terms)
-        (is_set_op(h.op) ? sets : is_pat_op(h.op) ? pats : is_col_op(h.op) ? ccs : ord).push_back(&h);
-    const size_t nt = ord.size(), no = outs.size(), ns = sets.size(), np = pats.size(), nc = ccs.size();
+        (is_set_op(h.op) ? sets : is_pat_op(h.op) ? pats : is_col_op(h.op) ? ccs : is_map_op(h.op) ? maps : ord).push_back(&h);
+    const size_t nt = ord.size(), no = outs.size(), ns = sets.size(), np = pats.size(), nc = ccs.size(), nm = maps.size();
     size_t str_bytes = 0;
     for (auto *h : ord) str_bytes += (h->str.size() + 15) & ~size_t(15);
     const size_t bytes = nt * sizeof(DevTerm) + no * sizeof(DevOut) + str_bytes;
@@ -1288,6 +1351,12 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
         HIP_TRY(sl.d_cdesc.alloc(d.dev, nc));
     }
     for (size_t i = 0; i < nc; ++i) fill_col_term(t, sl, *ccs[i], sl.h_cdesc.p[i]);
+    if (nm) {
+        HIP_TRY(sl.h_vdesc.alloc(nm));
+        HIP_TRY(sl.d_vdesc.alloc(d.dev, nm));
+    }
+    for (size_t i = 0; i < nm; ++i)
+        if (int rc = fill_map_term(t, d, sl, *maps[i], sl.h_vdesc.p[i])) return rc;
     // pattern descriptors, then each term's tokens (16-byte aligned)
     size_t pat_bytes = np * sizeof(DevPatTerm), total_tokens = 0;
     for (auto *h : pats) pat_bytes += (h->pat->tok.size() * sizeof(uint16_t) + 15) & ~size_t(15);
@@ -1329,6 +1398,11 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
     if (ns) {
         HIP_TRY(hipMemcpyAsync(sl.d_sdesc.p, sl.h_sdesc.p, ns * sizeof(DevSetTerm), hipMemcpyHostToDevice, sl.stream));
         HIP_TRY(launch_keyset(sl.d_sdesc.p, (uint32_t)ns, (uint32_t)rows, sl.d_mask.p, sl.d_counts.p, d.err.p,
+                              sl.stream));
+    }
+    if (nm) {
+        HIP_TRY(hipMemcpyAsync(sl.d_vdesc.p, sl.h_vdesc.p, nm * sizeof(DevMapCmpTerm), hipMemcpyHostToDevice, sl.stream));
+        HIP_TRY(launch_mapcmp(sl.d_vdesc.p, (uint32_t)nm, (uint32_t)rows, sl.d_mask.p, sl.d_counts.p, d.err.p,
                               sl.stream));
     }
     if (np) {
@@ -1494,13 +1568,13 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
     std::vector<uint8_t> code_w(ncols, 0), in_term(ncols, 0), is_key(ncols, 0);
     for (auto &h : s.terms) {
         in_term[h.col] = 1;
-        if (is_col_op(h.op)) in_term[h.col2] = 1;
+        if (reads_col2(h.op)) in_term[h.col2] = 1;
     }
     for (auto *lists : {&s.alts, &s.conds})
         for (auto &q : *lists)
             for (auto &h : q) {
                 in_term[h.col] = 1;
-                if (is_col_op(h.op)) in_term[h.col2] = 1;
+                if (reads_col2(h.op)) in_term[h.col2] = 1;
             }
     for (uint32_t c : s.keys)
         if (!(c & FLS_KEY_MAPPED)) is_key[c] = 1;
@@ -1937,6 +2011,8 @@ static int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
         if (err & KERR_PATTERN) return fail(FLS_ERR_FORMAT, "filter: damaged pattern descriptor (flags 0x%x)", err);
         if (err & KERR_COLCMP)
             return fail(FLS_ERR_FORMAT, "filter: damaged column-comparison descriptor (flags 0x%x)", err);
+        if (err & KERR_MAPCMP)
+            return fail(FLS_ERR_FORMAT, "filter: damaged map-comparison descriptor (flags 0x%x)", err);
         if (err & KERR_KEYMAP) return fail(FLS_ERR_FORMAT, "grouped aggregate: damaged key-map descriptor (flags 0x%x)", err);
         if (err & KERR_KEYBUILD)
             return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a key-set build's key column "
@@ -2114,7 +2190,7 @@ static int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std:
     for (uint32_t i = 0; i < n; ++i) {
         if (at) *at = i;
         if (p[i].col >= t->meta.cols.size()) return fail(FLS_ERR_ARG, "filter column %u out of range", p[i].col);
-        if (p[i].op > FLS_CMP_COL_GE) return fail(FLS_ERR_ARG, "filter operator %u unknown", p[i].op);
+        if (p[i].op > FLS_CMP_MAP_GE) return fail(FLS_ERR_ARG, "filter operator %u unknown", p[i].op);
         HostTerm h;
         h.col = p[i].col;
         h.clause = p[i].clause;
@@ -2175,6 +2251,46 @@ static int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std:
                     return fail(FLS_ERR_ARG, "filter term %u: a column term shares clause %u with term %u (a column "
                                 "term is a clause of its own; columns %u and %u)", i, p[i].clause, j, h.col, h.col2);
             h.kind = col_kind(t, h.col);
+        } else if (is_map_op(h.op)) {
+            // `column op map[key column]`: value is the value map's handle, key_col the key column
+            const uint32_t kc = p[i].key_col;
+            if (kc >= t->meta.cols.size())
+                return fail(FLS_ERR_ARG, "filter term %u: key column %u out of range (left column %u, %zu columns)", i,
+                            kc, h.col, t->meta.cols.size());
+            h.col2 = kc;
+            const ColumnMeta &ca = t->meta.cols[h.col], &ck = t->meta.cols[kc];
+            const uint8_t tk = ck.type;
+            if (type_is_string(ty) || type_is_string(tk) || type_is_float(ty) || type_is_float(tk) || !type_valid(ty) ||
+                !type_valid(tk))
+                return fail(FLS_ERR_ARG, "filter term %u: a map term cannot read a VARCHAR / BLOB / FLOAT / DOUBLE "
+                            "column (left column %u, key column %u)", i, h.col, kc);
+            if ((ty == TY_DECIMAL && ca.width > 18) || (tk == TY_DECIMAL && ck.width > 18))
+                return fail(FLS_ERR_ARG, "filter term %u: a map term cannot read a DECIMAL wider than 64 bits (left "
+                            "column %u, key column %u)", i, h.col, kc);
+            h.map = valuemap_registry().find(p[i].value);
+            if (!h.map)
+                // (worded as LIKE's refusal on a non-VARCHAR column is: without a live map the operator means nothing)
+                return fail(FLS_ERR_ARG, "filter term %u: filter operator %u unknown for value 0x%llx: not a live value "
+                            "map (left column %u, key column %u)", i, h.op, (unsigned long long)p[i].value, h.col, kc);
+            const ValuemapImage &vi = h.map->img;
+            if (vi.value_signed != type_is_signed(ty))
+                return fail(FLS_ERR_ARG, "filter term %u: the value map's value kind is %s, left column %u is %s (key "
+                            "column %u)", i, vi.value_signed ? "signed" : "unsigned", h.col,
+                            type_is_signed(ty) ? "signed" : "unsigned", kc);
+            if (vi.set.is_signed != type_is_signed(tk))
+                return fail(FLS_ERR_ARG, "filter term %u: the value map's key kind is %s, key column %u is %s (left "
+                            "column %u)", i, vi.set.is_signed ? "signed" : "unsigned", kc,
+                            type_is_signed(tk) ? "signed" : "unsigned", h.col);
+            for (uint32_t j = 0; j < n; ++j)
+                if (j != i && p[j].clause == p[i].clause)
+                    return fail(FLS_ERR_ARG, "filter term %u: a map term shares clause %u with term %u (a map term is "
+                                "a clause of its own; left column %u, key column %u)", i, p[i].clause, j, h.col, kc);
+            uint32_t nmap = 0;
+            for (uint32_t j = 0; j <= i; ++j) nmap += p[j].op >= FLS_CMP_MAP_EQ && p[j].op <= FLS_CMP_MAP_GE;
+            if (nmap > kMaxMapTerms)
+                return fail(FLS_ERR_ARG, "filter term %u: more than %u map terms in one term list (left column %u, key "
+                            "column %u)", i, kMaxMapTerms, h.col, kc);
+            h.kind = vi.value_signed ? FK_INT : FK_UINT;
         } else if (is_pat_op(h.op)) {
             if (ty != TY_VARCHAR)
                 return fail(FLS_ERR_ARG, "filter term %u: filter operator %u unknown for column %u: LIKE needs a "
@@ -2310,6 +2426,19 @@ void fls_disconnect(fls_connection *conn) {
     if (conn) {  // ... and its key maps (a binding or scan still using one keeps it alive)
         KeyMapRegistry &R = keymap_registry();
         std::vector<std::shared_ptr<KeyMap>> dead;  // released outside the lock
+        std::lock_guard<std::mutex> lk(R.mu);
+        for (auto it = R.live.begin(); it != R.live.end();) {
+            if (it->second->conn == conn) {
+                dead.push_back(std::move(it->second));
+                it = R.live.erase(it);
+            } else {
+                ++it;
+            }
+        }
+    }
+    if (conn) {  // ... and its value maps (a filter or scan still using one keeps it alive)
+        ValueMapRegistry &R = valuemap_registry();
+        std::vector<std::shared_ptr<ValueMap>> dead;  // released outside the lock
         std::lock_guard<std::mutex> lk(R.mu);
         for (auto it = R.live.begin(); it != R.live.end();) {
             if (it->second->conn == conn) {

@@ -148,7 +148,34 @@ typedef struct fls_rowgroup {
  * clause of its own, AND-ed with the rest).  A row group is pruned when
  * either side is all NULL or when the two zone maps exclude the comparison
  * (min(a) < max(b) for `<`, intersecting ranges for `=`, ...); a missing zone
- * map on either side keeps it. */
+ * map on either side keeps it.
+ * FLS_CMP_MAP_EQ .. FLS_CMP_MAP_GE compare a column with the value a value
+ * map (fls_valuemap_create below) gives a key column of the same row,
+ * `left op map[key]`: `op - FLS_CMP_MAP_EQ` is the ordinary comparison, `col`
+ * the left column, `key_col` the key column, `value` the map's handle; `str`
+ * and `str_len` are ignored.  The term holds for a row when the left column
+ * is valid, the key column is valid, the key (sign- or zero-extended to 64
+ * bits) is in the map and `left op map[key]` holds.  A NULL on either side,
+ * or a key the map does not hold, satisfies no operator, `!=` included: an
+ * inner join whose payload would be NULL otherwise.  The left value is sign-
+ * or zero-extended to 64 bits and compared as signed when the map's value
+ * kind is signed, as unsigned otherwise.  The map's values are in the left
+ * column's physical unit (DATE days, DECIMAL scaled): units are the caller's
+ * business, nothing is rescaled.  The key column may be the left column or
+ * any other column.  A map term is a clause of its own, AND-ed with the rest;
+ * at most 8 map terms per term list (a filter, one condition, one
+ * alternative).  FLS_ERR_ARG, naming the term and both columns, before any
+ * device work: a key column out of range; VARCHAR / BLOB / FLOAT / DOUBLE on
+ * either side; a DECIMAL wider than 64 bits on either side; a left column
+ * whose signedness differs from the map's value kind, a key column whose
+ * signedness differs from its key kind (signed ints, DATE and DECIMAL are
+ * signed; unsigned ints and BOOLEAN unsigned); a handle that is not a live
+ * value map ("filter operator 19 unknown for value 0x...: not a live value
+ * map"); a map term sharing its clause; more than 8 map terms in a list.
+ * A row group is pruned when the left or the key chunk is all NULL, the map
+ * is empty, the key zone map holds no key of the map (exact on a sorted
+ * column), or the left zone map against the map's [value_min, value_max]
+ * excludes the comparison as for a column term; a missing zone map keeps it. */
 typedef enum fls_cmp {
     FLS_CMP_EQ = 0, FLS_CMP_NE = 1, FLS_CMP_LT = 2, FLS_CMP_LE = 3, FLS_CMP_GT = 4, FLS_CMP_GE = 5,
     FLS_CMP_IS_NULL = 6, FLS_CMP_IS_NOT_NULL = 7,
@@ -156,20 +183,25 @@ typedef enum fls_cmp {
     FLS_CMP_IN_SET = 9, FLS_CMP_NOT_IN_SET = 10,
     FLS_CMP_LIKE = 11, FLS_CMP_NOT_LIKE = 12,
     FLS_CMP_COL_EQ = 13, FLS_CMP_COL_NE = 14, FLS_CMP_COL_LT = 15, FLS_CMP_COL_LE = 16, FLS_CMP_COL_GT = 17,
-    FLS_CMP_COL_GE = 18           /* column against column: value is the right column's index */
+    FLS_CMP_COL_GE = 18,          /* column against column: value is the right column's index */
+    FLS_CMP_MAP_EQ = 19, FLS_CMP_MAP_NE = 20, FLS_CMP_MAP_LT = 21, FLS_CMP_MAP_LE = 22, FLS_CMP_MAP_GT = 23,
+    FLS_CMP_MAP_GE = 24           /* column against map[key_col]: value is the fls_valuemap handle */
 } fls_cmp;
 typedef struct fls_predicate {
     uint32_t col;                 /* table column */
     uint32_t clause;
     uint8_t op;                   /* fls_cmp */
-    uint8_t pad[7];
+    uint8_t pad[3];
+    uint32_t key_col;             /* MAP_EQ .. MAP_GE: the key column; every other op ignores it
+                                     (the tail of what was pad[7]: size and offsets are unchanged) */
     uint64_t value;               /* constant in the column's physical type:
                                      signed ints / DATE days / DECIMAL scaled as
                                      int64, unsigned as uint64, FLOAT as IEEE
                                      binary32 bits (low 32), DOUBLE binary64 bits;
                                      IN_SET / NOT_IN_SET: the fls_keyset handle;
                                      LIKE / NOT_LIKE: the escape byte, 0 for none;
-                                     COL_EQ .. COL_GE: the right column's index */
+                                     COL_EQ .. COL_GE: the right column's index;
+                                     MAP_EQ .. MAP_GE: the fls_valuemap handle */
     const char *str;              /* VARCHAR constant or LIKE pattern (copied) */
     uint64_t str_len;
 } fls_predicate;
@@ -728,6 +760,64 @@ void fls_keymap_free(fls_keymap *map);
 int fls_keymap_info(const fls_keymap *map, fls_keymap_info_t *info);
 /* Host probe of the very image a scan uploads: 1 found (*code set), 0 absent. */
 int fls_keymap_lookup(const fls_keymap *map, uint64_t key, uint32_t *code);
+
+/* Value maps: the build side of a join whose payload is a value a row is
+ * compared with (FLS_CMP_MAP_EQ .. FLS_CMP_MAP_GE above): Q17's per-part
+ * quantity threshold, Q2's minimum supply cost, Q21's min / max supplier of an
+ * order, an order's date for `l_shipdate > o_orderdate + k`.  A value map is a
+ * function from 64-bit keys to 64-bit values, built on the host like a key map
+ * (keys[i] -> values[i], i in [0, n)); no GPU is needed to create a map, query
+ * it or prune with it.  key_kind and value_kind are each a fls_keyset_kind:
+ * the order of the keys (key_min / key_max, pruning) and of the values
+ * (value_min / value_max and the comparison).  Every 64-bit pattern is a
+ * value, 0 and 2^64 - 1 included.  A key listed twice with one value is kept
+ * once; with two values the map is no function: FLS_ERR_ARG naming the key
+ * and both values.  n = 0 is a valid empty map.
+ * form: 0 auto, 1 dense, 2 hash table.
+ *   dense: uint64[max - min + 1] indexed by key - min (mod 2^64), followed by
+ *          a presence bitmap uint64[(max - min + 64) / 64] (a 64-bit value
+ *          has no spare "absent" pattern: a hole holds value 0 and bit 0);
+ *          max - min + 1 <= 2^28.
+ *   hash:  the key set's table (8-byte slots, capacity, home slot, ascending
+ *          insertion, sentinel and max_probe exactly as documented above),
+ *          followed at byte 8 * capacity by uint64[capacity]: the slots'
+ *          values, 0 in empty slots.
+ *   auto:  dense when max - min + 1 <= 2^28 and the dense image is no larger
+ *          than the hash image (16 bytes per slot) would be, or at most
+ *          1 MiB; else the hash table.
+ * The image is a pure function of the map, whatever the order of the input.
+ * FLS_ERR_LIMIT: n above 2^28 (returned before keys or values is read), a
+ * forced dense map spanning more than 2^28 keys.
+ * Handles are opaque counter tokens looked up among the live value maps,
+ * never dereferenced; a stale, foreign, key-set or key-map handle is
+ * FLS_ERR_ARG (and a value-map handle is neither a key set nor a key map).  A
+ * filter holding a map term and a running scan hold references, so freeing
+ * the handle or disconnecting while they use the map is safe.  The image is
+ * uploaded to a GPU by the first batch that probes it there (synchronously,
+ * fls_valuemap_info.device_bytes per GPU), cached inside the map and freed
+ * with its last reference; it does not count against FLS_SCAN_RESIDENT_MB.
+ * One map may serve any number of tables.  Not in the reference. */
+typedef struct fls_valuemap fls_valuemap;
+typedef enum fls_valuemap_form { FLS_VALUEMAP_AUTO = 0, FLS_VALUEMAP_DENSE = 1, FLS_VALUEMAP_HASH = 2 } fls_valuemap_form;
+typedef struct fls_valuemap_info_t {
+    uint64_t count;         /* distinct keys */
+    uint32_t form;          /* the form chosen: FLS_VALUEMAP_DENSE or FLS_VALUEMAP_HASH */
+    uint32_t key_kind;      /* fls_keyset_kind of the keys */
+    uint32_t value_kind;    /* fls_keyset_kind of the values */
+    uint32_t max_probe;     /* hash: longest probe sequence (0 for a dense or an empty map) */
+    uint64_t device_bytes;  /* bytes of the image, per GPU that probes the map */
+    uint64_t capacity;      /* hash: slots (0 for a dense map) */
+    uint64_t key_min, key_max;      /* patterns, in the key kind's order (0 for the empty map) */
+    uint64_t value_min, value_max;  /* patterns, in the value kind's order (0 for the empty map) */
+    uint64_t empty;         /* hash: the empty slot's sentinel */
+} fls_valuemap_info_t;
+int fls_valuemap_create(fls_connection *conn, const uint64_t *keys, const uint64_t *values, uint64_t n,
+                        int key_kind /* fls_keyset_kind */, int value_kind /* fls_keyset_kind */, int form,
+                        fls_valuemap **out);
+void fls_valuemap_free(fls_valuemap *map);
+int fls_valuemap_info(const fls_valuemap *map, fls_valuemap_info_t *info);
+/* Host probe of the very image a scan uploads: 1 found (*value set), 0 absent. */
+int fls_valuemap_lookup(const fls_valuemap *map, uint64_t key, uint64_t *value);
 
 /* Mapped GROUP BY keys.  fls_aggregate_key_bindings sets the table's bindings
  * (copied and replaced as a whole; n <= 4; n = 0 clears; sticky like
