@@ -104,14 +104,37 @@ class Mapped:
     """the right-hand side of a map filter term: (a, "<", Mapped(key_col, vm))
     holds for the rows where column a and column key_col are valid, the key is
     in the ValueMap vm and a < vm[key]; a NULL on either side or an absent
-    key satisfies no operator, "!=" included"""
+    key satisfies no operator, "!=" included.
 
-    def __init__(self, key_col: int, valuemap):
+    A Mapped is also a column of its own, vm[key_col] (a 64-bit integer, NULL
+    where the key is NULL or absent), wherever an aggregate tuple takes a
+    column index -- ("sum", M), ("count", M), ("min" | "max", M),
+    ("sum_product", a, M), a sum_expr factor (k, sign, M), the same inside
+    When -- and as an element of aggregate_hashed's keys.  There it is an
+    inner join by default (a selected row without a mapped value leaves the
+    call's selection, count(*) included); keep_unmatched=True makes it a left
+    join: the row stays, operands skip it and as a key it forms the NULL
+    group.  In a filter term keep_unmatched=True is a ValueError: a NULL
+    satisfies no operator there already."""
+
+    def __init__(self, key_col: int, valuemap, keep_unmatched: bool = False):
         self.key_col = int(key_col)
         self.valuemap = valuemap
+        self.keep_unmatched = bool(keep_unmatched)
+
+    def _ident(self):
+        vm = self.valuemap
+        return (self.key_col, vm.h if isinstance(vm, ValueMap) else vm, id(vm), self.keep_unmatched)
+
+    def __eq__(self, other):
+        return isinstance(other, Mapped) and other._ident() == self._ident()
+
+    def __hash__(self):
+        return hash(("Mapped",) + self._ident())
 
     def __repr__(self):
-        return f"Mapped({self.key_col}, {self.valuemap!r})"
+        keep = ", keep_unmatched=True" if self.keep_unmatched else ""
+        return f"Mapped({self.key_col}, {self.valuemap!r}{keep})"
 
 
 def _pat_bytes(x, what):
@@ -165,6 +188,7 @@ class KeyMapInfo(C.Structure):     # fls_keymap_info_t
 
 # fls_valuemap_form
 VALUEMAP_AUTO, VALUEMAP_DENSE, VALUEMAP_HASH = 0, 1, 2
+KIND_SIGNED, KIND_UNSIGNED = 0, 1  # fls_keyset_kind: a map's key_kind / value_kind
 VALUEMAP_MAX_SPAN = 1 << 28        # kValuemapMaxSpan
 VALUEMAP_SMALL_DENSE = 1 << 20     # kValuemapSmallDense (bytes)
 
@@ -177,6 +201,16 @@ class ValueMapInfo(C.Structure):   # fls_valuemap_info_t
 
 
 class KeyBinding(C.Structure):     # fls_key_binding
+    _fields_ = [("col", C.c_uint32), ("flags", C.c_uint32), ("map", C.c_uint64)]
+
+
+# FLS_COL_MAPPED, FLS_VALUEMAP_KEEP_UNMATCHED
+COL_MAPPED = 0x40000000
+VALUEMAP_KEEP_UNMATCHED = 1
+MAX_VALUE_BINDINGS = 4             # kMaxValueBindings
+
+
+class ValueBinding(C.Structure):   # fls_value_binding
     _fields_ = [("col", C.c_uint32), ("flags", C.c_uint32), ("map", C.c_uint64)]
 
 
@@ -372,6 +406,7 @@ _sig("fls_valuemap_create", C.c_int, _P, _P, _P, C.c_uint64, C.c_int, C.c_int, C
 _sig("fls_valuemap_free", None, _P)
 _sig("fls_valuemap_info", C.c_int, _P, C.POINTER(ValueMapInfo))
 _sig("fls_valuemap_lookup", C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64))
+_sig("fls_aggregate_value_bindings", C.c_int, _P, C.POINTER(ValueBinding), C.c_uint32)
 _sig("fls_aggregate_key_bindings", C.c_int, _P, C.POINTER(KeyBinding), C.c_uint32)
 _sig("fls_aggregate", C.c_int, _P, C.POINTER(AggregateSpec), C.c_uint32, C.c_uint32, C.c_uint32,
      C.POINTER(AggregateValue))
@@ -894,7 +929,7 @@ class ValueMap:
         if found != 1:
             return None
         v = val.value
-        return v - (1 << 64) if self.info.value_kind == 0 and v >> 63 else v
+        return v - (1 << 64) if self.info.value_kind == KIND_SIGNED and v >> 63 else v
 
     def close(self):
         if self.h:
@@ -944,6 +979,9 @@ def _mask(t: "Table", cols) -> C.Array | None:
         return None
     m = (C.c_uint8 * t.ncols)()
     for c in cols:
+        if isinstance(c, Mapped) or (isinstance(c, int) and c & COL_MAPPED):
+            raise ValueError(f"column {c!r}: a mapped column cannot be delivered (it exists only inside an aggregate "
+                             "call, as an operand or a key of aggregate_hashed)")
         m[c] = 1
     return m
 
@@ -959,12 +997,24 @@ def _agg_exprs(exprs) -> C.Array:
     return arr
 
 
-def _agg_specs(aggs):
+def _mapped_col(x, binds):
+    """a column index as given, or for a Mapped COL_MAPPED | its place in
+    binds, the call's list of distinct Mapped objects (appended to)"""
+    if not isinstance(x, Mapped):
+        return x
+    if x not in binds:
+        binds.append(x)
+    return COL_MAPPED | binds.index(x)
+
+
+def _agg_specs(aggs, binds=None):
     """fls_aggregate_spec[] of aggregate()'s tuples, the factor lists of its
     ("sum_expr", [...]) items in the order their specs index them, and the
     distinct conditions of its When items in the order their specs' cond - 1
     index them (equal conditions share one); a first element that is an int is
-    passed through as the function code"""
+    passed through as the function code.  A Mapped in a column's place becomes
+    COL_MAPPED | i and joins binds, the call's value bindings."""
+    binds = [] if binds is None else binds
     arr = (AggregateSpec * max(1, len(aggs)))()
     exprs, conds = [], []
     for i, a in enumerate(aggs[:len(arr)]):
@@ -977,13 +1027,14 @@ def _agg_specs(aggs):
         if fn == "sum_expr":
             arr[i].fn = AGG_FNS[fn]
             arr[i].col = len(exprs)
-            exprs.append(list(a[1]))
+            exprs.append([tuple(f[:2]) + (_mapped_col(f[2], binds),) + tuple(f[3:]) if len(f) > 2 else f
+                          for f in a[1]])
             continue
         if isinstance(fn, str):
             fn = AGG_FNS["count_star" if fn == "count" and len(a) == 1 else fn]
         arr[i].fn = fn
-        arr[i].col = a[1] if len(a) > 1 else 0
-        arr[i].col2 = a[2] if len(a) > 2 else 0
+        arr[i].col = _mapped_col(a[1], binds) if len(a) > 1 else 0
+        arr[i].col2 = _mapped_col(a[2], binds) if len(a) > 2 else 0
     return arr, exprs, conds
 
 
@@ -1080,6 +1131,7 @@ class Table:
     def __init__(self, h, conn):
         self.h, self.conn, self._keep = h, conn, None
         self._alts_set = False   # alternatives are set on the table (set_filter_alternatives)
+        self._vbind_signed = []  # per value binding set: its map's values are signed (set_aggregate_value_bindings)
 
     def close(self):
         if self.h:
@@ -1277,6 +1329,9 @@ class Table:
             if isinstance(val, Mapped):
                 if p.op > GE:
                     raise TypeError(f"filter term {i}: operator {op!r} takes no mapped value on its right")
+                if val.keep_unmatched:
+                    raise ValueError(f"filter term {i}: keep_unmatched=True means nothing in a filter term (a NULL "
+                                     "satisfies no operator there already)")
                 p.op += MAP_EQ
                 val = (val.key_col, val.valuemap)
             if MAP_EQ <= p.op <= MAP_GE:
@@ -1504,6 +1559,29 @@ class Table:
             arr[i].flags = b[2] if len(b) > 2 else 0
         _check(_lib.fls_aggregate_key_bindings(self.h, arr if bindings else None, len(bindings)))
 
+    def set_aggregate_value_bindings(self, bindings):
+        """fls_aggregate_value_bindings: what COL_MAPPED | i names in the
+        following aggregate calls (an operand, a sum_expr factor, a key of
+        aggregate_hashed); each binding a Mapped, or (col, valuemap) /
+        (col, valuemap, flags) with valuemap a ValueMap or a raw handle.  [] or
+        None clears.  What a Mapped in a call's aggs or keys sets and clears
+        per call."""
+        bindings = bindings or []
+        arr = (ValueBinding * max(1, len(bindings)))()
+        for i, b in enumerate(bindings[:len(arr)]):
+            if isinstance(b, Mapped):
+                b = (b.key_col, b.valuemap, VALUEMAP_KEEP_UNMATCHED if b.keep_unmatched else 0)
+            arr[i].col = b[0]
+            arr[i].map = (b[1].h or 0) if isinstance(b[1], ValueMap) else int(b[1])
+            arr[i].flags = b[2] if len(b) > 2 else 0
+        _check(_lib.fls_aggregate_value_bindings(self.h, arr if bindings else None, len(bindings)))
+        # how each binding's values extend, for a raw COL_MAPPED | i key of aggregate_hashed (the handles are live here)
+        self._vbind_signed = []
+        for i in range(len(bindings)):
+            info = ValueMapInfo()
+            _check(_lib.fls_valuemap_info(arr[i].map, C.byref(info)))
+            self._vbind_signed.append(info.value_kind == KIND_SIGNED)
+
     # -- aggregates reduced on the GPU
     def set_aggregate_exprs(self, exprs):
         """fls_aggregate_exprs: the expression list function code 6 (sum_expr)
@@ -1529,9 +1607,12 @@ class Table:
         items replace that list for the call and clear it afterwards."""
         if rg_end is None:
             rg_end = self.nrowgroups
-        arr, exprs, conds = _agg_specs(aggs)
+        vbinds = []
+        arr, exprs, conds = _agg_specs(aggs, vbinds)
         out = (AggregateValue * max(1, len(aggs)))()
         try:
+            if vbinds:   # (before the expressions, whose factors name them)
+                self.set_aggregate_value_bindings(vbinds)
             if exprs:
                 self.set_aggregate_exprs(exprs)
             if conds:
@@ -1542,6 +1623,8 @@ class Table:
                 self.set_aggregate_exprs(None)
             if conds:
                 self.set_aggregate_conditions(None)
+            if vbinds:
+                self.set_aggregate_value_bindings(None)
         return list(out)[:len(aggs)]
 
     def aggregate(self, aggs, filt=None, rg_begin=0, rg_end=None) -> list:
@@ -1580,6 +1663,9 @@ class Table:
             rg_end = self.nrowgroups
         raw, binds = [], []
         for k in keys:
+            if isinstance(k, Mapped):
+                raise ValueError(f"aggregate_grouped: key {k!r}: a Mapped is a key of aggregate_hashed; a "
+                                 'low-cardinality mapped key here is ("map", col, keymap) over a KeyMap')
             if isinstance(k, (tuple, list)):
                 if len(k) not in (3, 4) or k[0] != "map" or (len(k) == 4 and k[3] != "keep_unmatched"):
                     raise ValueError(f"aggregate_grouped: key {k!r} is not a column or "
@@ -1589,10 +1675,13 @@ class Table:
             else:
                 raw.append(k)
         karr = (C.c_uint32 * max(1, len(raw)))(*raw[:max(1, len(raw))])
-        arr, exprs, conds = _agg_specs(aggs)
+        vbinds = []
+        arr, exprs, conds = _agg_specs(aggs, vbinds)
         res = _P()
         self.set_filter(filt)
         try:
+            if vbinds:   # (before the expressions, whose factors name them)
+                self.set_aggregate_value_bindings(vbinds)
             if exprs:
                 self.set_aggregate_exprs(exprs)
             if conds:
@@ -1609,6 +1698,8 @@ class Table:
                 self.set_aggregate_conditions(None)
             if binds:
                 self.set_key_bindings(None)
+            if vbinds:
+                self.set_aggregate_value_bindings(None)
         try:
             out = []
             k = GroupKey()
@@ -1685,18 +1776,23 @@ class Table:
         all three None the plain call is made."""
         if rg_end is None:
             rg_end = self.nrowgroups
-        karr = (C.c_uint32 * max(1, len(keys)))(*keys[:max(1, len(keys))])
-        arr, exprs, conds = _agg_specs(aggs)
+        vbinds = []
+        raw = [_mapped_col(k, vbinds) for k in keys]   # a Mapped key: COL_MAPPED | its value binding
+        karr = (C.c_uint32 * max(1, len(raw)))(*raw[:max(1, len(raw))])
+        arr, exprs, conds = _agg_specs(aggs, vbinds)
         res = _P()
         select = having is not None or order_by is not None or limit is not None
         if select:
             sel, terms = self._group_select(having, order_by, limit)
         self.set_filter(filt)
         try:
+            if vbinds:   # (before the expressions, whose factors name them)
+                self.set_aggregate_value_bindings(vbinds)
             if exprs:
                 self.set_aggregate_exprs(exprs)
             if conds:
                 self.set_aggregate_conditions(conds)
+            vsigned = list(self._vbind_signed)   # (of the bindings in force for this call)
             if select:
                 _check(_lib.fls_aggregate_hashed_select(self.h, karr, len(keys), arr, len(aggs), max_groups,
                                                         C.byref(sel), rg_begin, rg_end, C.byref(res)))
@@ -1709,8 +1805,12 @@ class Table:
                 self.set_aggregate_exprs(None)
             if conds:
                 self.set_aggregate_conditions(None)
+            if vbinds:
+                self.set_aggregate_value_bindings(None)
         try:
-            signed = [self.column(k).type in (INT8, INT16, INT32, INT64, DATE, DECIMAL) for k in keys]
+            # (a mapped key extends by its map's value kind: a raw COL_MAPPED | i key by what the setter recorded)
+            signed = [vsigned[r & ~COL_MAPPED] if r & COL_MAPPED else
+                      self.column(r).type in (INT8, INT16, INT32, INT64, DATE, DECIMAL) for r in raw]
             return HashGroups(res, signed, len(aggs), in_result_order=order_by is not None or bool(limit))
         finally:
             _lib.fls_hash_result_free(res)

@@ -386,6 +386,13 @@ struct Slot {                       // one batch of row groups in flight
     DevBuf<DevMapTerm> d_mdesc;
     DevBuf<uint16_t> d_kcode;       // per binding 1024 codes per vector: the derived key columns
     DevBuf<uint64_t> d_kvalid;      // per binding 16 words per vector: a keep-unmatched key's validity
+    // mapped columns of an aggregate batch (fls_aggregate_value_bindings): per
+    // used binding (mapped_slot) a derived column and its validity, both
+    // defined at selected rows only (fls_mapval.hip)
+    PinBuf<DevMapValTerm> h_mvdesc;
+    DevBuf<DevMapValTerm> d_mvdesc;
+    DevBuf<uint64_t> d_mval;        // per used binding 1024 values per vector
+    DevBuf<uint64_t> d_mvalid;      // per used binding 16 words per vector
     // top-N batches (fls_topn)
     PinBuf<uint32_t> h_tdesc;       // per row group its first vector and vector count
     DevBuf<uint32_t> d_tdesc;
@@ -581,6 +588,23 @@ struct HostBinding {
     std::shared_ptr<KeyMap> map;
 };
 
+// One mapped column (fls_aggregate_value_bindings), host side: the value the
+// map gives column col.  FLS_COL_MAPPED | i names binding i of the table's
+// list wherever an aggregate takes a column and as a hash aggregate's key; a
+// scan carries the whole list (ScanCtx::vbinds, same numbering) and the bits of
+// the bindings its call names (ScanCtx::vused): only those are probed, narrow
+// the mask or prune.
+struct HostValueBinding {
+    uint32_t col = 0;
+    bool keep = false;              // FLS_VALUEMAP_KEEP_UNMATCHED
+    std::shared_ptr<ValueMap> map;
+};
+constexpr uint32_t kMaxValueBindings = 4;
+inline bool is_mapped_col(uint32_t c) { return (c & FLS_COL_MAPPED) != 0; }
+inline uint32_t mapped_index(uint32_t c) { return c & ~FLS_COL_MAPPED; }
+// binding i's place among the used ones: which derived column of the slot is its own
+inline uint32_t mapped_slot(uint32_t vused, uint32_t i) { return (uint32_t)__builtin_popcount(vused & ((1u << i) - 1)); }
+
 // One term of a pushed-down filter (fls_scan_filter), host side.
 struct HostTerm {
     uint32_t col = 0, clause = 0;
@@ -671,7 +695,12 @@ struct ScanPlan {
     // FLS_KEY_MAPPED | i for binding i of binds
     const std::vector<uint32_t> *keys = nullptr;
     const std::vector<HostBinding> *binds = nullptr;  // the mapped keys' bindings (NULL: none)
-    // Reduce::HashAggregate (max_groups != 0): keys are plain columns, hash their layout and tables
+    // the mapped columns' bindings (NULL: none), FLS_COL_MAPPED | i in an
+    // aggregate's columns or a hash key numbering them, and the bits of those
+    // the call names (used_value_bindings)
+    const std::vector<HostValueBinding> *vbinds = nullptr;
+    uint32_t vused = 0;
+    // Reduce::HashAggregate (max_groups != 0): keys are plain columns or mapped ones, hash their layout and tables
     uint64_t max_groups = 0;
     const HashPlan *hash = nullptr;
     const fls_order_key *order = nullptr;           // Reduce::TopN: the key and
@@ -706,11 +735,19 @@ struct ScanCtx {
     // ... where FLS_KEY_MAPPED | i stands for the code binding i gives its
     // column (keymap_kernel).  With a binding the scan always has a mask.
     std::vector<HostBinding> binds;
+    // mapped columns (FLS_COL_MAPPED | i in aggs or keys): the table's value
+    // bindings and the bits of those this scan probes (mapval_kernel).  With
+    // one used the scan always has a mask; the key columns of the used ones
+    // are decoded and their validity staged, as for binds.
+    std::vector<HostValueBinding> vbinds;
+    uint32_t vused = 0;
     // key-set build (Reduce::KeySet): nothing is delivered, the batches' keys
     // meet in the plan's bitmaps; their per-vector counts ride in the HostBatch.
     // Such a scan always has a mask, as one with a binding has.
     KeyBuildPlan keybuild;
-    bool masked() const { return !terms.empty() || !alts.empty() || !binds.empty() || reduce == Reduce::KeySet; }
+    bool masked() const {
+        return !terms.empty() || !alts.empty() || !binds.empty() || vused != 0 || reduce == Reduce::KeySet;
+    }
     // hash aggregate scan (Reduce::HashAggregate): the key layout and the
     // pipelines' tables, and the groups one table may hold
     HashPlan hash;
@@ -867,6 +904,7 @@ struct fls_table {
     std::vector<fls_agg_expr> exprs;  // fls_aggregate_exprs: what FLS_AGG_SUM_EXPR's spec.col indexes
     std::vector<std::vector<fls::engine::HostTerm>> conds;  // fls_aggregate_conditions: what spec.cond - 1 indexes
     std::vector<fls::engine::HostBinding> bindings;  // fls_aggregate_key_bindings: what FLS_KEY_MAPPED | i names
+    std::vector<fls::engine::HostValueBinding> vbindings;  // fls_aggregate_value_bindings: what FLS_COL_MAPPED | i names
     bool dict_codes = false;        // fls_scan_dict_codes: applies to the next fls_scan_begin
     bool narrow = false;            // fls_scan_narrow: applies to the next fls_scan_begin
     bool defer_records = false;     // fls_scan_defer_records: applies to the next fls_scan_begin
@@ -958,6 +996,36 @@ bool binding_may_match(const fls_table *t, uint32_t rg, const HostBinding &b);
 // The batch's probe of the scan's bindings, after the filter's kernels on the
 // slot's mask: the derived key columns into sl.d_kcode / sl.d_kvalid.
 int enqueue_keymap(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows);
+
+// ---- mapped columns (fls_scan_valuemap.hip) --------------------------------------
+
+// The bits of the table's value bindings that aggregates ha and (hash
+// aggregate) keys name; every FLS_COL_MAPPED | i in them has a binding i
+// (check_aggregates and hash_check refused the others).
+uint32_t used_value_bindings(const std::vector<HostAgg> &ha, const std::vector<uint32_t> *keys);
+// May a row of row group rg carry a key of inner value binding b?  (binding_may_match)
+bool value_binding_may_match(const fls_table *t, uint32_t rg, const HostValueBinding &b);
+// Drops from rgs the row groups an inner binding among the used ones rules
+// out; how many went.
+uint32_t prune_value_bindings(const fls_table *t, const std::vector<HostValueBinding> &vb, uint32_t vused,
+                              std::vector<uint32_t> &rgs);
+// Operand or key `c` of an aggregate call, a column or FLS_COL_MAPPED | i: is
+// it FLOAT / DOUBLE (a mapped column never is), and do its values sign-extend?
+bool operand_is_float(const fls_table *t, uint32_t c);
+bool operand_is_signed(const fls_table *t, uint32_t c);
+// Where the kernels read operand or key `c` of the slot's batch: the decoded
+// column, its bytes per value, FK_* kind and staged validity (NULL: none), or
+// for FLS_COL_MAPPED | i the derived column enqueue_mapval filled (8 bytes;
+// validity: NULL for an inner binding, whose misses left the mask).
+struct OperandRef {
+    const uint8_t *col = nullptr;
+    const uint64_t *valid = nullptr;
+    uint8_t ob = 0, kind = 0;
+};
+OperandRef operand_ref(const fls_table *t, const ScanCtx &s, const Slot &sl, uint32_t c);
+// The batch's gather of the scan's used value bindings, where enqueue_keymap
+// runs: the derived columns into sl.d_mval / sl.d_mvalid.
+int enqueue_mapval(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows);
 
 // A reducing scan on the table's scan context under its filter: nothing is
 // delivered; fold(rg, hb) sees every surviving row group once, in scan order,

@@ -256,6 +256,41 @@ enum : uint32_t { KERR_MAPCMP = 65536 };
 hipError_t launch_mapcmp(const DevMapCmpTerm *d_terms, uint32_t nterms, uint32_t nrows, uint64_t *d_mask,
                          uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
 
+// One mapped column (fls_aggregate_value_bindings: map[key column] as an
+// aggregate operand or a hash GROUP BY key) as mapval_kernel sees it, rebuilt
+// per scan batch; the map's image (fls_valuemap.hpp) lives in HBM with the map.
+// The kernel writes the map's value at every selected row whose key is valid
+// and in the map into `out`, one uint64 per batch row, and the ballot of those
+// rows into `ovalid`; the reduce kernels then read (out, 8 bytes, ovalid) as
+// they read any column.  Both are DEFINED AT SELECTED ROWS ONLY: a 64-row word
+// no row of which is selected is neither probed nor written.
+struct DevMapValTerm {        // 80 B
+    const uint8_t *key;       // the decoded key column of the batch in HBM (row 0 of the batch)
+    const uint64_t *vk;       // as DevTerm::valid, of the key column
+    const uint64_t *table;    // dense: values then presence words; hash: slots then values
+    uint64_t *out;            // the derived column: one value per batch row (HBM)
+    uint64_t *ovalid;         // the derived column's validity words, 16 per vector
+    uint64_t min, span;       // dense: value (key - min) for key - min <= span
+    uint64_t empty;           // hash: the empty slot's sentinel
+    uint32_t cap_log2;        // hash: log2 of the capacity
+    uint32_t max_probe;       // hash: slots a lookup examines at most
+    uint8_t form;             // VM_DENSE / VM_HASH
+    uint8_t obk;              // bytes per decoded key: 1, 2, 4 or 8
+    uint8_t ksign;            // keys sign-extend to 64 bits
+    uint8_t keep;             // keep-unmatched (left join): the mask is left alone
+    uint8_t pad[4];
+};
+static_assert(sizeof(DevMapValTerm) == 80 && sizeof(DevMapValTerm) % 16 == 0, "DevMapValTerm is 80 B");
+// a mapped-column descriptor no sound map produces (an unknown form, a key
+// width outside {1, 2, 4, 8}, a dense span or a capacity past the format's
+// limits, max_probe above the capacity)
+enum : uint32_t { KERR_MAPVAL = 131072 };
+// Probes the bindings' maps under the mask the filter's kernels wrote for the
+// same nrows rows, writes the derived columns, narrows the mask by the inner
+// bindings and recomputes the counts (fls_mapval.hip).
+hipError_t launch_mapval(const DevMapValTerm *d_terms, uint32_t nterms, uint32_t nrows, uint64_t *d_mask,
+                         uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
+
 // One pattern term (OP_LIKE / OP_NOT_LIKE) as strmatch_kernel sees it, rebuilt
 // per scan batch; the tokens (fls_strmatch.hpp) follow the descriptors in one
 // buffer.  A row stays selected when its string is valid and matches (negate:

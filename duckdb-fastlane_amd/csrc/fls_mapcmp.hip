@@ -27,43 +27,6 @@
 namespace fls {
 namespace {
 
-// the value at p, sign- or zero-extended to 64 bits (keyset_kernel's load_key)
-__device__ __forceinline__ uint64_t load_value(const uint8_t *p, uint32_t ob, bool sign) {
-    switch (ob) {
-    case 1: return sign ? (uint64_t)(int64_t) * (const int8_t *)p : (uint64_t)*p;
-    case 2: return sign ? (uint64_t)(int64_t) * (const int16_t *)p : (uint64_t) * (const uint16_t *)p;
-    case 4: return sign ? (uint64_t)(int64_t) * (const int32_t *)p : (uint64_t) * (const uint32_t *)p;
-    default: return *(const uint64_t *)p;
-    }
-}
-
-__device__ __forceinline__ bool width_ok(uint32_t ob) { return ob == 1 || ob == 2 || ob == 4 || ob == 8; }
-
-// is key in the map, and its value (valuemap_lookup, fls_valuemap.hpp)
-__device__ __forceinline__ bool probe(const DevMapCmpTerm &t, uint64_t key, uint64_t &value) {
-    if (t.form == VM_DENSE) {
-        const uint64_t d = key - t.min;
-        if (d > t.span) return false;
-        // two independent loads: the presence word and the value (0 in a hole)
-        const uint64_t present = t.table[t.span + 1 + (d >> 6)];
-        value = t.table[d];
-        return (present >> (d & 63)) & 1;
-    }
-    if (key == t.empty) return false;  // the sentinel is no key
-    const uint64_t cap_mask = (1ull << t.cap_log2) - 1;
-    const uint64_t h = t.cap_log2 ? (key * kKeysetHashMul) >> (64 - t.cap_log2) : 0;
-    for (uint32_t p = 0; p < t.max_probe; ++p) {
-        const uint64_t i = (h + p) & cap_mask;
-        const uint64_t slot = t.table[i];
-        if (slot == key) {
-            value = t.table[cap_mask + 1 + i];
-            return true;
-        }
-        if (slot == t.empty) return false;
-    }
-    return false;
-}
-
 __global__ __launch_bounds__(256) void mapcmp_kernel(const DevMapCmpTerm *__restrict__ terms, uint32_t nterms,
                                                      uint32_t nrows, uint64_t *__restrict__ mask,
                                                      uint32_t *__restrict__ counts, uint32_t *__restrict__ err) {
@@ -85,7 +48,7 @@ __global__ __launch_bounds__(256) void mapcmp_kernel(const DevMapCmpTerm *__rest
         const DevMapCmpTerm t = terms[i];
         // a descriptor no sound map produces selects nothing and is reported
         // (a dense image holds span + 1 <= 2^28 values, a hash image at most 2^29 slots)
-        if ((t.form != VM_DENSE && t.form != VM_HASH) || !width_ok(t.oba) || !width_ok(t.obk) || t.op > OP_GE ||
+        if ((t.form != VM_DENSE && t.form != VM_HASH) || !valuemap_width_ok(t.oba) || !valuemap_width_ok(t.obk) || t.op > OP_GE ||
             (t.form == VM_DENSE && t.span >= kValuemapMaxSpan) ||
             (t.form == VM_HASH && (t.cap_log2 > 29 || t.max_probe > (1ull << t.cap_log2)))) {
             bad = true;
@@ -102,8 +65,8 @@ __global__ __launch_bounds__(256) void mapcmp_kernel(const DevMapCmpTerm *__rest
             a[k] = key[k] = 0;
             if ((live[k] >> lane) & 1) {  // a NULL row's placeholder is never loaded
                 const uint64_t row = (uint64_t)v * 1024 + 64 * word + lane;
-                key[k] = load_value(t.key + row * t.obk, t.obk, t.ksign != 0);
-                a[k] = load_value(t.a + row * t.oba, t.oba, t.vsign != 0);
+                key[k] = valuemap_load(t.key + row * t.obk, t.obk, t.ksign != 0);
+                a[k] = valuemap_load(t.a + row * t.oba, t.oba, t.vsign != 0);
             }
         }
 #pragma unroll
@@ -112,7 +75,7 @@ __global__ __launch_bounds__(256) void mapcmp_kernel(const DevMapCmpTerm *__rest
             bool hit = false;
             if ((live[k] >> lane) & 1) {
                 uint64_t b = 0;
-                if (probe(t, key[k], b)) {
+                if (valuemap_probe(t, key[k], b)) {  // (fls_valuemap.hpp)
                     const int c = t.vsign ? cmp_int((int64_t)a[k], (int64_t)b) : cmp_uint(a[k], b);
                     hit = op_holds(t.op, c);
                 }

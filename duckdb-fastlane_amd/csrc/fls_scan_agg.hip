@@ -15,7 +15,6 @@ FLS_ENGINE_BEGIN
 // The aggregates of a batch as the kernels see them (sl.h_adesc -> sl.d_adesc
 // on the slot's stream), over the slot's decoded columns and staged validity.
 int upload_agg_descs(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl) {
-    const std::vector<uint8_t> &need = sl.valid_staged;
     const uint32_t na = (uint32_t)s.aggs.size();
     HIP_TRY(sl.h_adesc.alloc(na));
     HIP_TRY(sl.d_adesc.alloc(d.dev, na));
@@ -31,27 +30,30 @@ int upload_agg_descs(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl) {
         if (a.fn == AGG_SUM_EXPR) {
             da.nf = (uint8_t)a.nf;
             for (uint32_t k = 0; k < a.nf; ++k) {
-                const uint32_t c = a.fcol[k];
-                da.f[k].col = sl.d_out[c].p;
-                da.f[k].valid = need[c] ? sl.d_valid[c].p : nullptr;
+                // (a column, or FLS_COL_MAPPED | i: the derived column mapval_kernel wrote)
+                const OperandRef o = operand_ref(t, s, sl, a.fcol[k]);
+                da.f[k].col = o.col;
+                da.f[k].valid = o.valid;
                 da.f[k].k = a.fk[k];
-                da.fob[k] = (uint8_t)out_bytes_of(t, c);
-                da.fkind[k] = col_kind(t, c);
+                da.fob[k] = o.ob;
+                da.fkind[k] = o.kind;
                 da.fneg[k] = a.fneg[k];
             }
             continue;
         }
-        da.valid = need[a.col] ? sl.d_valid[a.col].p : nullptr;
+        const OperandRef o = operand_ref(t, s, sl, a.col);
+        da.valid = o.valid;
         if (a.fn == AGG_COUNT) continue;
-        da.col = sl.d_out[a.col].p;
-        da.ob = (uint8_t)out_bytes_of(t, a.col);
-        da.kind = col_kind(t, a.col);
+        da.col = o.col;
+        da.ob = o.ob;
+        da.kind = o.kind;
         if (a.fn == AGG_SUM && da.kind == FK_FLOAT) da.fslot = nfsum++;
         if (a.fn != AGG_SUM_PRODUCT) continue;
-        da.col2 = sl.d_out[a.col2].p;
-        da.ob2 = (uint8_t)out_bytes_of(t, a.col2);
-        da.kind2 = col_kind(t, a.col2);
-        da.valid2 = need[a.col2] ? sl.d_valid[a.col2].p : nullptr;
+        const OperandRef o2 = operand_ref(t, s, sl, a.col2);
+        da.col2 = o2.col;
+        da.ob2 = o2.ob;
+        da.kind2 = o2.kind;
+        da.valid2 = o2.valid;
     }
     HIP_TRY(hipMemcpyAsync(sl.d_adesc.p, sl.h_adesc.p, na * sizeof(DevAgg), hipMemcpyHostToDevice, sl.stream));
     return 0;
@@ -170,6 +172,13 @@ namespace {
 // Largest magnitude of column c's non-NULL values in row group rg: from the
 // zone map, else the type's range.
 uint64_t max_magnitude(const fls_table *t, uint32_t rg, uint32_t c) {
+    if (is_mapped_col(c)) {  // a mapped operand: max(|value_min|, |value_max|) of its map, 0 for the empty one
+        const ValuemapImage &vi = t->vbindings[mapped_index(c)].map->img;
+        if (vi.set.keys.empty()) return 0;
+        if (!vi.value_signed) return vi.vmax;
+        auto mag = [](uint64_t v) { return (int64_t)v < 0 ? 0 - v : v; };
+        return std::max(mag(vi.vmin), mag(vi.vmax));
+    }
     const uint8_t ty = t->meta.cols[c].type;
     const bool sign = type_is_signed(ty);
     const auto &zs = t->meta.rgs[rg].zones;
@@ -193,6 +202,20 @@ double dbl_up(uint64_t v) { return v == 0 ? 0.0 : std::nextafter((double)v, HUGE
 // the zone-map range (else the type's range), exact in 128 bits, then rounded
 // upwards.  0 for an all-NULL chunk: no row of it contributes.
 double max_factor(const fls_table *t, uint32_t rg, uint32_t c, bool neg, int64_t k) {
+    auto bound = [&](__int128 lo, __int128 hi) {
+        auto mag = [&](__int128 x) {
+            const __int128 v = (__int128)k + (neg ? -x : x);
+            return (unsigned __int128)(v < 0 ? -v : v);
+        };
+        const unsigned __int128 m = std::max(mag(lo), mag(hi));  // < 2^65
+        return m == 0 ? 0.0 : std::nextafter((double)m, HUGE_VAL);
+    };
+    if (is_mapped_col(c)) {  // a mapped factor: the ends of its map's [value_min, value_max]; no value in an empty map
+        const ValuemapImage &vi = t->vbindings[mapped_index(c)].map->img;
+        if (vi.set.keys.empty()) return 0.0;
+        if (vi.value_signed) return bound((int64_t)vi.vmin, (int64_t)vi.vmax);
+        return bound(vi.vmin, vi.vmax);
+    }
     const uint8_t ty = t->meta.cols[c].type;
     const bool sign = type_is_signed(ty);
     const auto &zs = t->meta.rgs[rg].zones;
@@ -209,12 +232,7 @@ double max_factor(const fls_table *t, uint32_t rg, uint32_t c, bool neg, int64_t
         lo = zs[c].min;
         hi = zs[c].max;
     }
-    auto mag = [&](__int128 x) {
-        const __int128 v = (__int128)k + (neg ? -x : x);
-        return (unsigned __int128)(v < 0 ? -v : v);
-    };
-    const unsigned __int128 m = std::max(mag(lo), mag(hi));  // < 2^65
-    return m == 0 ? 0.0 : std::nextafter((double)m, HUGE_VAL);
+    return bound(lo, hi);
 }
 
 }  // namespace
@@ -246,22 +264,42 @@ int check_aggregates(const fls_table *t, const char *who, const fls_aggregate_sp
             const fls_agg_expr &e = t->exprs[a.col];
             ha[i].nf = e.nfactors;
             for (uint32_t k = 0; k < e.nfactors; ++k) {
+                // (the bindings may have been replaced since fls_aggregate_exprs checked the factor)
+                if (is_mapped_col(e.f[k].col) && mapped_index(e.f[k].col) >= t->vbindings.size())
+                    return fail(FLS_ERR_ARG, "aggregate %u: expression %u names value binding %u (%u set by "
+                                "fls_aggregate_value_bindings)", i, a.col, mapped_index(e.f[k].col),
+                                (uint32_t)t->vbindings.size());
                 ha[i].fcol[k] = e.f[k].col;
                 ha[i].fneg[k] = e.f[k].sign < 0;
                 ha[i].fk[k] = e.f[k].k;
             }
             continue;
         }
-        if (a.col >= ncols) return fail(FLS_ERR_ARG, "aggregate %u: column %u out of range", i, a.col);
+        // an operand: a column, or FLS_COL_MAPPED | b for value binding b, a 64-bit integer column
+        auto mapped_ok = [&](uint32_t c) {
+            return mapped_index(c) < t->vbindings.size()
+                       ? 0
+                       : fail(FLS_ERR_ARG, "aggregate %u: no value binding %u (%u set by fls_aggregate_value_bindings)", i,
+                              mapped_index(c), (uint32_t)t->vbindings.size());
+        };
+        if (is_mapped_col(a.col)) {
+            if (int rc = mapped_ok(a.col)) return rc;
+        } else if (a.col >= ncols) {
+            return fail(FLS_ERR_ARG, "aggregate %u: column %u out of range", i, a.col);
+        }
         ha[i].col = a.col;
         if (a.fn == FLS_AGG_COUNT) continue;
-        const uint8_t ty = t->meta.cols[a.col].type;
+        const uint8_t ty = is_mapped_col(a.col) ? (uint8_t)TY_INT64 : t->meta.cols[a.col].type;
         if (type_is_string(ty))
             return fail(FLS_ERR_ARG, "aggregate %u: SUM / MIN / MAX of string column %u is not supported", i, a.col);
         if (a.fn != FLS_AGG_SUM_PRODUCT) continue;
-        if (a.col2 >= ncols) return fail(FLS_ERR_ARG, "aggregate %u: column %u out of range", i, a.col2);
+        if (is_mapped_col(a.col2)) {
+            if (int rc = mapped_ok(a.col2)) return rc;
+        } else if (a.col2 >= ncols) {
+            return fail(FLS_ERR_ARG, "aggregate %u: column %u out of range", i, a.col2);
+        }
         ha[i].col2 = a.col2;
-        const uint8_t ty2 = t->meta.cols[a.col2].type;
+        const uint8_t ty2 = is_mapped_col(a.col2) ? (uint8_t)TY_INT64 : t->meta.cols[a.col2].type;
         if (type_is_string(ty2))
             return fail(FLS_ERR_ARG, "aggregate %u: SUM_PRODUCT of string column %u is not supported", i, a.col2);
         if (type_is_float(ty) || type_is_float(ty2))
@@ -315,7 +353,7 @@ void used_conditions(const fls_table *t, std::vector<HostAgg> &ha, std::vector<s
 }
 
 bool agg_is_float(const fls_table *t, const HostAgg &h) {
-    return h.fn >= AGG_SUM && h.fn != AGG_SUM_EXPR && type_is_float(t->meta.cols[h.col].type);
+    return h.fn >= AGG_SUM && h.fn != AGG_SUM_EXPR && operand_is_float(t, h.col);
 }
 
 FLS_ENGINE_END
@@ -378,7 +416,7 @@ void finish_value(const fls_table *t, const HostAgg &h, const AggAcc &a, fls_agg
     } else if (flt) {
         const double d = agg_unkey_float(a.key);
         memcpy(&o.lo, &d, 8);
-    } else if (type_is_signed(t->meta.cols[h.col].type)) {
+    } else if (operand_is_signed(t, h.col)) {  // (a mapped operand: by its map's value kind)
         const int64_t v = agg_unkey_int(a.key);
         o.lo = (uint64_t)v;
         o.hi = v < 0 ? ~0ull : 0ull;
@@ -415,6 +453,12 @@ int fls_aggregate_exprs(fls_table *t, const fls_agg_expr *exprs, uint32_t n) {
             const fls_agg_factor &f = e.f[k];
             if (f.sign != 1 && f.sign != -1)
                 return fail(FLS_ERR_ARG, "expression %u: factor %u has sign %d (+1 or -1)", i, k, (int)f.sign);
+            if (is_mapped_col(f.col)) {  // FLS_COL_MAPPED | b: a 64-bit integer column, k in the map's value unit
+                if (mapped_index(f.col) >= t->vbindings.size())
+                    return fail(FLS_ERR_ARG, "expression %u: no value binding %u (%u set by "
+                                "fls_aggregate_value_bindings)", i, mapped_index(f.col), (uint32_t)t->vbindings.size());
+                continue;
+            }
             if (f.col >= ncols) return fail(FLS_ERR_ARG, "expression %u: column %u out of range", i, f.col);
             const uint8_t ty = t->meta.cols[f.col].type;
             if (type_is_string(ty) || type_is_float(ty))
@@ -438,6 +482,8 @@ int fls_aggregate(fls_table *t, const fls_aggregate_spec *aggs, uint32_t n, uint
     plan.rg1 = rg_end;
     plan.aggs = &ha;
     plan.conds = &conds;
+    plan.vbinds = &t->vbindings;
+    plan.vused = used_value_bindings(ha, nullptr);
     // fold the per-vector records in row order
     std::vector<AggAcc> acc;
     for (uint32_t i = 0; i < n; ++i) acc.emplace_back(ha[i].fn);
@@ -478,6 +524,10 @@ int fls_aggregate_grouped(fls_table *t, const uint32_t *keys, uint32_t nkeys, co
             binds.push_back(t->bindings[i]);
             continue;
         }
+        if (is_mapped_col(c))
+            return fail(FLS_ERR_ARG, "key %u: a mapped column (FLS_COL_MAPPED) cannot be a grouped aggregate's key; a key "
+                        "map (FLS_KEY_MAPPED, fls_aggregate_key_bindings) gives a low-cardinality mapped key, "
+                        "fls_aggregate_hashed takes a mapped column", q);
         if (c >= ncols) return fail(FLS_ERR_ARG, "key %u: column %u out of range", q, c);
         for (uint32_t p = 0; p < q; ++p)
             if (keys[p] == c) return fail(FLS_ERR_ARG, "key %u: column %u is key %u already", q, c, p);
@@ -536,6 +586,8 @@ int fls_aggregate_grouped(fls_table *t, const uint32_t *keys, uint32_t nkeys, co
     plan.conds = &conds;
     plan.keys = &hk;
     plan.binds = &binds;
+    plan.vbinds = &t->vbindings;
+    plan.vused = used_value_bindings(ha, nullptr);
     auto res = std::make_unique<fls_group_result>();
     res->nkeys = nkeys;
     res->naggs = n;

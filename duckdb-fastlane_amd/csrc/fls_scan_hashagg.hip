@@ -51,6 +51,21 @@ int enqueue_hash_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint6
     DevHashKey *dk = (DevHashKey *)sl.h_hdesc.p;
     for (uint32_t q = 0; q < nk; ++q) {
         const uint32_t c = s.keys[q];
+        if (is_mapped_col(c)) {
+            // the derived column mapval_kernel wrote for the key's binding: never
+            // NULL (inner), or valid where the map had the value (keep-unmatched);
+            // its range is the map's [value_min, value_max]
+            const OperandRef o = operand_ref(t, s, sl, c);
+            dk[q].col = o.col;
+            dk[q].valid = o.valid;
+            dk[q].min = H.min[q];
+            dk[q].span = H.span[q];
+            dk[q].ob = o.ob;
+            dk[q].sign = o.kind == FK_INT ? 1 : 0;
+            dk[q].shift = (uint8_t)H.shift[q];
+            dk[q].null_bit = (uint8_t)H.null_bit[q];
+            continue;
+        }
         dk[q].col = sl.d_out[c].p;
         dk[q].valid = need[c] ? sl.d_valid[c].p : nullptr;
         dk[q].min = H.min[q];
@@ -106,6 +121,15 @@ int hash_key_layout(const fls_table *t, const std::vector<uint32_t> &keys, uint3
     const uint32_t nk = (uint32_t)keys.size();
     for (uint32_t q = 0; q < nk; ++q) {
         const uint32_t c = keys[q];
+        if (is_mapped_col(c)) {
+            // a mapped key: the map's [value_min, value_max] in its value kind's
+            // order instead of zone maps (the empty map: one value, 0 bits)
+            const ValuemapImage &vi = t->vbindings[mapped_index(c)].map->img;
+            H.min[q] = vi.vmin;
+            H.span[q] = vi.vmax - vi.vmin;
+            H.bits[q] = H.span[q] == 0 ? 0 : 64 - (uint32_t)__builtin_clzll(H.span[q]);
+            continue;
+        }
         const uint8_t ty = t->meta.cols[c].type;
         const bool sign = type_is_signed(ty);
         const int tb = type_value_bits(ty);
@@ -143,7 +167,8 @@ int hash_key_layout(const fls_table *t, const std::vector<uint32_t> &keys, uint3
         for (uint32_t q = 0, bits = nk; q < nk; ++q)
             if ((bits += H.bits[q]) > kHashKeyBits)
                 return fail(FLS_ERR_ARG, "key %u: the packed key needs %u bits (at most %u: per key the bits of max - min "
-                            "of its zone maps over the range, the type's width where a row group has none, and 1 for "
+                            "of its zone maps over the range, the type's width where a row group has none, of "
+                            "value_max - value_min of a mapped key's map, and 1 for "
                             "NULL); use fls_aggregate_grouped or fewer / narrower keys", q, H.total, kHashKeyBits);
     return 0;
 }
@@ -191,6 +216,15 @@ int hash_check(fls_table *t, const uint32_t *keys, uint32_t nkeys, const fls_agg
         if (c & FLS_KEY_MAPPED)
             return fail(FLS_ERR_ARG, "key %u: a mapped key (FLS_KEY_MAPPED) cannot be a hash aggregate's key; "
                         "fls_aggregate_grouped takes it", q);
+        if (is_mapped_col(c)) {  // FLS_COL_MAPPED | b: the value binding b's map gives its column
+            const uint32_t b = mapped_index(c);
+            if (b >= t->vbindings.size())
+                return fail(FLS_ERR_ARG, "key %u: no value binding %u (%u set by fls_aggregate_value_bindings)", q, b,
+                            (uint32_t)t->vbindings.size());
+            for (uint32_t p = 0; p < q; ++p)
+                if (keys[p] == c) return fail(FLS_ERR_ARG, "key %u: value binding %u is key %u already", q, b, p);
+            continue;
+        }
         if (c >= ncols) return fail(FLS_ERR_ARG, "key %u: column %u out of range", q, c);
         for (uint32_t p = 0; p < q; ++p)
             if (keys[p] == c) return fail(FLS_ERR_ARG, "key %u: column %u is key %u already", q, c, p);
@@ -254,6 +288,8 @@ int hash_scan(HashCall &c) {
     // one the scan below does no device work and no table is needed)
     std::vector<uint32_t> rgs;
     select_rowgroups(t, t->filter, t->alts, nullptr, 0, rg_begin, rg_end, rgs);
+    const uint32_t vused = used_value_bindings(c.ha, &c.hk);  // the mapped operands' and keys' bindings
+    prune_value_bindings(t, t->vbindings, vused, rgs);
     const size_t G = t->devices.size();
     tables = std::vector<DevBuf<uint64_t>>(rgs.empty() ? 0 : G);
     for (size_t g = 0; g < tables.size(); ++g) {
@@ -275,6 +311,8 @@ int hash_scan(HashCall &c) {
     plan.aggs = &c.ha;
     plan.conds = &c.conds;
     plan.keys = &c.hk;
+    plan.vbinds = &t->vbindings;
+    plan.vused = vused;
     plan.max_groups = max_groups;
     plan.hash = &H;
     ScanCtx &s = t->scan;
@@ -439,7 +477,7 @@ void hash_unpack(HashCall &c, const uint64_t *F, uint64_t mg) {
         const bool is_sum = fn == AGG_SUM || fn == AGG_SUM_PRODUCT || fn == AGG_SUM_EXPR;
         const uint64_t *hi = is_sum ? F + (uint64_t)H.fields[a].hi * mg : nullptr;
         const bool flt = agg_is_float(t, ha[a]);
-        const bool sign = !flt && !is_sum && type_is_signed(t->meta.cols[ha[a].col].type);
+        const bool sign = !flt && !is_sum && operand_is_signed(t, ha[a].col);  // (a mapped operand: by its map's value kind)
         for (uint64_t i = 0; i < mg; ++i) {
             if (A.count[i] == 0) {
                 A.kind[i] = FLS_AGGV_NULL;
@@ -534,7 +572,7 @@ int select_check(const HashCall &c, const fls_group_select *sel, DevGroupSelect 
             uint64_t key = 0;
             if (flt) {
                 key = agg_key_float(as_double(h.lo));
-            } else if (type_is_signed(t->meta.cols[a.col].type)) {
+            } else if (operand_is_signed(t, a.col)) {
                 if (h.hi != ((h.lo >> 63) ? ~0ull : 0ull)) d.mode = out_of_range_mode(h.op, neg ? -1 : 1);
                 key = agg_key_int((int64_t)h.lo);
             } else {

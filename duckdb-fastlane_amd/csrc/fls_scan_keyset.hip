@@ -107,6 +107,8 @@ int fls_keyset_from_scan(fls_table *t, uint32_t col, uint32_t rg_begin, uint32_t
     if (info) memset(info, 0, sizeof(*info));
     // the refusals, before any device work
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    if (is_mapped_col(col))
+        return fail(FLS_ERR_ARG, "fls_keyset_from_scan: a mapped column (FLS_COL_MAPPED) cannot be a key-set build's column");
     if (col >= ncols) return fail(FLS_ERR_ARG, "fls_keyset_from_scan: column %u out of range", col);
     const ColumnMeta &cm = t->meta.cols[col];
     const uint8_t ty = cm.type;

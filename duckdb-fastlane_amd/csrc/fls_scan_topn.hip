@@ -76,6 +76,8 @@ namespace {
 int check_topn(const fls_table *t, const fls_order_key *key, uint32_t k, const uint8_t *col_mask, uint32_t rg_begin,
                uint32_t rg_end) {
     const uint32_t ncols = (uint32_t)t->meta.cols.size();
+    if (is_mapped_col(key->col))
+        return fail(FLS_ERR_ARG, "order key: a mapped column (FLS_COL_MAPPED) cannot be a top-N key");
     if (key->col >= ncols) return fail(FLS_ERR_ARG, "order key: column %u out of range", key->col);
     const ColumnMeta &cm = t->meta.cols[key->col];
     if (type_is_string(cm.type))

@@ -8,8 +8,10 @@
 // Host only (no HIP include): a map is built, queried and used for pruning
 // without a GPU, and a stand-alone CPU program can drive this header
 // (tests/fuzz/fuzz_valuemap.cpp).  The image built here is the very byte
-// sequence the scan uploads; valuemap_lookup probes it the way mapcmp_kernel
-// does.
+// sequence the scan uploads; valuemap_lookup probes it the way the kernels do:
+// their one device probe, valuemap_probe, is at the end of this header (HIP
+// compilations only), shared by mapcmp_kernel and mapval_kernel
+// (fls_mapval.hip: map[key] as a derived column of the aggregate calls).
 //
 // Keys are 64-bit patterns as in key sets (fls_keyset.hpp), ordered by the key
 // kind; values are 64-bit patterns ordered by the value kind (`value_signed`),
@@ -174,5 +176,53 @@ inline int valuemap_build(const uint64_t *keys, const uint64_t *values, uint64_t
     }
     return VM_OK;
 }
+
+#ifdef __HIPCC__
+// What the two kernels that probe a value map share (mapcmp_kernel,
+// mapval_kernel): the load of a key or a left value, the widths a decoded
+// column may have, and the probe.
+
+// the value at p, sign- or zero-extended to 64 bits
+__device__ __forceinline__ uint64_t valuemap_load(const uint8_t *p, uint32_t ob, bool sign) {
+    switch (ob) {
+    case 1: return sign ? (uint64_t)(int64_t) * (const int8_t *)p : (uint64_t)*p;
+    case 2: return sign ? (uint64_t)(int64_t) * (const int16_t *)p : (uint64_t) * (const uint16_t *)p;
+    case 4: return sign ? (uint64_t)(int64_t) * (const int32_t *)p : (uint64_t) * (const uint32_t *)p;
+    default: return *(const uint64_t *)p;
+    }
+}
+
+__device__ __forceinline__ bool valuemap_width_ok(uint32_t ob) { return ob == 1 || ob == 2 || ob == 4 || ob == 8; }
+
+// Is key in the map, and its value (valuemap_lookup above), over any
+// descriptor that carries the image's fields: table, min, span, empty,
+// cap_log2, max_probe, form (DevMapCmpTerm, DevMapValTerm; fls_filter.hpp).
+// Dense: a range test, then two independent loads, the presence word and the
+// value (0 in a hole).  Hash: at most max_probe 8-byte gathers and one from
+// the value array at the matched slot.
+template <class Desc>
+__device__ __forceinline__ bool valuemap_probe(const Desc &t, uint64_t key, uint64_t &value) {
+    if (t.form == VM_DENSE) {
+        const uint64_t d = key - t.min;
+        if (d > t.span) return false;
+        const uint64_t present = t.table[t.span + 1 + (d >> 6)];
+        value = t.table[d];
+        return (present >> (d & 63)) & 1;
+    }
+    if (key == t.empty) return false;  // the sentinel is no key
+    const uint64_t cap_mask = (1ull << t.cap_log2) - 1;
+    const uint64_t h = t.cap_log2 ? (key * kKeysetHashMul) >> (64 - t.cap_log2) : 0;
+    for (uint32_t p = 0; p < t.max_probe; ++p) {
+        const uint64_t i = (h + p) & cap_mask;
+        const uint64_t slot = t.table[i];
+        if (slot == key) {
+            value = t.table[cap_mask + 1 + i];
+            return true;
+        }
+        if (slot == t.empty) return false;
+    }
+    return false;
+}
+#endif
 
 }  // namespace fls

@@ -822,6 +822,8 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     s.conds.clear();
     s.keys.clear();
     s.binds.clear();
+    s.vbinds.clear();
+    s.vused = 0;
     s.tk = 0;
     s.tkey = fls_order_key{};
     bool string_key = false;
@@ -847,7 +849,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
         if (p.binds) s.binds = *p.binds;
         for (const HostBinding &b : s.binds) s.dmask[b.col] = 1;  // a mapped key's column is decoded to be probed
         for (uint32_t c : s.keys) {
-            if (c & FLS_KEY_MAPPED) continue;
+            if ((c & FLS_KEY_MAPPED) || is_mapped_col(c)) continue;  // (a derived column: its binding's column is decoded)
             s.dmask[c] = 1;
             string_key = string_key || type_is_string(t->meta.cols[c].type);
         }
@@ -860,13 +862,22 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
         // groups the scan reads: a condition prunes nothing
         if (p.conds) s.conds = *p.conds;
         for (auto &q : s.conds) decode_columns_of(q);
+        // (a mapped operand, FLS_COL_MAPPED | i, is a derived column: the key
+        // column of its binding is decoded to be probed)
+        if (p.vbinds && p.vused) {
+            s.vbinds = *p.vbinds;
+            s.vused = p.vused;
+            for (uint32_t i = 0; i < s.vbinds.size(); ++i)
+                if ((s.vused >> i) & 1) s.dmask[s.vbinds[i].col] = 1;
+        }
         for (auto &a : s.aggs) {
             if (a.fn == AGG_SUM_EXPR) {
-                for (uint32_t i = 0; i < a.nf; ++i) s.dmask[a.fcol[i]] = 1;
+                for (uint32_t i = 0; i < a.nf; ++i)
+                    if (!is_mapped_col(a.fcol[i])) s.dmask[a.fcol[i]] = 1;
                 continue;
             }
-            if (a.fn >= AGG_SUM) s.dmask[a.col] = 1;
-            if (a.fn == AGG_SUM_PRODUCT) s.dmask[a.col2] = 1;
+            if (a.fn >= AGG_SUM && !is_mapped_col(a.col)) s.dmask[a.col] = 1;
+            if (a.fn == AGG_SUM_PRODUCT && !is_mapped_col(a.col2)) s.dmask[a.col2] = 1;
         }
         break;
     case Reduce::TopN:
@@ -888,6 +899,8 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
         s.pruned += (uint32_t)(s.rgs.size() - keep.size());
         s.rgs.swap(keep);
     }
+    // ... and so does an inner value binding the call names
+    s.pruned += prune_value_bindings(t, s.vbinds, s.vused, s.rgs);
     if (p.only) {  // a scan of listed row groups: fls_topn's late materialisation
         s.rgs = *p.only;
         s.pruned = 0;
@@ -994,17 +1007,21 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
                 need[h.col] = 1;
                 if (reads_col2(h.op)) need[h.col2] = 1;
             }
+    // (a mapped operand or key has its validity from mapval_kernel; its binding's key column is staged)
     for (auto &a : s.aggs) {
         if (a.fn == AGG_SUM_EXPR) {
-            for (uint32_t i = 0; i < a.nf; ++i) need[a.fcol[i]] = 1;
+            for (uint32_t i = 0; i < a.nf; ++i)
+                if (!is_mapped_col(a.fcol[i])) need[a.fcol[i]] = 1;
             continue;
         }
-        if (a.fn != AGG_COUNT_STAR) need[a.col] = 1;
-        if (a.fn == AGG_SUM_PRODUCT) need[a.col2] = 1;
+        if (a.fn != AGG_COUNT_STAR && !is_mapped_col(a.col)) need[a.col] = 1;
+        if (a.fn == AGG_SUM_PRODUCT && !is_mapped_col(a.col2)) need[a.col2] = 1;
     }
     for (uint32_t c : s.keys)
-        if (!(c & FLS_KEY_MAPPED)) need[c] = 1;
+        if (!(c & FLS_KEY_MAPPED) && !is_mapped_col(c)) need[c] = 1;
     for (const HostBinding &b : s.binds) need[b.col] = 1;
+    for (uint32_t i = 0; i < s.vbinds.size(); ++i)
+        if ((s.vused >> i) & 1) need[s.vbinds[i].col] = 1;
     if (s.reduce == Reduce::TopN) need[s.tkey.col] = 1;
     if (s.reduce == Reduce::KeySet) need[s.keybuild.col] = 1;
     for (uint32_t c = 0; c < ncols; ++c) {
@@ -1414,6 +1431,8 @@ static int enqueue_filter(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64
         if (int rc = enqueue_alternatives(t, s, d, sl, rows, in_lo, in_len)) return rc;
     if (!s.binds.empty())  // mapped GROUP BY keys: their codes, and the inner ones' narrowing of the mask
         if (int rc = enqueue_keymap(t, s, d, sl, rows)) return rc;
+    if (s.vused)  // mapped columns: their values and validity, and the inner ones' narrowing of the mask
+        if (int rc = enqueue_mapval(t, s, d, sl, rows)) return rc;
     if (s.reduce != Reduce::None) return 0;  // an aggregate / top-N scan reduces under the mask: nothing is compacted or delivered
     HIP_TRY(hb.h_counts.alloc(hb.nvec));
     HIP_TRY(hb.h_sel.alloc(std::max<uint64_t>(rows, 1)));
@@ -1577,7 +1596,7 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
                 if (reads_col2(h.op)) in_term[h.col2] = 1;
             }
     for (uint32_t c : s.keys)
-        if (!(c & FLS_KEY_MAPPED)) is_key[c] = 1;
+        if (!(c & FLS_KEY_MAPPED) && !is_mapped_col(c)) is_key[c] = 1;  // (a mapped key or column is derived, never a string)
     for (uint32_t c = 0; c < ncols; ++c) {
         hb.ob[c] = (uint8_t)out_bytes_of(t, c);
         const bool coded = is_key[c] || (s.dict_codes && col_selected(s.mask, c));
@@ -2014,6 +2033,8 @@ static int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
         if (err & KERR_MAPCMP)
             return fail(FLS_ERR_FORMAT, "filter: damaged map-comparison descriptor (flags 0x%x)", err);
         if (err & KERR_KEYMAP) return fail(FLS_ERR_FORMAT, "grouped aggregate: damaged key-map descriptor (flags 0x%x)", err);
+        if (err & KERR_MAPVAL)
+            return fail(FLS_ERR_FORMAT, "aggregate: damaged mapped-column descriptor (flags 0x%x)", err);
         if (err & KERR_KEYBUILD)
             return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a key-set build's key column "
                         "(flags 0x%x)", err);
@@ -2189,6 +2210,9 @@ static int to_terms(const fls_table *t, const fls_predicate *p, uint32_t n, std:
     if (n && !p) return fail(FLS_ERR_ARG, "fls_scan_filter: NULL predicates");
     for (uint32_t i = 0; i < n; ++i) {
         if (at) *at = i;
+        if (is_mapped_col(p[i].col))
+            return fail(FLS_ERR_ARG, "a mapped column (FLS_COL_MAPPED) cannot be a filter term's column; `col op "
+                        "map[key]` is a map term (FLS_CMP_MAP_EQ .. FLS_CMP_MAP_GE)");
         if (p[i].col >= t->meta.cols.size()) return fail(FLS_ERR_ARG, "filter column %u out of range", p[i].col);
         if (p[i].op > FLS_CMP_MAP_GE) return fail(FLS_ERR_ARG, "filter operator %u unknown", p[i].op);
         HostTerm h;

@@ -851,6 +851,60 @@ int fls_valuemap_lookup(const fls_valuemap *map, uint64_t key, uint64_t *value);
 #define FLS_KEYMAP_KEEP_UNMATCHED 1u   /* left join: unmatched rows form the NULL group */
 typedef struct fls_key_binding { uint32_t col; uint32_t flags; uint64_t map; /* the fls_keymap handle */ } fls_key_binding;
 int fls_aggregate_key_bindings(fls_table *t, const fls_key_binding *b, uint32_t n);
+
+/* Mapped columns: the join's payload itself.  fls_aggregate_value_bindings
+ * sets the table's value bindings (copied and replaced as a whole; n <= 4;
+ * n = 0 clears; sticky like fls_aggregate_key_bindings): binding i says "probe
+ * value map `map` with column col".  The mapped column map[col] is a 64-bit
+ * integer column, signed or unsigned by the map's value_kind, NULL at a row
+ * where col is NULL or its value is not in the map.  In the following calls
+ * FLS_COL_MAPPED | i names it
+ *   - as fls_aggregate_spec.col / .col2 of COUNT, SUM, MIN, MAX and
+ *     SUM_PRODUCT in fls_aggregate, fls_aggregate_grouped and
+ *     fls_aggregate_hashed[_select], with or without a condition (spec.cond),
+ *     and under HAVING / ORDER BY over such an aggregate: SUM is the exact
+ *     128-bit sum, MIN / MAX come back as FLS_AGGV_INT sign- or zero-extended
+ *     by value_kind, sum(l_quantity * cost[l_partkey]) is a SUM_PRODUCT;
+ *   - as fls_agg_factor.col of fls_aggregate_exprs (k in the map's value unit);
+ *   - as keys[q] of fls_aggregate_hashed[_select] (GROUP BY cust[l_orderkey]):
+ *     the key's range is the map's [value_min, value_max] instead of zone
+ *     maps, plus the NULL bit (an empty map: 0 value bits); fls_hash_result_key
+ *     returns the mapped value, is_null the NULL group of a keep-unmatched
+ *     binding.  The packed key still holds at most 63 bits.
+ * Default (inner join), exactly as a key-map binding: a selected row whose
+ * mapped value is NULL leaves the scan's selection, so count(*) and every
+ * other aggregate of the call loses it; row groups are pruned as under IN_SET
+ * on the map's keys (an all-NULL chunk, a zone map without a map key; an empty
+ * map prunes everything: zero groups, NULL sums, no device work) and count in
+ * fls_scan_pruned.  FLS_VALUEMAP_KEEP_UNMATCHED (left join): the selection is
+ * left alone and nothing is pruned; the mapped column is simply NULL there:
+ * operands skip the row, COUNT(mapped) does not count it, as a hash key it
+ * forms the NULL group.
+ * Only the bindings a call names are probed: a binding that is set but unused
+ * narrows nothing and prunes nothing, so every call that names none behaves as
+ * if none were set.  Each binding holds a reference to its map: freeing the
+ * handle before the scan is fine.  The values are gathered on the GPU per
+ * selected row (csrc/fls_mapval.hip) into a derived 8-byte column in HBM,
+ * which the reduce kernels read like any other; the bit is 0x40000000 so that
+ * FLS_KEY_MAPPED keeps its meaning in fls_aggregate_grouped's keys.
+ * The overflow bounds of SUM_PRODUCT and SUM_EXPR take max(|value_min|,
+ * |value_max|) of the map for a mapped operand (0 for an empty map).
+ * FLS_ERR_ARG before any device work.  The setter, naming "value binding i":
+ * n > 4, a column out of range, a VARCHAR / BLOB / FLOAT / DOUBLE column or a
+ * DECIMAL wider than 64 bits, a map whose key kind differs from the column's
+ * signedness, a handle that is not a live value map (a key-set or key-map
+ * handle does not resolve), unknown flag bits.  The calls, naming "aggregate
+ * i", "expression i" or "key q": FLS_COL_MAPPED | i with no binding i, the
+ * same binding as two hash keys, and FLS_COL_MAPPED anywhere else: a key of
+ * fls_aggregate_grouped (a key map gives low-cardinality mapped keys),
+ * fls_topn's order key, a filter, condition or alternative term's col /
+ * key_col, fls_keyset_from_scan's column.  A delivered column cannot name one:
+ * col_mask holds a byte per table column, so the bit has no place there (the
+ * Python column lists refuse it by name).  Not in the reference. */
+#define FLS_COL_MAPPED 0x40000000u            /* col = FLS_COL_MAPPED | i : value binding i of the table */
+#define FLS_VALUEMAP_KEEP_UNMATCHED 1u        /* left join: the mapped column is NULL at unmatched rows */
+typedef struct fls_value_binding { uint32_t col; uint32_t flags; uint64_t map; /* the fls_valuemap handle */ } fls_value_binding;
+int fls_aggregate_value_bindings(fls_table *t, const fls_value_binding *b, uint32_t n);
 /* ORDER BY key [DESC] LIMIT k selected on the GPU: the k best rows of row
  * groups [rg_begin, rg_end) under the filter set by fls_scan_filter, ordered
  * by one key column; their global row indices and the values of the columns
