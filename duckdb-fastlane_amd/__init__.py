@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from pathlib import Path
 
 import numpy as np
@@ -200,6 +201,12 @@ class ValueMapInfo(C.Structure):   # fls_valuemap_info_t
                 ("value_max", C.c_uint64), ("empty", C.c_uint64)]
 
 
+class MapBuildInfo(C.Structure):   # fls_map_build_info_t
+    _fields_ = [("rows_selected", C.c_uint64), ("keys", C.c_uint64), ("scratch_bytes", C.c_uint64),
+                ("d2h_bytes", C.c_uint64), ("base", C.c_uint64), ("span", C.c_uint64),
+                ("rowgroups_read", C.c_uint32), ("rowgroups_pruned", C.c_uint32)]
+
+
 class KeyBinding(C.Structure):     # fls_key_binding
     _fields_ = [("col", C.c_uint32), ("flags", C.c_uint32), ("map", C.c_uint64)]
 
@@ -311,7 +318,7 @@ class AggregateValue(C.Structure):
 
 # fls_key_kind / fls_group_key (include/flsgpu.h)
 KEYV_NULL, KEYV_INT, KEYV_STRING = 0, 1, 2
-ERR_LIMIT = -8
+ERR_ARG, ERR_LIMIT = -3, -8
 
 
 class GroupKey(C.Structure):
@@ -406,6 +413,10 @@ _sig("fls_valuemap_create", C.c_int, _P, _P, _P, C.c_uint64, C.c_int, C.c_int, C
 _sig("fls_valuemap_free", None, _P)
 _sig("fls_valuemap_info", C.c_int, _P, C.POINTER(ValueMapInfo))
 _sig("fls_valuemap_lookup", C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64))
+_sig("fls_valuemap_from_scan", C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P),
+     C.POINTER(MapBuildInfo))
+_sig("fls_keymap_from_scan", C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P),
+     C.POINTER(MapBuildInfo))
 _sig("fls_aggregate_value_bindings", C.c_int, _P, C.POINTER(ValueBinding), C.c_uint32)
 _sig("fls_aggregate_key_bindings", C.c_int, _P, C.POINTER(KeyBinding), C.c_uint32)
 _sig("fls_aggregate", C.c_int, _P, C.POINTER(AggregateSpec), C.c_uint32, C.c_uint32, C.c_uint32,
@@ -878,10 +889,12 @@ def _key_patterns(values, who: str) -> np.ndarray:
 class KeyMap:
     """fls_keymap: the build side of a join whose payload is a GROUP BY code.
     The handle is a token the library looks up; a closed map in a binding is
-    refused, never dereferenced."""
+    refused, never dereferenced.  build_info: the MapBuildInfo of a map
+    Table.keymap built on the GPU (fls_keymap_from_scan), None for a map
+    built on the host."""
 
-    def __init__(self, h, conn):
-        self.h, self.conn = h, conn
+    def __init__(self, h, conn, build_info=None):
+        self.h, self.conn, self.build_info = h, conn, build_info
 
     @property
     def info(self) -> KeyMapInfo:
@@ -910,10 +923,12 @@ class KeyMap:
 class ValueMap:
     """fls_valuemap: the build side of a join whose payload is a value a row
     is compared with.  The handle is a token the library looks up; a closed
-    map in a filter term is refused, never dereferenced."""
+    map in a filter term is refused, never dereferenced.  build_info: the
+    MapBuildInfo of a map Table.valuemap built on the GPU
+    (fls_valuemap_from_scan), None for a map built on the host."""
 
-    def __init__(self, h, conn):
-        self.h, self.conn = h, conn
+    def __init__(self, h, conn, build_info=None):
+        self.h, self.conn, self.build_info = h, conn, build_info
 
     @property
     def info(self) -> ValueMapInfo:
@@ -1502,16 +1517,55 @@ class Table:
         signed = ci.type in (INT8, INT16, INT32, INT64, DATE, DECIMAL)
         return self.conn.keyset(np.unique(vals), signed=signed, form=form)
 
+    @staticmethod
+    def _wide_decimal(cis) -> bool:
+        # (a DECIMAL wider than 64 bits is no column of the device build)
+        return any(ci.type == DECIMAL and ci.width > 18 for ci in cis)
+
+    def _map_from_scan(self, call, key_col, value_col, filt, form):
+        """The device build of keymap() / valuemap() under filt: (handle,
+        MapBuildInfo), None where the call's gate sends the columns to the
+        host route (ERR_LIMIT), or the FlsError of any other failure (for the
+        caller to raise once the filter is cleared)."""
+        self.set_filter(filt or [])
+        try:
+            h, info = _P(), MapBuildInfo()
+            _check(call(self.h, key_col, value_col, 0, self.nrowgroups, form, C.byref(h), C.byref(info)))
+            return h.value, info
+        except FlsError as e:
+            return None if e.code == ERR_LIMIT else e
+        finally:
+            self._clear_filter()
+
     def keymap(self, key_col: int, value_col: int, filt=None, form: int = KEYMAP_AUTO) -> "KeyMap":
         """The build side of a join: the key map key_col -> value_col of two
         integer-like columns of this (dimension) table over the rows filt
         selects; rows with a NULL in either column are left out.  A value
-        outside [0, 65534] raises ValueError.  Use it as ("map", col, keymap)
-        in aggregate_grouped on this or another table of the same connection."""
+        outside [0, 65534] raises ValueError (also where a key has two values
+        as well), a key with two different values raises.  Use it as ("map", col, keymap) in aggregate_grouped on this
+        or another table of the same connection.  Built on the GPU
+        (fls_keymap_from_scan: the selected pairs are collected in an array
+        over the range of the key column's zone maps and compacted there; the
+        map's build_info says what that took); where the call's gate refuses
+        the columns (FlsError ERR_LIMIT), or with FLS_KEYMAP_BUILD=host in the
+        environment, from a filtered scan of both columns on the host.  The
+        map is the same either way."""
         cis = [self.column(c) for c in (key_col, value_col)]
         for c, ci in zip((key_col, value_col), cis):
             if ci.type in STRING_TYPES or ci.type in (FLOAT, DOUBLE) or ci.out_bytes > 8:
                 raise ValueError(f"keymap: column {c} ({TYPE_NAMES.get(ci.type, ci.type)}) is not integer-like")
+        if os.environ.get("FLS_KEYMAP_BUILD", "") != "host" and not self._wide_decimal(cis):
+            got = self._map_from_scan(_lib.fls_keymap_from_scan, key_col, value_col, filt, form)
+            if isinstance(got, FlsError):
+                m = re.search(r"value (-?\d+) of column \d+ is outside \[0, 65534\]", got.msg)
+                if m:
+                    raise ValueError(f"keymap: value {int(m.group(1))} of column {value_col} is outside [0, 65534]")
+                # a key with two values: the host route below checks the values' range over every
+                # selected row first, so columns that hold both faults raise what they always raised
+                if not (got.code == ERR_ARG and "a map is a function" in got.msg):
+                    raise got
+            elif got is not None:
+                return KeyMap(got[0], self.conn, got[1])
         terms = list(filt or []) + [(key_col, "is_not_null", None), (value_col, "is_not_null", None)]
         ks, vs = [], []
         for _, _, _, arrs in self.scan_filtered(terms, cols=sorted({key_col, value_col})):
@@ -1529,13 +1583,23 @@ class Table:
         """The build side of a join: the value map key_col -> value_col of two
         integer-like columns of this (dimension) table over the rows filt
         selects; rows with a NULL in either column are left out, and a key
-        with two different values raises.  A host build, like keymap().  Use
-        it as (a, op, Mapped(col, valuemap)) on this or another table of the
-        same connection."""
+        with two different values raises.  Use it as
+        (a, op, Mapped(col, valuemap)) on this or another table of the same
+        connection.  Built on the GPU like keymap() (fls_valuemap_from_scan;
+        the map's build_info says what that took); where the call's gate
+        refuses the columns (FlsError ERR_LIMIT), or with
+        FLS_VALUEMAP_BUILD=host in the environment, from a filtered scan of
+        both columns on the host.  The map is the same either way."""
         cis = [self.column(c) for c in (key_col, value_col)]
         for c, ci in zip((key_col, value_col), cis):
             if ci.type in STRING_TYPES or ci.type in (FLOAT, DOUBLE) or ci.out_bytes > 8:
                 raise ValueError(f"valuemap: column {c} ({TYPE_NAMES.get(ci.type, ci.type)}) is not integer-like")
+        if os.environ.get("FLS_VALUEMAP_BUILD", "") != "host" and not self._wide_decimal(cis):
+            got = self._map_from_scan(_lib.fls_valuemap_from_scan, key_col, value_col, filt, form)
+            if isinstance(got, FlsError):
+                raise got
+            if got is not None:
+                return ValueMap(got[0], self.conn, got[1])
         terms = list(filt or []) + [(key_col, "is_not_null", None), (value_col, "is_not_null", None)]
         ks, vs = [], []
         for _, _, _, arrs in self.scan_filtered(terms, cols=sorted({key_col, value_col})):

@@ -645,6 +645,7 @@ enum class Reduce {
     TopN,            // fls_topn: per-row-group candidate lists (enqueue_topn)
     HashAggregate,   // fls_aggregate_hashed: every batch into the pipeline's table in HBM (enqueue_hash_aggregate)
     KeySet,          // fls_keyset_from_scan: every batch's keys into the GPU's collecting bitmap (enqueue_keyset_build)
+    MapBuild,        // fls_valuemap_from_scan / fls_keymap_from_scan: every batch's pairs into the GPU's collecting array (enqueue_mapbuild)
 };
 
 // The collecting range and bitmaps of a key-set build (fls_scan_keyset.hip):
@@ -657,6 +658,19 @@ struct KeyBuildPlan {
     uint64_t base = 0, span = 0;
     bool window = true;                  // clustered words go through the wave's LDS window
     std::vector<uint32_t *> bitmaps;     // per pipeline, in HBM (NULL: the pipeline reads no row group)
+};
+
+// The columns, the collecting range and the collecting arrays of a map build
+// (fls_scan_mapbuild.hip): slot key - base of an array over
+// [base, base + span], span < kValuemapMaxSpan, takes the row's value.  The
+// arrays belong to the call, one per GPU its row groups shard over (slots[g]
+// for ScanCtx::devs[g]; pipelines on one GPU share theirs), span + 4 entries
+// each (the last three: the conflict cells), allocated and filled with 0xFF bytes
+// before scan_start.
+struct MapBuildPlan {
+    uint32_t key_col = 0, value_col = 0;
+    uint64_t base = 0, span = 0;
+    std::vector<uint64_t *> slots;       // per pipeline, in HBM (NULL: the pipeline reads no row group)
 };
 
 // The packed key and the tables of a hash aggregate (fls_scan_hashagg.hip):
@@ -706,9 +720,10 @@ struct ScanPlan {
     const fls_order_key *order = nullptr;           // Reduce::TopN: the key and
     uint32_t k = 0;                                 // ... how many rows
     const KeyBuildPlan *keybuild = nullptr;         // Reduce::KeySet: the key column, the range and the bitmaps
+    const MapBuildPlan *mapbuild = nullptr;         // Reduce::MapBuild: the two columns, the range and the arrays
     // exactly these row groups (ascending, inside the range) instead of
     // pruning the range: fls_topn's late materialisation, and the survivors
-    // fls_keyset_from_scan took its range from
+    // fls_keyset_from_scan and the map builds took their range from
     const std::vector<uint32_t> *only = nullptr;
 };
 
@@ -745,8 +760,11 @@ struct ScanCtx {
     // meet in the plan's bitmaps; their per-vector counts ride in the HostBatch.
     // Such a scan always has a mask, as one with a binding has.
     KeyBuildPlan keybuild;
+    // map build (Reduce::MapBuild): the same, with the plan's collecting arrays
+    MapBuildPlan mapbuild;
     bool masked() const {
-        return !terms.empty() || !alts.empty() || !binds.empty() || vused != 0 || reduce == Reduce::KeySet;
+        return !terms.empty() || !alts.empty() || !binds.empty() || vused != 0 || reduce == Reduce::KeySet ||
+               reduce == Reduce::MapBuild;
     }
     // hash aggregate scan (Reduce::HashAggregate): the key layout and the
     // pipelines' tables, and the groups one table may hold
@@ -972,6 +990,14 @@ int enqueue_group_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint
 int enqueue_topn(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);             // fls_scan_topn.hip
 int enqueue_hash_aggregate(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);   // fls_scan_hashagg.hip
 int enqueue_keyset_build(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);     // fls_scan_keyset.hip
+int enqueue_mapbuild(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows, uint64_t in_lo);         // fls_scan_mapbuild.hip
+
+// ---- what the builds from a scan share (fls_scan_keyset.hip) ---------------------
+
+// The collecting range of column c over the row groups rgs, in the key order:
+// the union of their valid zone maps, the physical type's whole range where
+// one of them has none.
+void keybuild_range(const fls_table *t, uint32_t c, const std::vector<uint32_t> &rgs, uint64_t &base, uint64_t &span);
 
 // ---- what the aggregate calls share (fls_scan_agg.hip) ---------------------------
 

@@ -203,6 +203,45 @@ enum : uint32_t { KERR_KEYBUILD = 32768 };
 // set a bit into d_counts (fls_keyset_build.hip).
 hipError_t launch_keyset_build(const DevKeyBuild &p, uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
 
+// The build of a value map or key map from a scan (fls_valuemap_from_scan,
+// fls_keymap_from_scan) as mapbuild_kernel sees a batch: at every selected row
+// where key and value are both valid, the value (in the value order,
+// keyset_ord) goes into slot[key - base] of a collecting array over
+// [base, base + span] that the call's batches on one GPU share.  slot has
+// span + 4 entries, all ones before the first batch: span + 1 slots (span <
+// 2^28) and, from slot[span + 1], the three cells one conflict records its
+// key's d and the two values in (value order).
+struct DevMapBuild {          // 72 B, a kernel argument
+    const uint8_t *key;       // decoded key column of the batch in HBM (row 0 of the batch)
+    const uint8_t *value;     // ... and the value column
+    const uint64_t *vk, *vv;  // as DevTerm::valid, per column
+    const uint64_t *mask;     // the batch's selection mask, 16 words per vector
+    uint64_t *slot;           // the collecting array of the call on this GPU
+    uint64_t base, span;
+    uint32_t nrows;
+    uint8_t obk, obv;         // bytes per decoded key / value
+    uint8_t ksign, vsign;     // keys / values sign-extend to 64 bits; vsign: the value order is signed
+};
+static_assert(sizeof(DevMapBuild) == 72, "DevMapBuild is 72 B");
+// a selected, valid key outside [base, base + span]: the zone maps that gave
+// the range do not bound the data (corrupt or foreign file); it touches nothing
+enum : uint32_t { KERR_MAPBUILD = 262144 };
+// one key with two values among the call's rows on this GPU: no function
+enum : uint32_t { KERR_MAPBUILD_CONFLICT = 524288 };
+// Collects the batch's pairs into p.slot and writes per vector the rows that
+// took part into d_counts (fls_mapbuild.hip).
+hipError_t launch_mapbuild(const DevMapBuild &p, uint32_t *d_counts, uint32_t *d_err, hipStream_t stream);
+// The compaction of a collecting array of n = span + 1 slots: one presence
+// word per 64 slots into presence[(n + 63) / 64] and the present slots of
+// each 1024-slot block counted into block_counts[(n + 1023) / 1024]; then,
+// given the exclusive scan of those counts in block_offsets, the present
+// slots' values (stored patterns again) in ascending slot order into
+// out[0, nout).
+hipError_t launch_mapbuild_presence(const uint64_t *slot, uint64_t n, uint64_t *presence, uint32_t *block_counts,
+                                    hipStream_t stream);
+hipError_t launch_mapbuild_gather(const uint64_t *slot, uint64_t n, const uint64_t *block_offsets, bool vsign,
+                                  uint64_t *out, uint64_t nout, hipStream_t stream);
+
 // One column term (OP_COL_EQ .. OP_COL_GE) as colcmp_kernel sees it, rebuilt
 // per scan batch.  A row stays selected when both values are valid and
 // `a op b` holds: op_holds(op, cmp_int | cmp_uint | cmp_float) over the values

@@ -88,43 +88,27 @@ inline uint16_t keymap_lookup(const KeymapImage &m, uint64_t key) {
     return kKeymapAbsent;
 }
 
-// Builds the map keys[i] -> values[i], i in [0, n): n is checked before keys
-// or values is read.
-inline int keymap_build(const uint64_t *keys, const uint16_t *values, uint64_t n, bool is_signed, uint32_t form,
-                        KeymapImage &out) {
+// The second half of every construction: keys holds the map's distinct keys,
+// ascending in the key order, values their codes in that order, none of them
+// kKeymapAbsent (the sort, the de-duplication and the checks of the values are
+// the caller's: keymap_build below, or the device build of
+// fls_keymap_from_scan, whose compact arrays arrive in key order).  Chooses
+// the form (the auto rule above) and fills max_code and the image.
+inline int keymap_finish_sorted(std::vector<uint64_t> sorted, std::vector<uint16_t> values, bool is_signed, uint32_t form,
+                                KeymapImage &out) {
     if (form > KM_HASH) return KM_BAD_FORM;
-    if (n > kMaxKeysetKeys) return KM_TOO_MANY;
+    const uint64_t nd = sorted.size();
+    if (nd > kMaxKeysetKeys || values.size() != nd) return KM_TOO_MANY;
     out = KeymapImage();
-    std::vector<std::pair<uint64_t, uint16_t>> kv(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        if (values[i] == kKeymapAbsent) {
-            out.bad_key = keys[i];
-            out.bad_a = values[i];
+    out.values = std::move(values);
+    for (uint64_t i = 0; i < nd; ++i) {
+        if (out.values[i] == kKeymapAbsent) {
+            out.bad_key = sorted[i];
+            out.bad_a = out.values[i];
             return KM_BAD_VALUE;
         }
-        kv[i] = {keys[i], values[i]};
+        out.max_code = std::max(out.max_code, out.values[i]);
     }
-    std::sort(kv.begin(), kv.end(), [is_signed](const auto &a, const auto &b) {
-        const uint64_t x = keyset_ord(a.first, is_signed), y = keyset_ord(b.first, is_signed);
-        return x != y ? x < y : a.second < b.second;
-    });
-    kv.erase(std::unique(kv.begin(), kv.end()), kv.end());
-    for (size_t i = 1; i < kv.size(); ++i)
-        if (kv[i].first == kv[i - 1].first) {  // one key, two values: no function
-            out.bad_key = kv[i].first;
-            out.bad_a = kv[i - 1].second;
-            out.bad_b = kv[i].second;
-            return KM_CONFLICT;
-        }
-    const uint64_t nd = kv.size();
-    std::vector<uint64_t> sorted(nd);
-    out.values.resize(nd);
-    for (uint64_t i = 0; i < nd; ++i) {
-        sorted[i] = kv[i].first;
-        out.values[i] = kv[i].second;
-        out.max_code = std::max(out.max_code, kv[i].second);
-    }
-    kv = {};
     const uint64_t span = nd ? sorted.back() - sorted.front() : 0;
     const uint32_t cap_log2 = keyset_cap_log2(nd);
     const bool fits = span < kKeymapMaxSpan;
@@ -164,6 +148,45 @@ inline int keymap_build(const uint64_t *keys, const uint16_t *values, uint64_t n
         v[j] = out.values[i];
     }
     return KM_OK;
+}
+
+// Builds the map keys[i] -> values[i], i in [0, n): n is checked before keys
+// or values is read.
+inline int keymap_build(const uint64_t *keys, const uint16_t *values, uint64_t n, bool is_signed, uint32_t form,
+                        KeymapImage &out) {
+    if (form > KM_HASH) return KM_BAD_FORM;
+    if (n > kMaxKeysetKeys) return KM_TOO_MANY;
+    out = KeymapImage();
+    std::vector<std::pair<uint64_t, uint16_t>> kv(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (values[i] == kKeymapAbsent) {
+            out.bad_key = keys[i];
+            out.bad_a = values[i];
+            return KM_BAD_VALUE;
+        }
+        kv[i] = {keys[i], values[i]};
+    }
+    std::sort(kv.begin(), kv.end(), [is_signed](const auto &a, const auto &b) {
+        const uint64_t x = keyset_ord(a.first, is_signed), y = keyset_ord(b.first, is_signed);
+        return x != y ? x < y : a.second < b.second;
+    });
+    kv.erase(std::unique(kv.begin(), kv.end()), kv.end());
+    for (size_t i = 1; i < kv.size(); ++i)
+        if (kv[i].first == kv[i - 1].first) {  // one key, two values: no function
+            out.bad_key = kv[i].first;
+            out.bad_a = kv[i - 1].second;
+            out.bad_b = kv[i].second;
+            return KM_CONFLICT;
+        }
+    const uint64_t nd = kv.size();
+    std::vector<uint64_t> sorted(nd);
+    std::vector<uint16_t> vals(nd);
+    for (uint64_t i = 0; i < nd; ++i) {
+        sorted[i] = kv[i].first;
+        vals[i] = kv[i].second;
+    }
+    kv = {};
+    return keymap_finish_sorted(std::move(sorted), std::move(vals), is_signed, form, out);
 }
 
 }  // namespace fls

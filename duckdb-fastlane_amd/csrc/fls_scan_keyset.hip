@@ -53,10 +53,6 @@ int enqueue_keyset_build(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_
     return 0;
 }
 
-FLS_ENGINE_END
-
-namespace {
-
 // The collecting range of column c over the row groups rgs, in the set's
 // order: the union of their valid zone maps, the physical type's whole range
 // where one of them has none.
@@ -84,6 +80,10 @@ void keybuild_range(const fls_table *t, uint32_t c, const std::vector<uint32_t> 
     base = lo;
     span = hi - lo;
 }
+
+FLS_ENGINE_END
+
+namespace {
 
 int register_keyset(std::shared_ptr<KeySet> ks, fls_keyset **out) {
     KeySetRegistry &R = keyset_registry();

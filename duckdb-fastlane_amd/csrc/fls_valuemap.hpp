@@ -100,38 +100,25 @@ inline bool valuemap_lookup(const ValuemapImage &m, uint64_t key, uint64_t *valu
     return false;
 }
 
-// Builds the map keys[i] -> values[i], i in [0, n): n is checked before keys
-// or values is read.
-inline int valuemap_build(const uint64_t *keys, const uint64_t *values, uint64_t n, bool key_signed, bool value_signed,
-                          uint32_t form, ValuemapImage &out) {
+// The second half of every construction: keys holds the map's distinct keys,
+// ascending in the key order, values their values in that order (the sort,
+// the de-duplication and the conflict check are the caller's: valuemap_build
+// below, or the device build of fls_valuemap_from_scan, whose compact arrays
+// arrive in key order).  Chooses the form (the auto rule above) and fills
+// vmin / vmax and the image.
+inline int valuemap_finish_sorted(std::vector<uint64_t> sorted, std::vector<uint64_t> values, bool key_signed,
+                                  bool value_signed, uint32_t form, ValuemapImage &out) {
     if (form > VM_HASH) return VM_BAD_FORM;
-    if (n > kMaxKeysetKeys) return VM_TOO_MANY;
+    const uint64_t nd = sorted.size();
+    if (nd > kMaxKeysetKeys || values.size() != nd) return VM_TOO_MANY;
     out = ValuemapImage();
     out.value_signed = value_signed;
-    std::vector<std::pair<uint64_t, uint64_t>> kv(n);
-    for (uint64_t i = 0; i < n; ++i) kv[i] = {keys[i], values[i]};
-    std::sort(kv.begin(), kv.end(), [key_signed](const auto &a, const auto &b) {
-        const uint64_t x = keyset_ord(a.first, key_signed), y = keyset_ord(b.first, key_signed);
-        return x != y ? x < y : a.second < b.second;
-    });
-    kv.erase(std::unique(kv.begin(), kv.end()), kv.end());
-    for (size_t i = 1; i < kv.size(); ++i)
-        if (kv[i].first == kv[i - 1].first) {  // one key, two values: no function
-            out.bad_key = kv[i].first;
-            out.bad_a = kv[i - 1].second;
-            out.bad_b = kv[i].second;
-            return VM_CONFLICT;
-        }
-    const uint64_t nd = kv.size();
-    std::vector<uint64_t> sorted(nd);
-    out.values.resize(nd);
+    out.values = std::move(values);
     for (uint64_t i = 0; i < nd; ++i) {
-        sorted[i] = kv[i].first;
-        const uint64_t v = out.values[i] = kv[i].second;
+        const uint64_t v = out.values[i];
         if (i == 0 || keyset_ord(v, value_signed) < keyset_ord(out.vmin, value_signed)) out.vmin = v;
         if (i == 0 || keyset_ord(v, value_signed) > keyset_ord(out.vmax, value_signed)) out.vmax = v;
     }
-    kv = {};
     const uint64_t span = nd ? sorted.back() - sorted.front() : 0;
     const uint32_t cap_log2 = keyset_cap_log2(nd);
     const bool fits = span < kValuemapMaxSpan;
@@ -175,6 +162,38 @@ inline int valuemap_build(const uint64_t *keys, const uint64_t *values, uint64_t
         v[j] = out.values[i];
     }
     return VM_OK;
+}
+
+// Builds the map keys[i] -> values[i], i in [0, n): n is checked before keys
+// or values is read.
+inline int valuemap_build(const uint64_t *keys, const uint64_t *values, uint64_t n, bool key_signed, bool value_signed,
+                          uint32_t form, ValuemapImage &out) {
+    if (form > VM_HASH) return VM_BAD_FORM;
+    if (n > kMaxKeysetKeys) return VM_TOO_MANY;
+    out = ValuemapImage();
+    out.value_signed = value_signed;
+    std::vector<std::pair<uint64_t, uint64_t>> kv(n);
+    for (uint64_t i = 0; i < n; ++i) kv[i] = {keys[i], values[i]};
+    std::sort(kv.begin(), kv.end(), [key_signed](const auto &a, const auto &b) {
+        const uint64_t x = keyset_ord(a.first, key_signed), y = keyset_ord(b.first, key_signed);
+        return x != y ? x < y : a.second < b.second;
+    });
+    kv.erase(std::unique(kv.begin(), kv.end()), kv.end());
+    for (size_t i = 1; i < kv.size(); ++i)
+        if (kv[i].first == kv[i - 1].first) {  // one key, two values: no function
+            out.bad_key = kv[i].first;
+            out.bad_a = kv[i - 1].second;
+            out.bad_b = kv[i].second;
+            return VM_CONFLICT;
+        }
+    const uint64_t nd = kv.size();
+    std::vector<uint64_t> sorted(nd), vals(nd);
+    for (uint64_t i = 0; i < nd; ++i) {
+        sorted[i] = kv[i].first;
+        vals[i] = kv[i].second;
+    }
+    kv = {};
+    return valuemap_finish_sorted(std::move(sorted), std::move(vals), key_signed, value_signed, form, out);
 }
 
 #ifdef __HIPCC__

@@ -804,6 +804,7 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     if (p.aggs) s.reduce = p.hash ? Reduce::HashAggregate : p.keys ? Reduce::GroupAggregate : Reduce::Aggregate;
     else if (p.order && p.k) s.reduce = Reduce::TopN;
     else if (p.keybuild) s.reduce = Reduce::KeySet;
+    else if (p.mapbuild) s.reduce = Reduce::MapBuild;
     // the delivery options: consumers' scans only (not materialize); a reducing scan delivers nothing
     const bool options = p.delivering_scan && s.reduce == Reduce::None;
     s.dict_codes = options && t->dict_codes;
@@ -830,8 +831,14 @@ int scan_setup(fls_table *t, ScanCtx &s, const ScanPlan &p) {
     s.hash = HashPlan();
     s.max_groups = 0;
     s.keybuild = KeyBuildPlan();
+    s.mapbuild = MapBuildPlan();
     switch (s.reduce) {
     case Reduce::None: break;
+    case Reduce::MapBuild:
+        // a map build decodes the filter's columns, its key and its value column
+        s.mapbuild = *p.mapbuild;
+        s.dmask[s.mapbuild.key_col] = s.dmask[s.mapbuild.value_col] = 1;
+        break;
     case Reduce::KeySet:
         // a key-set build decodes the filter's columns and its key column
         s.keybuild = *p.keybuild;
@@ -1024,6 +1031,7 @@ int stage_validity(fls_table *t, ScanCtx &s, ScanDev &d, Slot &sl, uint64_t rows
         if ((s.vused >> i) & 1) need[s.vbinds[i].col] = 1;
     if (s.reduce == Reduce::TopN) need[s.tkey.col] = 1;
     if (s.reduce == Reduce::KeySet) need[s.keybuild.col] = 1;
+    if (s.reduce == Reduce::MapBuild) need[s.mapbuild.key_col] = need[s.mapbuild.value_col] = 1;
     for (uint32_t c = 0; c < ncols; ++c) {
         bool any = false;
         for (uint32_t r = sl.rg0; need[c] && r < sl.rg0 + sl.nrg; ++r)
@@ -1812,6 +1820,7 @@ static int fill_batch(fls_table *t, ScanCtx &s, ScanDev &d, int si) {
         case Reduce::TopN: rc = enqueue_topn(t, s, d, sl, rows, lo); break;                       // candidate lists
         case Reduce::HashAggregate: rc = enqueue_hash_aggregate(t, s, d, sl, rows, lo); break;    // into the pipeline's table
         case Reduce::KeySet: rc = enqueue_keyset_build(t, s, d, sl, rows, lo); break;             // into the GPU's bitmap
+        case Reduce::MapBuild: rc = enqueue_mapbuild(t, s, d, sl, rows, lo); break;               // into the GPU's array
         }
         if (rc) return rc;
     }
@@ -2038,6 +2047,12 @@ static int scan_acquire(fls_table *t, ScanCtx &s, fls_rowgroup *out) {
         if (err & KERR_KEYBUILD)
             return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a key-set build's key column "
                         "(flags 0x%x)", err);
+        if (err & KERR_MAPBUILD)
+            return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a map build's key column "
+                        "(flags 0x%x)", err);
+        // (fls_valuemap_from_scan / fls_keymap_from_scan name the key from the GPU's conflict cell)
+        if (err & KERR_MAPBUILD_CONFLICT)
+            return fail(FLS_ERR_ARG, "map build: a key is listed with two values: a map is a function (flags 0x%x)", err);
         if (err & KERR_NARROW)
             return fail(FLS_ERR_FORMAT, "corrupt chunk: a value outside its zone map in a narrowed column (flags 0x%x)", err);
         if (err & KERR_HASH_RANGE)

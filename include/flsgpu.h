@@ -819,6 +819,56 @@ int fls_valuemap_info(const fls_valuemap *map, fls_valuemap_info_t *info);
 /* Host probe of the very image a scan uploads: 1 found (*value set), 0 absent. */
 int fls_valuemap_lookup(const fls_valuemap *map, uint64_t key, uint64_t *value);
 
+/* The build side of a join on the GPU: the map key_col -> value_col over the
+ * rows of row groups [rg_begin, rg_end) that the filter and alternatives
+ * currently set on the table select and where both columns are non-NULL --
+ * the map fls_valuemap_create / fls_keymap_create builds from those pairs,
+ * image for image: the same form under the auto rule, every fls_*_info field,
+ * every lookup, every image word.  The kinds follow the columns (signed:
+ * INT*, DATE, DECIMAL; unsigned: UINT*, BOOLEAN); the map belongs to the
+ * table's connection and is used, queried and freed like any other map.
+ * The scan decodes the filter's, the alternatives' and the two columns and
+ * delivers nothing: on each GPU every selected pair goes into slot key - base
+ * of one uint64 array over the union of the key column's zone maps over the
+ * row groups that survive pruning (a row group whose key or value chunk is
+ * all NULL is skipped) with one atomic minimum per row, which also detects a
+ * key with two values exactly (csrc/fls_mapbuild.hip).  The array is then
+ * compacted on the GPU, and the host receives (span + 64) / 64 presence words
+ * and the distinct keys' values, already in key order, per GPU: never the
+ * keys, never a duplicate row, never the array.  That needs
+ *   span + 1 <= 2^28 (kValuemapMaxSpan),
+ *   an array (8 bytes per value of the range) of at most 1 MiB, or no larger
+ *   than the hash image of the surviving row groups' rows would be (the auto
+ *   rule's own comparison of the dense form against the hash form), and
+ *   a value column that cannot hold the all-ones pattern of its order
+ *   (INT64_MAX signed, UINT64_MAX unsigned), which marks an untouched slot:
+ *   narrower than 8 bytes, or every surviving row group with a zone map
+ *   whose maximum is below it;
+ * otherwise FLS_ERR_LIMIT before any device work, the message stating the
+ * numbers: build the map from a filtered scan and fls_*map_create.
+ * No surviving row group gives the empty map without device work.
+ * FLS_ERR_ARG before any device work, naming the column: a mapped column, a
+ * column out of range, a VARCHAR / BLOB / FLOAT / DOUBLE column, a DECIMAL
+ * wider than 64 bits on either side, a form outside 0..2, a row-group range
+ * outside the table.  FLS_ERR_ARG after the scan: a key with two values (the
+ * message names one such key and ends "a map is a function"; with several,
+ * which one is unspecified); fls_keymap_from_scan: a value outside
+ * [0, 65534] (the smallest if it is negative, otherwise the largest).
+ * FLS_ERR_FORMAT: a decoded key outside the zone maps that gave the range
+ * (it touches nothing).  Not in the reference. */
+typedef struct fls_map_build_info_t {
+    uint64_t rows_selected;     /* selected rows with key and value both valid */
+    uint64_t keys;              /* distinct keys in the finished map */
+    uint64_t scratch_bytes;     /* collecting array, per device */
+    uint64_t d2h_bytes;         /* everything the build copied to the host */
+    uint64_t base, span;        /* collecting range of the key column */
+    uint32_t rowgroups_read, rowgroups_pruned;
+} fls_map_build_info_t;
+int fls_valuemap_from_scan(fls_table *t, uint32_t key_col, uint32_t value_col, uint32_t rg_begin, uint32_t rg_end,
+                           int form, fls_valuemap **out, fls_map_build_info_t *info /* may be NULL */);
+int fls_keymap_from_scan(fls_table *t, uint32_t key_col, uint32_t value_col, uint32_t rg_begin, uint32_t rg_end,
+                         int form, fls_keymap **out, fls_map_build_info_t *info /* may be NULL */);
+
 /* Mapped GROUP BY keys.  fls_aggregate_key_bindings sets the table's bindings
  * (copied and replaced as a whole; n <= 4; n = 0 clears; sticky like
  * fls_aggregate_exprs): binding i says "probe map with column col".  In the
